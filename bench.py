@@ -41,6 +41,9 @@ the slowest rank and rank 0's gap to it) and `exchange.exchange_ms`.  Every rend
 waits longer names the step on stderr and exits non-zero.  Every cross-check of the line (`matches_*`, `same_*`,
 `verified_*`) is enforced: if one is false the line carries "parity_ok": false and the exit code is 3.
 
+`--dump-outputs DIR` writes, after the timed steps, the headline workload's indices and distances of the last timed
+step to DIR (see dump_outputs), so that two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -292,6 +295,25 @@ def load_traffic(kernel_key):
         return None, None
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(pkg, out_dir, idx, keys):
+    """--dump-outputs: what the timed path handed its caller in the last timed step — the int32 indices and the packed
+    keys — as DIR/indices.npy (float64: every int32 exactly) and DIR/distances.npy (float32: V0's squared distance of
+    each query's nearest ref, unpacked from the keys by the library).  Inputs are the seeded synthetic clouds, so two
+    builds given the same arguments can be compared file for file."""
+    dist = pkg.keys_unpack(keys, return_distances=True)[1]
+    torch.cuda.synchronize()
+    arrays = {"indices": idx.cpu().numpy().astype(np.float64), "distances": dist.cpu().numpy().astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_CAP_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class Ctx:
     """What one rank needs to run workloads."""
 
@@ -517,7 +539,12 @@ def main():
     ap.add_argument("--rendezvous-timeout", type=float, default=240.0,
                     help="N > 1: seconds a rank waits in process-group set-up, communicator creation or the first "
                          "collective before it names the step on stderr and exits non-zero (0: unbounded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline workload's results of the last timed step as "
+                         "DIR/indices.npy (float64) and DIR/distances.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -593,6 +620,8 @@ def main():
 
     ctx = Ctx(pkg, dev, rank, world, dist, comm, args.rehearse_one_gpu, args.rendezvous_timeout)
     out, idx, q, r, ix, keys = run_workload(ctx, args.workload, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(pkg, args.dump_outputs, idx, keys)
     m, n_local, k, dtype = WORKLOADS[args.workload]
     n_total = n_local * world
 

@@ -1085,6 +1085,32 @@ def test_bench_self_launch_rehearsal():
     assert d["exchange"]["exchange_ms"]["payload_bytes"] == 8 * d["config"]["m"] and d["parity_ok"] is True
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs(orc, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's indices and distances, index-for-index and bit-for-bit
+    V0's answer for the workload's seeded inputs (queries then refs of generator stream 1000); --steps is the number of
+    timed steps the line reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--workload", "c1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         cwd=root, capture_output=True, text=True, timeout=500)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    m, n, k = d["config"]["m"], d["config"]["n"], d["config"]["k"]
+    q = orc.rng_uniform(m * k, 1000, 0).reshape(m, k)
+    r = orc.rng_uniform(n * k, 1000, m * k).reshape(n, k)
+    want_idx, want_dist = orc.v0_search(q, r, threads=8)
+    idx = np.load(tmp_path / "indices.npy")
+    dist = np.load(tmp_path / "distances.npy")
+    assert idx.dtype == np.float64 and dist.dtype == np.float32 and idx.shape == dist.shape == (m,)
+    assert np.array_equal(idx, want_idx.astype(np.float64))
+    assert np.array_equal(_bits(dist), _bits(want_dist))
+
+
 def test_search_indices_fused_unpack_and_k1a_rearm(pkg, orc):
     """nns_index_search_indices: keys + unpacked indices / distances from one call on every path, and K1a's
     in-kernel second stage across repeated launches on the same index (its arrival counters must re-arm),
@@ -1637,14 +1663,17 @@ def test_library_never_waits_for_foreign_streams(pkg, orc):
 
     work()                                   # warm: code objects, pool, pinned scratch, library streams
     torch.cuda.synchronize()
-    # The runtime multiplexes HIP streams onto a few hardware queues (four by default), and work behind the foreign
-    # kernel on ITS queue waits for it whatever a library does: which of torch's pooled side streams shares a queue
-    # with one of the library's streams is the runtime's business.  A device-wide synchronisation, on the other hand,
-    # waits for EVERY foreign stream.  So: up to four foreign streams in turn (consecutive pool streams land on
-    # different queues); the library is clean if for at least one of them nothing waited.
+    # The runtime multiplexes HIP streams onto a few hardware queues, and work that lands on the queue of the foreign
+    # kernel runs behind it whatever a library does: with a default-priority foreign stream, whether one of the
+    # library's streams shares its queue depends on how many streams the process has made so far (a clean-checkout run
+    # of the whole suite saw that on four pool streams in a row).  The runtime keeps separate queues per priority
+    # level, and the library's streams and the default stream are all of default priority, so the foreign kernel runs
+    # on a high-priority stream: nothing of the library can queue behind it, and ANY wait is the library's own.  Two
+    # such streams in turn; neither may be waited for.
     outcomes = []
-    for attempt in range(4):
-        side = torch.cuda.Stream()           # torch's side streams are hipStreamNonBlocking
+    for attempt in range(2):
+        side = torch.cuda.Stream(priority=-1)    # torch's side streams are hipStreamNonBlocking
+        assert side.priority < 0, f"no high-priority stream (priority {side.priority})"
         done = torch.cuda.Event()
         with torch.cuda.stream(side):
             torch.cuda._sleep(int(4e9))      # a foreign kernel that spins for ~1.7 s
@@ -1655,10 +1684,8 @@ def test_library_never_waits_for_foreign_streams(pkg, orc):
         side.synchronize()
         spans = [(n1, round(1e3 * (t1 - t0), 2)) for (n0, t0), (n1, t1) in zip(marks, marks[1:])]
         outcomes.append((still_running, round(marks[-1][1] - marks[0][1], 3), spans))
-        if still_running and marks[-1][1] - marks[0][1] < 1.0:
-            break
-    assert any(ok and dt < 1.0 for ok, dt, _ in outcomes), \
-        f"the library waited for the application's stream on every attempt; (still running, seconds, ms per operation): {outcomes}"
+    assert all(ok and dt < 1.0 for ok, dt, _ in outcomes), \
+        f"the library waited for the application's stream; (still running, seconds, ms per operation): {outcomes}"
 
 
 def test_entry_points_restore_the_current_device(pkg, orc):
