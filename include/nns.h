@@ -246,6 +246,41 @@ int nns_keys_min(nns_key *inout_dev, const nns_key *other_dev, int m, void *stre
 int nns_keys_unpack(const nns_key *keys_dev, int m, int *idx_dev,
                     float *dist_dev, void *stream);
 
+/* ---- k nearest neighbours (top-K) --------------------------------------------
+ * Semantics: for query i, the kn references with the smallest V0 distance (the value nns_index_search computes:
+ * sum_{t ascending} fl(fl(q - r)^2), un-contracted fp32 from 0), ordered by ascending (distance, global index) —
+ * the first kn entries of a stable sort by V0 distance, which is plain key order.  A NaN or +INF distance is never
+ * selected (V0's rule, in every slot).  When fewer than kn references are selectable (n < kn, non-finite data) the
+ * row is padded with NNS_KEY_NONE, which nns_keys_topk_unpack turns into index -1 and distance +INF.  Distances are
+ * bit-equal to V0's; indices are global (index_base added).  kn = 1 gives keys bit-identical to nns_index_search.
+ * Supported: 1 <= kn <= NNS_TOPK_MAX (larger: NNS_ERR_UNSUPPORTED; kn <= 0: NNS_ERR_INVALID), fp32 and bf16 points,
+ * every k the exact path accepts (k <= 16384).  The exact scan (K6) runs whatever path the index was created for;
+ * its ref-split workspace (at most 256 MiB) belongs to the index and grows on demand. */
+#define NNS_TOPK_MAX 256
+
+/* keys_dev[m][kn] = the kn nearest refs of each query as packed keys, ascending.  q_dev has the index's dtype.
+ * Reads the index's point-major refs.  nns_index_stats then reports NNS_PATH_EXACT (with NNS_PROFILE, exact_ms /
+ * total_ms cover the scan and merge).  Same one-index-per-stream rule as nns_index_search. */
+int nns_index_search_topk(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, void *stream);
+/* Per row i of [m][kn]: inout[i] = the kn smallest keys of the union of the ascending rows inout[i] and other[i]
+ * (shards with disjoint index ranges): the top-K form of nns_keys_min. */
+int nns_keys_topk_merge(nns_key *inout_dev, const nns_key *other_dev, int m, int kn, void *stream);
+/* idx_dev[m][kn] = index of each key (-1 for NNS_KEY_NONE); dist_dev (optional) = its fp32 distance (+INF for
+ * NNS_KEY_NONE). */
+int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, float *dist_dev, void *stream);
+/* Whole calls: host buffers, idx_out[m][kn], dist_out[m][kn] optional.  num_shards > 1: the V8/V9 contiguous split
+ * searched one after another on the one device and merged with nns_keys_topk_merge (as nns_search_f32_ex).  flags:
+ * NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE; any other: NNS_ERR_UNSUPPORTED.  Library stream, no
+ * device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is allocated. */
+int nns_search_f32_topk(int k, int m, int n, const float *s_points, const float *r_points, int kn, int *idx_out,
+                        float *dist_out, int num_shards, unsigned flags, int device);
+int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
+                         int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
+/* Diagnostic (host only, no device needed): the top-K launch geometry for a k-D search of m queries over n refs.
+ * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
+ * split-workspace keys (0 with one split)}. */
+int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
+
 /* Deterministic synthetic clouds: dev[i] = u24(splitmix64(seed, offset+i)) * 2^-24
  * in [0,1) — bit-identical to oracle/v0_oracle.c:nns_rng_fill on the CPU. */
 int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,

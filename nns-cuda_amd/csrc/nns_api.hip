@@ -101,6 +101,10 @@ struct nns_index {
     int exact_ws_m = 0;
     bool exact_ws_fresh = false;   // (re)allocated since the last K1a launch: its arrival counters need zeroing once
 
+    // top-K (K6): per-split sorted lists [splits][m][kn]
+    nns_key *topk_ws = nullptr;
+    size_t topk_ws_keys = 0;
+
     // NNS_PROFILE: a ring of event sets, one per search (refresh + search = one step), so that a
     // caller can time many steps back to back and read the averages once, without a device
     // synchronisation inside every step
@@ -209,7 +213,7 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     // reusable when that work has completed.  No host wait — an application's kernels on other streams (or this
     // index's own, still running) are not waited for.  (Round 2: hipDeviceSynchronize() here.)
     void *const blocks[] = {ix->r_own, ix->rimg, ix->rnorm, ix->mean, ix->mean_ws, ix->scal, ix->qimg, ix->qnorm,
-                            ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws};
+                            ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws, ix->topk_ws};
     if (stream_idle)
         for (void *b : blocks) pool_free(b);
     else
@@ -571,6 +575,217 @@ int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *k
     }
     DeviceScope keep_device;
     return index_search_impl(ix, m, q_dev, ix ? ix->bf16 : 0, keys_dev, stream, idx_dev, dist_dev);
+}
+
+// ---- top-K (K6) ----------------------------------------------------------------------------------------------
+// argument checks shared by the split and whole-call entry points (no device touched)
+static int topk_check_kn(const char *where, int kn)
+{
+    if (kn <= 0) {
+        set_error("%s: kn must be > 0 (kn=%d)", where, kn);
+        return NNS_ERR_INVALID;
+    }
+    if (kn > NNS_TOPK_MAX) {
+        set_error("%s: kn = %d above 256 is not supported", where, kn);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
+static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, hipStream_t st)
+{
+    if (!ix || !q_dev || !keys_dev || m <= 0) {
+        set_error("nns_index_search_topk: m must be > 0 and pointers non-null (m=%d)", m);
+        return NNS_ERR_INVALID;
+    }
+    NNS_TRY(topk_check_kn("nns_index_search_topk", kn));
+    if (m > kMaxPoints) {
+        set_error("nns_index_search_topk: m = %d exceeds NNS_MAX_POINTS (%d)", m, kMaxPoints);
+        return NNS_ERR_INVALID;
+    }
+    TopkPlan p{};
+    NNS_TRY(topk_plan(ix->k, m, ix->n, kn, &p));
+    NNS_TRY(ensure_device_ok(ix->device));
+    ix->last_stream = st;
+    if (p.ws_keys > ix->topk_ws_keys) {
+        // (the old block may still be read by an earlier search of this index: back to the pool behind an event)
+        pool_free_after(ix->topk_ws, st);
+        ix->topk_ws = nullptr;
+        ix->topk_ws_keys = 0;
+        if (pool_alloc(&ix->topk_ws, p.ws_keys * sizeof(nns_key)) != hipSuccess) {
+            set_error("nns_index_search_topk: split workspace allocation failed (%zu keys)", p.ws_keys);
+            return NNS_ERR_NOMEM;
+        }
+        ix->topk_ws_keys = p.ws_keys;
+    }
+    const bool prof = ix->profile;
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
+    NNS_TRY(launch_topk_search(p, ix->k, m, ix->n, kn, q_dev, ix->r_dev, ix->bf16, ix->base, keys_dev, ix->topk_ws, st));
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
+    ix->last_m = m;
+    ix->last_path = NNS_PATH_EXACT;
+    ix->searched = true;
+    profile_advance(ix, NNS_PATH_EXACT);
+    return NNS_OK;
+}
+
+int nns_index_search_topk(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_search_topk_impl(ix, m, q_dev, kn, keys_dev, (hipStream_t)stream);
+}
+
+int nns_keys_topk_merge(nns_key *inout_dev, const nns_key *other_dev, int m, int kn, void *stream)
+{
+    if (!inout_dev || !other_dev || m <= 0) {
+        set_error("nns_keys_topk_merge: m must be > 0 and pointers non-null (m=%d)", m);
+        return NNS_ERR_INVALID;
+    }
+    NNS_TRY(topk_check_kn("nns_keys_topk_merge", kn));
+    return launch_topk_merge(inout_dev, other_dev, m, kn, (hipStream_t)stream);
+}
+
+int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, float *dist_dev, void *stream)
+{
+    if (!keys_dev || !idx_dev || m <= 0) {
+        set_error("nns_keys_topk_unpack: m must be > 0 and pointers non-null (m=%d)", m);
+        return NNS_ERR_INVALID;
+    }
+    NNS_TRY(topk_check_kn("nns_keys_topk_unpack", kn));
+    return launch_topk_unpack(keys_dev, m, kn, idx_dev, dist_dev, (hipStream_t)stream);
+}
+
+int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len)
+{
+    (void)bf16_points;   // (same geometry: bf16 refs are widened as they are read)
+    if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    NNS_TRY(topk_check_kn("nns_plan_topk", kn));
+    if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
+    TopkPlan p{};
+    NNS_TRY(topk_plan(k, m, n, kn, &p));
+    const int64_t wgs = (int64_t)p.qgroups * p.splits;
+    const int64_t ws = (int64_t)p.ws_keys;
+    const int v[6] = {p.qt, p.splits, p.per, wgs > 0x7FFFFFFF ? 0x7FFFFFFF : (int)wgs, p.lds, (int)ws};
+    memcpy(out, v, sizeof(v));
+    return NNS_OK;
+}
+
+static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
+                                 int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const char *where = bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
+    if (k <= 0 || m <= 0 || n <= 0 || !s_points || !r_points || !idx_out) {
+        set_error("%s: k, m, n must be > 0 and pointers non-null (k=%d m=%d n=%d)", where, k, m, n);
+        return NNS_ERR_INVALID;
+    }
+    NNS_TRY(topk_check_kn(where, kn));
+    if (m > kMaxPoints || n > kMaxPoints) {
+        set_error("%s: m = %d / n = %d exceeds NNS_MAX_POINTS (%d)", where, m, n, kMaxPoints);
+        return NNS_ERR_INVALID;
+    }
+    if ((int64_t)k * m > 0x7FFFFFFFll * 4 || (int64_t)k * n > 0x7FFFFFFFll * 4) {
+        set_error("%s: point set too large for one call", where);
+        return NNS_ERR_INVALID;
+    }
+    if ((int64_t)m * kn > 0x7FFFFFFFll * 4) {
+        set_error("%s: m * kn too large for one call", where);
+        return NNS_ERR_INVALID;
+    }
+    const unsigned path = flags & NNS_PATH_MASK;
+    if ((path != NNS_PATH_AUTO && path != NNS_PATH_EXACT) || (flags & ~(unsigned)(NNS_PATH_MASK | NNS_REFS_SOA | NNS_PROFILE))) {
+        set_error("%s: flags 0x%x: top-K accepts the auto / exact path, dimension-major refs and profiling only", where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    {
+        TopkPlan p{};
+        NNS_TRY(topk_plan(k, m, n, kn, &p));   // (k beyond the exact path: before any device work)
+    }
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(device));
+    if (num_shards < 1) num_shards = 1;
+    if (num_shards > n) num_shards = n;   // the reference clamps GPUs to n (core.cu:771-772)
+
+    const size_t rows = (size_t)m * kn;
+    char *q_d = nullptr, *r_d = nullptr, *r_t = nullptr;
+    nns_key *keys = nullptr, *keys_tmp = nullptr;
+    int *idx_d = nullptr;
+    float *dist_d = nullptr;
+    hipStream_t st = lib_stream_acquire();
+    int rc = NNS_OK;
+    do {
+        const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz;
+        if (pool_alloc(&q_d, qb) != hipSuccess || pool_alloc(&r_d, rb) != hipSuccess ||
+            pool_alloc(&keys, rows * sizeof(nns_key)) != hipSuccess ||
+            (num_shards > 1 && pool_alloc(&keys_tmp, rows * sizeof(nns_key)) != hipSuccess) ||
+            pool_alloc(&idx_d, rows * sizeof(int)) != hipSuccess ||
+            (dist_out && pool_alloc(&dist_d, rows * sizeof(float)) != hipSuccess)) {
+            set_error("%s: device allocation failed", where);
+            rc = NNS_ERR_NOMEM;
+            break;
+        }
+        if (hipMemcpyAsync(q_d, s_points, qb, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(r_d, r_points, rb, hipMemcpyHostToDevice, st) != hipSuccess) {
+            set_error("%s: H2D copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+            rc = NNS_ERR_HIP;
+            break;
+        }
+        if (flags & NNS_REFS_SOA) {
+            // dimension-major refs: transpose once on the device, then shard the point-major copy
+            if (pool_alloc(&r_t, rb) != hipSuccess) {
+                set_error("%s: device allocation failed (point-major copy)", where);
+                rc = NNS_ERR_NOMEM;
+                break;
+            }
+            if ((rc = launch_soa_to_aos(k, n, r_d, r_t, (int)esz, st)) != NNS_OK) break;
+            char *tmp = r_d;
+            r_d = r_t;
+            r_t = tmp;
+        }
+        // contiguous ceil(n / shards) ranges (reference split rule core.cu:781-791); the shard indexes skip the
+        // MFMA filter's ref pre-pass (top-K reads the point-major refs only)
+        const unsigned create_flags = NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync;
+        const int per = divup(n, num_shards);
+        for (int s = 0; s < num_shards && rc == NNS_OK; ++s) {
+            const int beg = s * per;
+            const int cnt = ((int64_t)beg + per <= n) ? per : n - beg;
+            if (cnt <= 0) break;
+            nns_key *dst = s == 0 ? keys : keys_tmp;
+            nns_index *ix = nullptr;
+            rc = index_create_impl(&ix, device, k, cnt, r_d + (size_t)beg * k * esz, bf16, beg, create_flags, st);
+            if (rc != NNS_OK) break;
+            rc = index_search_topk_impl(ix, m, q_d, kn, dst, st);
+            if (rc == NNS_OK && s > 0) rc = launch_topk_merge(keys, keys_tmp, m, kn, st);
+            // (its workspace goes back to the pool behind an event on the stream: no wait here)
+            index_destroy_impl(ix, false);
+        }
+        if (rc != NNS_OK) break;
+        if ((rc = launch_topk_unpack(keys, m, kn, idx_d, dist_d, st)) != NNS_OK) break;
+        if (hipMemcpyAsync(idx_out, idx_d, rows * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            (dist_out && hipMemcpyAsync(dist_out, dist_d, rows * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            set_error("%s: kernel execution or D2H copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+            rc = NNS_ERR_HIP;
+        }
+    } while (0);
+    // success: the stream was waited for with the download; error paths: behind an event on the stream
+    void *const blocks[] = {q_d, r_d, r_t, keys, keys_tmp, idx_d, dist_d};
+    if (rc == NNS_OK) for (void *b : blocks) pool_free(b);
+    else pool_free_after(blocks, 7, st);
+    lib_stream_release(st);
+    return rc;
+}
+
+int nns_search_f32_topk(int k, int m, int n, const float *s_points, const float *r_points, int kn, int *idx_out,
+                        float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_topk_host_impl(k, m, n, s_points, r_points, 0, kn, idx_out, dist_out, num_shards, flags, device);
+}
+
+int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
+                         int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_topk_host_impl(k, m, n, s_points, r_points, 1, kn, idx_out, dist_out, num_shards, flags, device);
 }
 
 int nns_index_stats(nns_index *ix, nns_stats *out)

@@ -316,4 +316,20 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
                     DevScalars *scal, int64_t index_base, nns_key *keys, int *amb_list,
                     int *multi_list, hipStream_t st);
 
+// topk_kernels.hip (K6: the kn nearest refs per query, exact)
+struct TopkPlan {
+    int qt;           // queries per workgroup
+    int qgroups;      // grid.x
+    int splits;       // grid.y: contiguous ref ranges, every one non-empty
+    int per;          // refs per split (the last may hold fewer)
+    int lds;          // LDS bytes per workgroup
+    size_t ws_keys;   // split workspace [splits][m][kn] (0 with one split)
+};
+int topk_plan(int k, int m, int n, int kn, TopkPlan *p);
+// keys[m][kn]; ws: p.ws_keys keys (unused with one split)
+int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
+                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st);
+int launch_topk_merge(nns_key *inout, const nns_key *other, int m, int kn, hipStream_t st);
+int launch_topk_unpack(const nns_key *keys, int m, int kn, int *idx, float *dist, hipStream_t st);
+
 }  // namespace nns

@@ -1,0 +1,357 @@
+// topk_kernels.hip — K6: exact k-nearest-neighbour search (the kn nearest refs per query) with V0's arithmetic,
+// and the top-K key utilities (merge of two sorted rows, unpack).
+//
+// K6 scan: lane = ref, a tile of QT queries in LDS read by broadcast (K1b's geometry), each (lane, query) pair one
+// t-ascending V0 chain (v0_step).  Every query owns, in LDS, a sorted list of its kn best packed keys so far and a
+// candidate queue; its threshold (the list's kn-th key, NNS_KEY_NONE while the list fills) is held in registers by
+// every lane.  A lane whose key is below the threshold appends it to the query's queue (LDS atomic counter).  At the
+// end of every round (one ref per lane) the workgroup flushes when some queue holds more than half its capacity
+// (so the next round, at most 256 appends per query, cannot overflow it) and after the last round: the queues are
+// sorted (bitonic, in LDS), merged into the lists by rank, and the thresholds lowered.  With random data appends
+// become rare after the first rounds (about kn ln(refs / kn) per query and split), so the scan costs about what the
+// 1-NN scan does per pair.  Keys are unique within a search (distinct indices), so integer order of the keys is
+// (distance, index) order and every merge below is exact.
+//
+// grid = query groups x ref splits.  One split: the lists are the answer.  Several: every (group, split) writes its
+// sorted list to a workspace [splits][m][kn] and topk_merge_splits_kernel ranks every entry among all the splits'
+// entries of its query (binary searches in the sorted rows) and scatters the kn smallest into place.
+#include "nns_internal.h"
+
+namespace nns {
+
+constexpr int kTopkThreads = 256;
+constexpr int kTopkQueue = 512;                    // queue capacity per query (keys)
+constexpr int kTopkFlushAt = kTopkQueue - kTopkThreads;   // a queue this full is flushed before the next round
+constexpr size_t kTopkLdsMax = 160 * 1024;
+constexpr size_t kTopkWsBudgetKeys = (size_t)32 << 20;   // 256 MiB of split workspace at most
+constexpr int kTopkTargetWgs = 2048;               // about 8 workgroups per CU
+constexpr int kTopkMinPerSplit = 2048;             // refs a split sees at least (so that its list warm-up amortises)
+
+__device__ __forceinline__ float tk_ld1(const float *p) { return *p; }
+__device__ __forceinline__ float tk_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
+__device__ __forceinline__ float4 tk_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 tk_ld4(const uint16_t *p)
+{
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 bf16, widened exactly
+    float4 o;
+    o.x = __uint_as_float(v.x << 16);
+    o.y = __uint_as_float(v.x & 0xFFFF0000u);
+    o.z = __uint_as_float(v.y << 16);
+    o.w = __uint_as_float(v.y & 0xFFFF0000u);
+    return o;
+}
+
+// number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
+__device__ __forceinline__ int tk_rank(const nns_key *a, int len, nns_key v, bool or_equal)
+{
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const nns_key x = a[mid];
+        if (x < v || (or_equal && x == v)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+static size_t topk_lds_bytes(int qt, int k, int kn)
+{
+    const size_t keys = (size_t)qt * (2 * kn + kTopkQueue) * sizeof(nns_key);
+    return ((keys + 15) & ~(size_t)15) + (size_t)qt * k * sizeof(float);
+}
+
+// LDS: list[2][QT][kn] (ping-pong), queue[QT][kTopkQueue], then the fp32 query tile [QT][k]
+template <int QT, int VEC, typename T>
+__global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, int n, int per, int kn,
+                                                                 const T *__restrict__ q, const T *__restrict__ r,
+                                                                 int64_t index_base, nns_key *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) nns_key tk_smem[];
+    __shared__ int qcnt[QT];
+    nns_key *lists = tk_smem;                              // [2][QT][kn]
+    nns_key *queue = tk_smem + 2 * QT * kn;                // [QT][kTopkQueue]
+    const size_t key_bytes = (size_t)QT * (2 * kn + kTopkQueue) * sizeof(nns_key);
+    float *sq = reinterpret_cast<float *>(reinterpret_cast<char *>(tk_smem) + ((key_bytes + 15) & ~(size_t)15));
+    const int tid = threadIdx.x;
+    const int q0 = blockIdx.x * QT;
+    const int j0 = blockIdx.y * per;
+    const int j1 = (int64_t)j0 + per < n ? j0 + per : n;
+
+    for (int e = tid; e < QT * k; e += kTopkThreads) {
+        const int u = e / k, t = e - u * k;
+        sq[e] = q0 + u < m ? tk_ld1(q + (size_t)(q0 + u) * k + t) : 0.0f;
+    }
+    for (int e = tid; e < 2 * QT * kn; e += kTopkThreads) lists[e] = NNS_KEY_NONE;
+    if (tid < QT) qcnt[tid] = 0;
+    __syncthreads();
+
+    int cur = 0;   // which half of the ping-pong lists holds the current lists
+    nns_key thr[QT];
+#pragma unroll
+    for (int u = 0; u < QT; ++u) thr[u] = NNS_KEY_NONE;
+    const int rounds = (j1 - j0 + kTopkThreads - 1) / kTopkThreads;
+    for (int rd = 0; rd < rounds; ++rd) {
+        const int j = j0 + rd * kTopkThreads + tid;
+        int near_full = 0;
+        if (j < j1) {
+            const T *rj = r + (size_t)j * k;
+            float sum[QT];
+#pragma unroll
+            for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
+            if (VEC == 4) {
+                for (int t = 0; t < k; t += 4) {
+                    const float4 rv = tk_ld4(rj + t);
+#pragma unroll
+                    for (int u = 0; u < QT; ++u) {
+                        const float4 qv = *reinterpret_cast<const float4 *>(&sq[u * k + t]);   // broadcast
+                        float s = sum[u];
+                        s = v0_step(s, qv.x, rv.x);
+                        s = v0_step(s, qv.y, rv.y);
+                        s = v0_step(s, qv.z, rv.z);
+                        s = v0_step(s, qv.w, rv.w);
+                        sum[u] = s;
+                    }
+                }
+            } else {
+                for (int t = 0; t < k; ++t) {
+                    const float rv = tk_ld1(rj + t);
+#pragma unroll
+                    for (int u = 0; u < QT; ++u) sum[u] = v0_step(sum[u], sq[u * k + t], rv);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < QT; ++u) {
+                const nns_key key = make_key(sum[u], index_base + j);   // NaN / +INF -> NNS_KEY_NONE: never below thr
+                if (key < thr[u]) {
+                    const int pos = atomicAdd(&qcnt[u], 1);
+                    queue[u * kTopkQueue + pos] = key;
+                    near_full |= pos >= kTopkFlushAt;
+                }
+            }
+        }
+        // (the lane whose append crossed the mark knows it: one barrier decides for the whole workgroup)
+        const bool flush = __syncthreads_or(near_full) || rd == rounds - 1;
+        if (!flush) continue;
+
+        // ---- flush: sort the queues, merge them into the lists, lower the thresholds --------------------------
+        int maxc = 0;
+#pragma unroll
+        for (int u = 0; u < QT; ++u) maxc = qcnt[u] > maxc ? qcnt[u] : maxc;
+        if (maxc == 0) continue;   // (workgroup-uniform: nothing changes qcnt between the barrier and here)
+        int P = 1;
+        while (P < maxc) P <<= 1;   // <= kTopkQueue
+        nns_key *src = lists + cur * QT * kn, *dst = lists + (cur ^ 1) * QT * kn;
+        for (int e = tid; e < QT * P; e += kTopkThreads) {
+            const int u = e / P, i = e - u * P;
+            if (i >= qcnt[u]) queue[u * kTopkQueue + i] = NNS_KEY_NONE;
+        }
+        for (int e = tid; e < QT * kn; e += kTopkThreads) dst[e] = NNS_KEY_NONE;
+        __syncthreads();
+        for (int size = 2; size <= P; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                for (int e = tid; e < QT * (P >> 1); e += kTopkThreads) {
+                    const int u = e / (P >> 1), i = e - u * (P >> 1);
+                    const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+                    nns_key *qq = queue + u * kTopkQueue;
+                    const nns_key a = qq[lo], b = qq[hi];
+                    const bool up = (lo & size) == 0;
+                    if ((a > b) == up) {
+                        qq[lo] = b;
+                        qq[hi] = a;
+                    }
+                }
+                __syncthreads();
+            }
+        // rank merge: an old entry goes before equal queue entries (there are none: keys are unique)
+        for (int e = tid; e < QT * kn; e += kTopkThreads) {
+            const int u = e / kn, i = e - u * kn;
+            const nns_key a = src[e];
+            if (a == NNS_KEY_NONE) continue;
+            const int rk = i + tk_rank(queue + u * kTopkQueue, qcnt[u], a, false);
+            if (rk < kn) dst[u * kn + rk] = a;
+        }
+        const int qtake = P < kn ? P : kn;   // a queue entry at position >= kn cannot land in the first kn
+        for (int e = tid; e < QT * qtake; e += kTopkThreads) {
+            const int u = e / qtake, i = e - u * qtake;
+            if (i >= qcnt[u]) continue;
+            const nns_key b = queue[u * kTopkQueue + i];
+            const int rk = i + tk_rank(src + u * kn, kn, b, true);
+            if (rk < kn) dst[u * kn + rk] = b;
+        }
+        __syncthreads();
+        cur ^= 1;
+#pragma unroll
+        for (int u = 0; u < QT; ++u) thr[u] = dst[u * kn + kn - 1];
+        __syncthreads();   // every thread has read the counts and thresholds before they change
+        if (tid < QT) qcnt[tid] = 0;
+        __syncthreads();
+    }
+
+    const nns_key *fin = lists + cur * QT * kn;
+    for (int e = tid; e < QT * kn; e += kTopkThreads) {
+        const int u = e / kn, i = e - u * kn;
+        if (q0 + u < m) out[((size_t)blockIdx.y * m + q0 + u) * kn + i] = fin[e];
+    }
+}
+
+// grid (query, split): entry i of split s's row goes to rank i + #(entries of lower splits <= it) + #(entries of
+// higher splits < it) — a stable merge, so equal keys (none within one search) would still land in distinct slots
+__global__ __launch_bounds__(kTopkThreads) void topk_merge_splits_kernel(const nns_key *__restrict__ ws, int m, int kn,
+                                                                         int splits, nns_key *__restrict__ out)
+{
+    const int qi = blockIdx.x, s = blockIdx.y, i = threadIdx.x;
+    nns_key *orow = out + (size_t)qi * kn;
+    if (s == 0) {
+        // slots behind the last selectable entry hold NNS_KEY_NONE
+        int total = 0;
+        for (int s2 = 0; s2 < splits; ++s2) total += tk_rank(ws + ((size_t)s2 * m + qi) * kn, kn, NNS_KEY_NONE - 1, true);
+        for (int p = total + i; p < kn; p += blockDim.x) orow[p] = NNS_KEY_NONE;
+    }
+    if (i >= kn) return;
+    const nns_key v = ws[((size_t)s * m + qi) * kn + i];
+    if (v == NNS_KEY_NONE) return;
+    int rk = i;
+    for (int s2 = 0; s2 < splits && rk < kn; ++s2)
+        if (s2 != s) rk += tk_rank(ws + ((size_t)s2 * m + qi) * kn, kn, v, s2 < s);
+    if (rk < kn) orow[rk] = v;
+}
+
+// nns_keys_topk_merge: one workgroup per row, both rows staged in LDS (the output overwrites `inout`)
+__global__ __launch_bounds__(kTopkThreads) void topk_merge_pair_kernel(nns_key *__restrict__ inout,
+                                                                       const nns_key *__restrict__ other, int kn)
+{
+    __shared__ nns_key a[NNS_TOPK_MAX];
+    __shared__ nns_key b[NNS_TOPK_MAX];
+    const size_t row = (size_t)blockIdx.x * kn;
+    const int i = threadIdx.x;
+    if (i < kn) {
+        a[i] = inout[row + i];
+        b[i] = other[row + i];
+    }
+    __syncthreads();
+    if (i >= kn) return;
+    const int na = tk_rank(a, kn, NNS_KEY_NONE - 1, true), nb = tk_rank(b, kn, NNS_KEY_NONE - 1, true);
+    if (i >= na + nb) inout[row + i] = NNS_KEY_NONE;
+    if (i < na) {
+        const int rk = i + tk_rank(b, nb, a[i], false);
+        if (rk < kn) inout[row + rk] = a[i];
+    }
+    if (i < nb) {
+        const int rk = i + tk_rank(a, na, b[i], true);
+        if (rk < kn) inout[row + rk] = b[i];
+    }
+}
+
+__global__ void topk_unpack_kernel(const nns_key *__restrict__ keys, size_t count, int *__restrict__ idx,
+                                   float *__restrict__ dist)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += stride) {
+        const nns_key kx = keys[e];
+        idx[e] = kx == NNS_KEY_NONE ? -1 : (int)(uint32_t)(kx & 0xFFFFFFFFull);
+        if (dist) dist[e] = __uint_as_float((uint32_t)(kx >> 32));   // NNS_KEY_NONE -> +INF
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+int topk_plan(int k, int m, int n, int kn, TopkPlan *p)
+{
+    if (k <= 0 || m <= 0 || n <= 0 || kn <= 0) return NNS_ERR_INVALID;
+    if (kn > NNS_TOPK_MAX) {
+        set_error("top-K: kn = %d above 256", kn);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if ((size_t)k * sizeof(float) > 64 * 1024) {
+        set_error("top-K: k = %d exceeds the LDS query tile (k <= 16384)", k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    // query-tile width: 16 queries while the lists are short, 8 beyond; fewer if the query tile or LDS runs out
+    int qt = kn <= 16 ? 16 : 8;
+    while (qt > 1 && ((size_t)qt * k * sizeof(float) > 64 * 1024 || topk_lds_bytes(qt, k, kn) > kTopkLdsMax)) qt >>= 1;
+    while (qt > 1 && qt / 2 >= m) qt >>= 1;
+    const int qgroups = divup(m, qt);
+    // ref splits: enough workgroups to fill the chip, every split worth its list warm-up, workspace within budget
+    int64_t splits = divup(kTopkTargetWgs, qgroups);
+    const int64_t min_per = kn * 16 > kTopkMinPerSplit ? kn * 16 : kTopkMinPerSplit;
+    const int64_t by_refs = divup64(n, min_per);
+    if (splits > by_refs) splits = by_refs;
+    const int64_t by_ws = (int64_t)(kTopkWsBudgetKeys / ((size_t)m * kn));
+    if (splits > by_ws) splits = by_ws;
+    if (splits > 65535) splits = 65535;
+    if (splits < 1) splits = 1;
+    // whole rounds per split; recount so that no split is empty
+    int64_t per = divup64(divup64(n, splits), kTopkThreads) * kTopkThreads;
+    splits = divup64(n, per);
+    p->qt = qt;
+    p->qgroups = qgroups;
+    p->splits = (int)splits;
+    p->per = (int)(per < n ? per : n);
+    if (splits == 1) p->per = n;
+    p->lds = (int)(topk_lds_bytes(qt, k, kn) + qt * sizeof(int));
+    p->ws_keys = splits > 1 ? (size_t)splits * m * kn : 0;
+    return NNS_OK;
+}
+
+template <int QT, typename T>
+static int launch_topk_scan_t(const TopkPlan &p, int k, int m, int n, int kn, const T *q, const T *r, int64_t base,
+                              nns_key *out, hipStream_t st)
+{
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    const size_t lds = topk_lds_bytes(QT, k, kn);
+    const dim3 grid(p.qgroups, p.splits);
+    auto kern = vec ? topk_scan_kernel<QT, 4, T> : topk_scan_kernel<QT, 1, T>;
+    if (lds > 48 * 1024)
+        NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(kTopkThreads), lds, st, k, m, n, p.per, kn, q, r, base, out);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+template <typename T>
+static int launch_topk_scan(const TopkPlan &p, int k, int m, int n, int kn, const T *q, const T *r, int64_t base,
+                            nns_key *out, hipStream_t st)
+{
+    switch (p.qt) {
+    case 16: return launch_topk_scan_t<16, T>(p, k, m, n, kn, q, r, base, out, st);
+    case 8: return launch_topk_scan_t<8, T>(p, k, m, n, kn, q, r, base, out, st);
+    case 4: return launch_topk_scan_t<4, T>(p, k, m, n, kn, q, r, base, out, st);
+    case 2: return launch_topk_scan_t<2, T>(p, k, m, n, kn, q, r, base, out, st);
+    default: return launch_topk_scan_t<1, T>(p, k, m, n, kn, q, r, base, out, st);
+    }
+}
+
+int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
+                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st)
+{
+    nns_key *scan_out = p.splits > 1 ? ws : keys;
+    if (bf16)
+        NNS_TRY(launch_topk_scan<uint16_t>(p, k, m, n, kn, (const uint16_t *)q, (const uint16_t *)r, base, scan_out, st));
+    else
+        NNS_TRY(launch_topk_scan<float>(p, k, m, n, kn, (const float *)q, (const float *)r, base, scan_out, st));
+    if (p.splits > 1) {
+        const int threads = (kn + 63) / 64 * 64;
+        hipLaunchKernelGGL(topk_merge_splits_kernel, dim3(m, p.splits), dim3(threads), 0, st, ws, m, kn, p.splits, keys);
+        NNS_HIP(hipGetLastError());
+    }
+    return NNS_OK;
+}
+
+int launch_topk_merge(nns_key *inout, const nns_key *other, int m, int kn, hipStream_t st)
+{
+    const int threads = (kn + 63) / 64 * 64;
+    hipLaunchKernelGGL(topk_merge_pair_kernel, dim3(m), dim3(threads), 0, st, inout, other, kn);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+int launch_topk_unpack(const nns_key *keys, int m, int kn, int *idx, float *dist, hipStream_t st)
+{
+    const size_t count = (size_t)m * kn;
+    size_t blocks = (count + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(topk_unpack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, keys, count, idx, dist);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+}  // namespace nns

@@ -47,7 +47,10 @@ ABI_SYMBOLS = (
     "nns_index_near_ties", "nns_tau_consts", "nns_index_search_indices", "nns_selftest_lane_share", "nns_plan_filter", "nns_plan_exact",
     "nns_comm_unique_id", "nns_comm_create", "nns_comm_size", "nns_comm_allreduce_min", "nns_comm_destroy",
     "nns_multi_last_exchange_ranks",
+    "nns_index_search_topk", "nns_keys_topk_merge", "nns_keys_topk_unpack", "nns_search_f32_topk",
+    "nns_search_bf16_topk", "nns_plan_topk",
 )
+NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
 
@@ -116,6 +119,12 @@ def _load() -> ctypes.CDLL:
     lib.nns_keys_unpack.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
     lib.nns_fill_uniform.argtypes = [c_vp, c_sz, c_u64, c_u64, c_vp]
     lib.nns_selftest_mfma.argtypes = [c_int, c_int, c_vp, c_vp, c_vp, c_vp]
+    lib.nns_index_search_topk.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp]
+    lib.nns_keys_topk_merge.argtypes = [c_vp, c_vp, c_int, c_int, c_vp]
+    lib.nns_keys_topk_unpack.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp]
+    lib.nns_search_f32_topk.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_u, c_int]
+    lib.nns_search_bf16_topk.argtypes = lib.nns_search_f32_topk.argtypes
+    lib.nns_plan_topk.argtypes = [c_int, c_int, c_int, c_int, c_int, c_vp, c_int]
     lib.nns_device_count.argtypes = []
     lib.nns_strerror.argtypes = [c_int]
     lib.nns_strerror.restype = ctypes.c_char_p
@@ -171,6 +180,14 @@ def plan_exact(k: int, m: int, n: int, refs_aligned: bool = True, have_workspace
     d = dict(zip(names, (int(v) for v in out)))
     d["kernel"] = ("k1a", "k1f", "k1b", "k1c")[d["kernel"]]
     return d
+
+
+def plan_topk(k: int, m: int, n: int, kn: int, bf16: bool = False) -> dict:
+    """nns_plan_topk: the top-K (K6) launch geometry for a shape (host only)."""
+    out = np.zeros(6, np.int32)
+    _check(lib.nns_plan_topk(k, m, n, kn, int(bf16), out.ctypes.data, 6), "nns_plan_topk")
+    names = ("queries_per_wg", "splits", "per", "workgroups", "lds_bytes", "ws_keys")
+    return dict(zip(names, (int(v) for v in out)))
 
 
 def selftest_lane_share(values, tile16: bool) -> np.ndarray:
@@ -301,6 +318,39 @@ def search_bf16(query_bits, reference_bits, *, return_distances: bool = False, s
     return (idx, dist) if return_distances else idx
 
 
+def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa):
+    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
+        raise ValueError("query and reference dimensionality differ")
+    m, k = q.shape
+    n = r.shape[1] if refs_soa else r.shape[0]
+    idx = np.empty((m, max(kn, 0)), dtype=np.int32)
+    dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
+    fn = lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
+    _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
+              shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0), device), "nns_search_topk")
+    return (idx, dist) if return_distances else idx
+
+
+def search_topk(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
+                path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """The kn nearest references of every query (nns_search_f32_topk): int32 [m][kn] indices in ascending
+    (V0 distance, index) order, -1 where fewer than kn references are selectable; optionally the fp32 distances
+    (+INF in those slots).  ``shards`` > 1 rehearses the contiguous ref split merged with keys_topk_merge."""
+    q = _as_f32(query_points, "query_points")
+    r = _as_f32(reference_points, "reference_points")
+    return _search_topk(q, r, kn, False, return_distances, shards, path, device, refs_soa)
+
+
+def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: bool = False, shards: int = 1,
+                     path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """search_topk() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_topk)."""
+    q = np.ascontiguousarray(query_bits, dtype=np.uint16)
+    r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
+    if q.ndim != 2 or r.ndim != 2:
+        raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
+    return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa)
+
+
 # ---------------------------------------------------------------------------
 # device-resident API (torch tensors are only the owners of device memory)
 # ---------------------------------------------------------------------------
@@ -377,6 +427,24 @@ class Index:
                "nns_index_search_indices")
         return idx
 
+    def search_topk_keys(self, queries, kn: int, keys=None, stream=None):
+        """[m][kn] packed (V0 distance, global index) int64 keys, ascending; NNS_KEY_NONE pads short rows."""
+        import torch
+        if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
+                or queries.shape[1] != self.k:
+            raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
+        m = queries.shape[0]
+        if keys is None:
+            keys = torch.empty((m, max(kn, 0)), dtype=torch.int64, device=queries.device)
+        _check(lib.nns_index_search_topk(self._h, m, queries.data_ptr(), kn, keys.data_ptr(), _stream_ptr(stream)),
+               "nns_index_search_topk")
+        return keys
+
+    def search_topk(self, queries, kn: int, return_distances: bool = False, stream=None):
+        """The kn nearest refs of every query: int32 [m][kn] (-1 in unfilled slots), optionally fp32 distances."""
+        keys = self.search_topk_keys(queries, kn, stream=stream)
+        return keys_topk_unpack(keys, return_distances=return_distances, stream=stream)
+
     def stats(self) -> dict:
         st = nns_stats()
         _check(lib.nns_index_stats(self._h, ctypes.byref(st)), "nns_index_stats")
@@ -424,6 +492,28 @@ def keys_unpack(keys, return_distances: bool = False, stream=None):
     _check(lib.nns_keys_unpack(keys.data_ptr(), m, idx.data_ptr(),
                                dist.data_ptr() if dist is not None else None, _stream_ptr(stream)),
            "nns_keys_unpack")
+    return (idx, dist) if return_distances else idx
+
+
+def keys_topk_merge(inout, other, stream=None) -> None:
+    """inout[i] = the kn smallest keys of the ascending rows inout[i] and other[i] ([m][kn] int64 tensors)."""
+    if inout.shape != other.shape or inout.dim() != 2:
+        raise ValueError("keys_topk_merge: two [m][kn] key tensors of one shape")
+    m, kn = inout.shape
+    _check(lib.nns_keys_topk_merge(inout.data_ptr(), other.data_ptr(), m, kn, _stream_ptr(stream)), "nns_keys_topk_merge")
+
+
+def keys_topk_unpack(keys, return_distances: bool = False, stream=None):
+    """[m][kn] keys -> int32 indices (-1 for NNS_KEY_NONE) and, optionally, fp32 distances (+INF there)."""
+    import torch
+    if keys.dim() != 2:
+        raise ValueError("keys_topk_unpack: an [m][kn] key tensor")
+    m, kn = keys.shape
+    idx = torch.empty((m, kn), dtype=torch.int32, device=keys.device)
+    dist = torch.empty((m, kn), dtype=torch.float32, device=keys.device) if return_distances else None
+    _check(lib.nns_keys_topk_unpack(keys.data_ptr(), m, kn, idx.data_ptr(),
+                                    dist.data_ptr() if dist is not None else None, _stream_ptr(stream)),
+           "nns_keys_topk_unpack")
     return (idx, dist) if return_distances else idx
 
 
