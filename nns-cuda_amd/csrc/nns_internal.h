@@ -70,11 +70,26 @@ void stager_release();         // free the small whole calls' pinned scratch (nn
 bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes);
 int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
                             int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp);
+// the argument checks of every whole-call entry point (nns_search_*_ex / _topk / _multi), before any device work:
+// k, m, n > 0, non-null pointers, NNS_MAX_POINTS and the k * m / k * n bounds; `where` names the entry point
+int check_whole_call(const char *where, int k, int m, int n, const void *s_points, const void *r_points,
+                     const int *idx_out);
 
 // (the sum in 64 bits: a + b - 1 passes 2^31 for a point count near NNS_MAX_POINTS and a large divisor — that is how
 //  a K1a plan for n = 2^31 - 2^20 once came out with a negative split count)
 static inline int divup(int a, int b) { return (int)(((int64_t)a + b - 1) / b); }
 static inline int64_t divup64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// shard s of n refs over `shards`: contiguous ceil(n / shards) ranges, the last takes the remainder (the reference's
+// split rule, core.cu:781-791; host.py shard_range mirrors it).  cnt == 0: no refs are left for shard s
+struct ShardRange {
+    int beg, cnt;
+};
+static inline ShardRange shard_range(int n, int shards, int s)
+{
+    const int per = divup(n, shards);
+    const int64_t beg = (int64_t)s * per;
+    return {(int)beg, beg + per <= n ? per : (beg < n ? (int)(n - beg) : 0)};
+}
 
 // ---- packed keys --------------------------------------------------------------
 // (fp32 bits << 32) | index; distances are >= +0 so integer order == (distance,

@@ -172,19 +172,8 @@ static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const v
 static int search_multi_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int *idx_out,
                              float *dist_out, int num_devices, unsigned flags)
 {
-    if (k <= 0 || m <= 0 || n <= 0 || !s_points || !r_points || !idx_out) {
-        set_error("nns_search_multi: k, m, n must be > 0 and pointers non-null");
-        return NNS_ERR_INVALID;
-    }
-    // the same limits as the single-device entry points (nns.h), before any thread or allocation
-    if (m > NNS_MAX_POINTS || n > NNS_MAX_POINTS) {
-        set_error("nns_search_multi: m = %d / n = %d exceeds NNS_MAX_POINTS (%d)", m, n, NNS_MAX_POINTS);
-        return NNS_ERR_INVALID;
-    }
-    if ((int64_t)k * m > 0x7FFFFFFFll * 4 || (int64_t)k * n > 0x7FFFFFFFll * 4) {
-        set_error("nns_search_multi: point set too large for one call");
-        return NNS_ERR_INVALID;
-    }
+    // the same checks as the single-device entry points (nns.h), before any thread or allocation
+    NNS_TRY(check_whole_call("nns_search_multi", k, m, n, s_points, r_points, idx_out));
     DeviceScope keep_device;   // the caller's current device is restored on every return path
     int visible = 0;
     if (hipGetDeviceCount(&visible) != hipSuccess || visible < 1) {
@@ -207,16 +196,14 @@ static int search_multi_impl(int k, int m, int n, const void *s_points, const vo
         return bf16 ? nns_search_bf16_ex(k, m, n, (const uint16_t *)s_points, (const uint16_t *)r_points, idx_out, dist_out, 1, flags, 0)
                     : nns_search_f32_ex(k, m, n, (const float *)s_points, (const float *)r_points, idx_out, dist_out, 1, flags, 0);
 
-    const int per = divup(n, G);                        // contiguous shards (core.cu:781-791)
     std::vector<ShardJob> jobs;
     for (int g = 0; g < G; ++g) {
-        const int beg = g * per;
-        const int cnt = ((int64_t)beg + per <= n) ? per : n - beg;
-        if (cnt <= 0) break;
+        const ShardRange sh = shard_range(n, G, g);   // contiguous shards (core.cu:781-791)
+        if (sh.cnt <= 0) break;
         ShardJob j;
         j.device = g % visible;
-        j.beg = beg;
-        j.cnt = cnt;
+        j.beg = sh.beg;
+        j.cnt = sh.cnt;
         jobs.push_back(j);
     }
     G = (int)jobs.size();

@@ -1566,6 +1566,43 @@ def test_small_whole_call_scratch_path_and_its_size_boundary(pkg, orc):
     assert np.array_equal(out[0], want) and np.array_equal(out[1], want)
 
 
+def test_whole_call_errors_after_the_upload_leave_the_library_usable(pkg, orc):
+    """Errors that a whole call meets after its asynchronous uploads (16 MiB of refs: neither the pinned-scratch path
+    nor the chunked upload): NNS_PATH_MFMA beyond the deepest tile, NNS_FILTER_BF16 on bf16 points.  Each returns its
+    status and message; the caller then overwrites its arrays at once, and valid calls of the same shape and of a
+    small-scratch-path shape still match V0 bit for bit.  This pins the statuses and shows the library stays usable;
+    whether the error path waited for the copies that read the caller's memory is not observable from here (the
+    race is too narrow) — that wait is established by reading HostCall's destructor in nns_api.hip."""
+    L = pkg.lib
+    NNS_PATH_MFMA, NNS_FILTER_BF16 = 2, 128
+    rng = np.random.default_rng(2468)
+    m, n, k = 64, 2048, 2048
+    q = rng.random((m, k), dtype=np.float32)
+    r = rng.random((n, k), dtype=np.float32)
+    idx = np.empty(m, np.int32)
+    dist = np.empty(m, np.float32)
+    assert L.nns_search_f32_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data, dist.ctypes.data, 1,
+                               NNS_PATH_MFMA, 0) == 5
+    assert b"NNS_PATH_MFMA" in L.nns_last_error()
+    q[:] = rng.random((m, k), dtype=np.float32)
+    r[:] = rng.random((n, k), dtype=np.float32)
+    idx[:] = -7
+    dist[:] = -7.0
+    _check(pkg, orc, q, r)
+    _check(pkg, orc, rng.random((64, 16), dtype=np.float32), rng.random((1000, 16), dtype=np.float32))
+
+    qb, rb = pkg.to_bf16_bits(q), pkg.to_bf16_bits(r)
+    assert L.nns_search_bf16_ex(k, m, n, qb.ctypes.data, rb.ctypes.data, idx.ctypes.data, dist.ctypes.data, 1,
+                                NNS_FILTER_BF16, 0) == 1
+    assert b"NNS_FILTER_BF16" in L.nns_last_error()
+    qb[:] = 0xFFFF
+    rb[:] = 0xFFFF
+    idx[:] = -7
+    dist[:] = -7.0
+    _check_bf16(pkg, orc, rng.random((m, k), dtype=np.float32), rng.random((n, k), dtype=np.float32))
+    _check_bf16(pkg, orc, rng.random((64, 64), dtype=np.float32), rng.random((1000, 64), dtype=np.float32))
+
+
 def test_deep_tile_specials_and_whole_call_bf16_pipeline(pkg, orc):
     """The 1024-deep tile with NaN / INF refs and magnitudes that void the error bound (exact kernels must take
     over), and a bf16 whole call large enough for the pipelined upload."""
