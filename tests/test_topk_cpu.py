@@ -1,7 +1,8 @@
 """CPU tests of the top-K (k nearest neighbours) boundary: the numpy oracle the GPU tests use agrees with the V0
-oracle, the new C-ABI symbols are exported, arguments are validated before any device is touched, and the launch
-planner (nns_plan_topk) keeps its invariants."""
+oracle, the new C-ABI symbols are exported, arguments are validated before any device is touched, the launch
+planner (nns_plan_topk) keeps its invariants, and the GPU tests' scan table (SCAN_CASES) reaches every scan kernel."""
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import pytest
@@ -10,6 +11,44 @@ import torch
 NNS_MAX_POINTS = 0x7FF00000
 WS_BUDGET_BYTES = 256 << 20       # the split workspace's stated cap (include/nns.h)
 LDS_BYTES = 160 * 1024
+
+# One case per instantiation of topk_scan_kernel<QT, VEC, T>: 5 tile widths x VEC in {4, 1} x {fp32, bf16}.
+# `offset` is the ref view's storage offset in elements (1: the pointer is not 4-element aligned, so the scan
+# takes VEC = 1 although k % 4 == 0); qt / vec are what the planner and the launcher must pick for the shape.
+# test_topk_edges_gpu.py runs every case against the oracle; test_scan_cases_reach_every_instantiation below
+# guards, without a device, that the table still reaches all 20.
+ScanCase = namedtuple("ScanCase", "dtype k m n kn offset qt vec")
+SCAN_CASES = [
+    ScanCase("f32", 16, 40, 3000, 16, 0, 16, 4),
+    ScanCase("f32", 16, 40, 3000, 16, 1, 16, 1),       # misaligned view of k % 4 == 0 refs
+    ScanCase("f32", 32, 21, 3000, 17, 0, 8, 4),        # kn = 17: the QT = 16 / 8 switch
+    ScanCase("f32", 33, 13, 3000, 64, 0, 8, 1),
+    ScanCase("f32", 4096, 6, 1500, 32, 0, 4, 4),       # the 64 KiB query tile holds 4 queries
+    ScanCase("f32", 2049, 7, 1500, 8, 0, 4, 1),
+    ScanCase("f32", 8, 2, 3000, 256, 0, 2, 4),         # two queries: the tile shrinks to m
+    ScanCase("f32", 8192, 3, 800, 5, 1, 2, 1),
+    ScanCase("f32", 16384, 2, 1000, 3, 0, 1, 4),       # the documented k limit
+    ScanCase("f32", 5, 1, 5000, 100, 0, 1, 1),
+    ScanCase("bf16", 32, 40, 3000, 16, 0, 16, 4),
+    ScanCase("bf16", 33, 40, 3000, 1, 0, 16, 1),
+    ScanCase("bf16", 40, 33, 3000, 25, 0, 8, 4),
+    ScanCase("bf16", 64, 24, 3000, 255, 1, 8, 1),
+    ScanCase("bf16", 4096, 5, 1500, 64, 0, 4, 4),
+    ScanCase("bf16", 33, 3, 3000, 20, 0, 4, 1),
+    ScanCase("bf16", 8192, 3, 800, 9, 0, 2, 4),
+    ScanCase("bf16", 3, 2, 5000, 3, 0, 2, 1),
+    ScanCase("bf16", 16384, 2, 1000, 2, 0, 1, 4),
+    ScanCase("bf16", 257, 1, 3000, 7, 0, 1, 1),
+]
+
+
+def scan_case_id(c):
+    return f"{c.dtype}-k{c.k}-m{c.m}-n{c.n}-kn{c.kn}-off{c.offset}"
+
+
+def scan_vec(k, ptr, elem_bytes):
+    """The scan's ref load width for refs at address ptr (launch_topk_scan_t's rule)."""
+    return 4 if k % 4 == 0 and ptr % (4 * elem_bytes) == 0 else 1
 
 
 def topk_oracle(q, r, kn, chunk=64):
@@ -179,3 +218,17 @@ def test_plan_topk_rejects_beyond_exact_path(pkg):
     with pytest.raises(pkg.NNSError) as e:
         pkg.plan_topk(16385, 4, 4, 4)
     assert e.value.status == 5
+
+
+def test_scan_cases_reach_every_instantiation(pkg):
+    # every case gets the tile width and load width it claims, and each covers a (T, VEC, QT) no other case does
+    reached = []
+    for c in SCAN_CASES:
+        esz = 2 if c.dtype == "bf16" else 4
+        p = pkg.plan_topk(c.k, c.m, c.n, c.kn, bf16=c.dtype == "bf16")
+        assert p["queries_per_wg"] == c.qt, (c, p)
+        assert scan_vec(c.k, 256 + c.offset * esz, esz) == c.vec, c   # (device allocations are 256-byte aligned)
+        reached.append((c.dtype, c.vec, c.qt))
+    want = {(t, v, q) for t in ("f32", "bf16") for v in (4, 1) for q in (16, 8, 4, 2, 1)}
+    assert set(reached) == want
+    assert len(reached) == len(want) == 20
