@@ -281,6 +281,48 @@ int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const ui
  * split-workspace keys (0 with one split)}. */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
 
+/* ---- fixed-radius neighbours (range search) -----------------------------------
+ * Semantics: a hit of query i is every reference j (global index, index_base added) whose V0 distance d (the value
+ * nns_index_search computes: sum_{t ascending} fl(fl(q - r)^2), un-contracted fp32 from 0) satisfies d <= radius2,
+ * compared in fp32, inclusive.  radius2 is the SQUARED radius, fp32 for both point types.  A NaN or +INF distance is
+ * never a hit, even with radius2 = +INF.  radius2 NaN or < 0: NNS_ERR_INVALID; -0.0 counts as 0 (then only exact
+ * duplicates of the query are hits).
+ * Output, CSR in the lims form of FAISS's range search: int64 lims[m + 1] with lims[0] = 0 and lims[i + 1] - lims[i]
+ * = the hit count of query i (at most n); query i's hits are idx[lims[i] .. lims[i + 1]) in ascending global index,
+ * and the optional dist[...] holds their V0 distances, bit-equal to V0's.  Every position comes from counts, never
+ * from the arrival order of atomics: two runs give identical buffers.  The total lims[m] may exceed 2^31.
+ * Supported: what top-K supports — every k the exact path accepts (k <= 16384; larger: NNS_ERR_UNSUPPORTED), fp32 and
+ * bf16 points, an index created for any path or with NNS_REFS_SOA (the range passes read its point-major refs).  The
+ * exact scan (K7) runs two passes, count and fill.  Their workspace (per-(query, ref chunk) offsets and the scan of the
+ * counts over m, at most 256 MiB) belongs to the index, grows on demand and is freed behind an event like the top-K
+ * workspace.  Same one-index-per-stream rule as nns_index_search; nns_index_stats then reports NNS_PATH_EXACT (with
+ * NNS_PROFILE, exact_ms / total_ms cover the pass). */
+
+/* Count pass.  lims_dev[m + 1] (device, int64) receives the lims above.  The per-chunk counts the fill needs stay in
+ * the index's range workspace.  q_dev has the index's dtype. */
+int nns_index_range_count(nns_index *ix, int m, const void *q_dev, float radius2, int64_t *lims_dev, void *stream);
+/* Fill pass.  Must follow nns_index_range_count on the same index with the same m, q_dev and radius2, and no other
+ * range count in between; otherwise NNS_ERR_INVALID.  1-NN and top-K searches in between are allowed.  lims_dev: the
+ * count's output (unchanged); idx_dev[lims[m]] (int32, device); dist_dev[lims[m]] optional.  A null idx_dev or
+ * dist_dev is not written, so a fill after a count with lims[m] == 0 succeeds with the null pointer a zero-size
+ * allocation returns (both null: nothing runs). */
+int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2, const int64_t *lims_dev,
+                         int *idx_dev, float *dist_dev, void *stream);
+/* Whole calls: count, read lims[m], allocate, fill.  lims_out: the caller's host int64[m + 1].  *idx_out (and
+ * *dist_out when dist_out != NULL) are malloc()'d by the library with lims[m] entries, never NULL on success; the
+ * caller free()s them.  On error both are set to NULL and nothing leaks; output beyond device or host memory gives
+ * NNS_ERR_NOMEM.  flags: NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE; any other: NNS_ERR_UNSUPPORTED.
+ * Library stream, no device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is
+ * allocated. */
+int nns_search_f32_range(int k, int m, int n, const float *s_points, const float *r_points, float radius2,
+                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
+                          int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+/* Diagnostic (host only, no device needed): the range search's launch geometry for a k-D search of m queries over n
+ * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
+ * workgroup, workspace bytes}. */
+int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
+
 /* Deterministic synthetic clouds: dev[i] = u24(splitmix64(seed, offset+i)) * 2^-24
  * in [0,1) — bit-identical to oracle/v0_oracle.c:nns_rng_fill on the CPU. */
 int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,

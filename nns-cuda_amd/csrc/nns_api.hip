@@ -105,6 +105,15 @@ struct nns_index {
     nns_key *topk_ws = nullptr;
     size_t topk_ws_keys = 0;
 
+    // range search (K7): per-(query, chunk) offsets + scan tile sums, and what the last range count was run for (the
+    // fill must match it)
+    void *range_ws = nullptr;
+    size_t range_ws_bytes = 0;
+    bool range_counted = false;
+    int range_m = 0;
+    const void *range_q = nullptr;
+    float range_r2 = 0.0f;
+
     // NNS_PROFILE: a ring of event sets, one per search (refresh + search = one step), so that a
     // caller can time many steps back to back and read the averages once, without a device
     // synchronisation inside every step
@@ -224,7 +233,8 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     // reusable when that work has completed.  No host wait — an application's kernels on other streams (or this
     // index's own, still running) are not waited for.  (Round 2: hipDeviceSynchronize() here.)
     void *const blocks[] = {ix->r_own, ix->rimg, ix->rnorm, ix->mean, ix->mean_ws, ix->scal, ix->qimg, ix->qnorm,
-                            ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws, ix->topk_ws};
+                            ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws, ix->topk_ws,
+                            ix->range_ws};
     if (stream_idle)
         for (void *b : blocks) pool_free(b);
     else
@@ -677,6 +687,119 @@ int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int ou
     const int64_t wgs = (int64_t)p.qgroups * p.splits;
     const int64_t ws = (int64_t)p.ws_keys;
     const int v[6] = {p.qt, p.splits, p.per, wgs > 0x7FFFFFFF ? 0x7FFFFFFF : (int)wgs, p.lds, (int)ws};
+    memcpy(out, v, sizeof(v));
+    return NNS_OK;
+}
+
+// ---- range search (K7) ---------------------------------------------------------------------------------------
+// argument checks shared by the split and whole-call entry points (no device touched)
+static int range_check_radius(const char *where, float radius2)
+{
+    if (!(radius2 >= 0.0f)) {   // (NaN fails the compare; -0.0 passes and counts as 0)
+        set_error("%s: radius2 must be a squared radius >= 0 (got %g)", where, (double)radius2);
+        return NNS_ERR_INVALID;
+    }
+    return NNS_OK;
+}
+
+static int range_check_split(const char *where, nns_index *ix, int m, const void *q_dev, float radius2, const void *out1,
+                             const void *out2)
+{
+    if (!ix || !q_dev || !out1 || !out2 || m <= 0) {
+        set_error("%s: m must be > 0 and pointers non-null (m=%d)", where, m);
+        return NNS_ERR_INVALID;
+    }
+    NNS_TRY(range_check_radius(where, radius2));
+    if (m > kMaxPoints) {
+        set_error("%s: m = %d exceeds NNS_MAX_POINTS (%d)", where, m, kMaxPoints);
+        return NNS_ERR_INVALID;
+    }
+    return NNS_OK;
+}
+
+static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float radius2, int64_t *lims_dev,
+                                  hipStream_t st)
+{
+    if (ix) ix->range_counted = false;   // (every count call, also one that fails, ends what a fill could use)
+    NNS_TRY(range_check_split("nns_index_range_count", ix, m, q_dev, radius2, lims_dev, lims_dev));
+    RangePlan p{};
+    NNS_TRY(range_plan(ix->k, m, ix->n, &p));
+    NNS_TRY(ensure_device_ok(ix->device));
+    ix->last_stream = st;
+    if (p.ws_bytes > ix->range_ws_bytes) {
+        // (the old block may still be read by an earlier pass of this index: back to the pool behind an event)
+        pool_free_after(ix->range_ws, st);
+        ix->range_ws = nullptr;
+        ix->range_ws_bytes = 0;
+        if (pool_alloc(&ix->range_ws, p.ws_bytes) != hipSuccess) {
+            set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
+            return NNS_ERR_NOMEM;
+        }
+        ix->range_ws_bytes = p.ws_bytes;
+    }
+    const bool prof = ix->profile;
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
+    NNS_TRY(launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st));
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
+    ix->range_counted = true;
+    ix->range_m = m;
+    ix->range_q = q_dev;
+    ix->range_r2 = radius2;
+    ix->last_m = m;
+    ix->last_path = NNS_PATH_EXACT;
+    ix->searched = true;
+    profile_advance(ix, NNS_PATH_EXACT);
+    return NNS_OK;
+}
+
+static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float radius2, const int64_t *lims_dev,
+                                 int *idx_dev, float *dist_dev, hipStream_t st)
+{
+    // (idx_dev / dist_dev may be null: a zero-size allocation when lims[m] == 0; a null buffer is not written)
+    NNS_TRY(range_check_split("nns_index_range_fill", ix, m, q_dev, radius2, lims_dev, lims_dev));
+    if (!ix->range_counted || ix->range_m != m || ix->range_q != q_dev || ix->range_r2 != radius2) {
+        set_error("nns_index_range_fill: m, q_dev and radius2 must be those of the last nns_index_range_count on this index");
+        return NNS_ERR_INVALID;
+    }
+    RangePlan p{};
+    NNS_TRY(range_plan(ix->k, m, ix->n, &p));
+    NNS_TRY(ensure_device_ok(ix->device));
+    ix->last_stream = st;
+    const bool prof = ix->profile;
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
+    if (idx_dev || dist_dev)
+        NNS_TRY(launch_range_fill(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, ix->base, lims_dev,
+                                  ix->range_ws, idx_dev, dist_dev, st));
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
+    ix->last_m = m;
+    ix->last_path = NNS_PATH_EXACT;
+    ix->searched = true;
+    profile_advance(ix, NNS_PATH_EXACT);
+    return NNS_OK;
+}
+
+int nns_index_range_count(nns_index *ix, int m, const void *q_dev, float radius2, int64_t *lims_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_range_count_impl(ix, m, q_dev, radius2, lims_dev, (hipStream_t)stream);
+}
+
+int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2, const int64_t *lims_dev, int *idx_dev,
+                         float *dist_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_range_fill_impl(ix, m, q_dev, radius2, lims_dev, idx_dev, dist_dev, (hipStream_t)stream);
+}
+
+int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
+{
+    (void)bf16_points;   // (same geometry: bf16 refs are widened as they are read)
+    if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
+    RangePlan p{};
+    NNS_TRY(range_plan(k, m, n, &p));
+    const int64_t wgs = (int64_t)p.qgroups * p.chunks;
+    const int v[6] = {p.qt, p.chunks, p.per, wgs > 0x7FFFFFFF ? 0x7FFFFFFF : (int)wgs, p.lds, (int)p.ws_bytes};
     memcpy(out, v, sizeof(v));
     return NNS_OK;
 }
@@ -1268,6 +1391,122 @@ static int search_topk_host_impl(int k, int m, int n, const void *s_points, cons
     if (num_shards < 1) num_shards = 1;
     if (num_shards > n) num_shards = n;   // the reference clamps GPUs to n (core.cu:771-772)
     return search_whole(where, k, m, n, s_points, r_points, bf16, kn, idx_out, dist_out, num_shards, flags, device);
+}
+
+// The range whole call: uploads, SoA transpose, one exact-path index, the count pass, the total read back (the one
+// host wait in the middle), the host arrays malloc()'d, the fill pass, downloads — on ONE library stream.
+// *hidx / *hdist (hdist null: no distances) receive the malloc()'d arrays; the caller frees them on an error.
+static int search_whole_range(const char *where, int k, int m, int n, const void *s_points, const void *r_points,
+                              int bf16, float radius2, int64_t *lims_out, int **hidx, float **hdist, unsigned flags,
+                              int device)
+{
+    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz, lb = ((size_t)m + 1) * sizeof(int64_t);
+    HostCall call(lib_stream_acquire());
+    const hipStream_t st = call.st;
+    char *q_d = nullptr, *r_d = nullptr, *r_t = nullptr;
+    int64_t *lims_d = nullptr;
+    int *idx_d = nullptr;
+    float *dist_d = nullptr;
+    if (!call.alloc(&q_d, qb) || !call.alloc(&r_d, rb) || !call.alloc(&lims_d, lb)) {
+        set_error("%s: device allocation failed", where);
+        return NNS_ERR_NOMEM;
+    }
+    if (call.copy(q_d, s_points, qb, hipMemcpyHostToDevice) != hipSuccess ||
+        call.copy(r_d, r_points, rb, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: H2D copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+        return NNS_ERR_HIP;
+    }
+    if (flags & NNS_REFS_SOA) {
+        // dimension-major refs: transpose once on the device into a point-major copy
+        if (!call.alloc(&r_t, rb)) {
+            set_error("%s: device allocation failed (point-major copy)", where);
+            return NNS_ERR_NOMEM;
+        }
+        NNS_TRY(launch_soa_to_aos(k, n, r_d, r_t, (int)esz, st));
+        r_d = r_t;
+    }
+    // (the exact path's index: no MFMA ref pre-pass, it reads the point-major refs only)
+    NNS_TRY(index_create_impl(&call.ix, device, k, n, r_d, bf16, 0, NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync,
+                              st));
+    NNS_TRY(index_range_count_impl(call.ix, m, q_d, radius2, lims_d, st));
+    if (call.copy(lims_out, lims_d, lb, hipMemcpyDeviceToHost) != hipSuccess || call.finish() != hipSuccess) {
+        set_error("%s: kernel execution or D2H copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+        return NNS_ERR_HIP;
+    }
+    const size_t total = (size_t)lims_out[m];
+    const bool with_dist = hdist != nullptr;
+    *hidx = (int *)malloc((total ? total : 1) * sizeof(int));   // (never NULL on success, also without hits)
+    if (with_dist) *hdist = (float *)malloc((total ? total : 1) * sizeof(float));
+    if (!*hidx || (with_dist && !*hdist)) {
+        set_error("%s: host allocation of %zu hits failed", where, total);
+        return NNS_ERR_NOMEM;
+    }
+    if (total == 0) return NNS_OK;
+    if (!call.alloc(&idx_d, total * sizeof(int)) || (with_dist && !call.alloc(&dist_d, total * sizeof(float)))) {
+        (void)hipGetLastError();
+        set_error("%s: device allocation of %zu hits failed", where, total);
+        return NNS_ERR_NOMEM;
+    }
+    call.idle = false;   // (work is enqueued again after the wait above)
+    NNS_TRY(index_range_fill_impl(call.ix, m, q_d, radius2, lims_d, idx_d, dist_d, st));
+    if (call.copy(*hidx, idx_d, total * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+        (with_dist && call.copy(*hdist, dist_d, total * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
+        call.finish() != hipSuccess) {
+        set_error("%s: kernel execution or D2H copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+        return NNS_ERR_HIP;
+    }
+    return NNS_OK;
+}
+
+static int search_range_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16,
+                                  float radius2, int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags,
+                                  int device)
+{
+    const char *where = bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
+    if (idx_out) *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
+    if (!idx_out) {
+        set_error("%s: idx_out is null", where);
+        return NNS_ERR_INVALID;
+    }
+    // (lims_out stands for the output buffer of the shared check)
+    NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
+    NNS_TRY(range_check_radius(where, radius2));
+    const unsigned path = flags & NNS_PATH_MASK;
+    if ((path != NNS_PATH_AUTO && path != NNS_PATH_EXACT) || (flags & ~(unsigned)(NNS_PATH_MASK | NNS_REFS_SOA | NNS_PROFILE))) {
+        set_error("%s: flags 0x%x: range search accepts the auto / exact path, dimension-major refs and profiling only",
+                  where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    RangePlan p{};
+    NNS_TRY(range_plan(k, m, n, &p));   // (k beyond the exact path: before any device work)
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(device));
+    int *hidx = nullptr;
+    float *hdist = nullptr;
+    const int rc = search_whole_range(where, k, m, n, s_points, r_points, bf16, radius2, lims_out, &hidx,
+                                      dist_out ? &hdist : nullptr, flags, device);
+    if (rc != NNS_OK) {
+        free(hidx);
+        free(hdist);
+        return rc;
+    }
+    *idx_out = hidx;
+    if (dist_out) *dist_out = hdist;
+    return NNS_OK;
+}
+
+int nns_search_f32_range(int k, int m, int n, const float *s_points, const float *r_points, float radius2,
+                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    return search_range_host_impl(k, m, n, s_points, r_points, 0, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
+                          int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    return search_range_host_impl(k, m, n, s_points, r_points, 1, radius2, lims_out, idx_out, dist_out, flags, device);
 }
 
 int nns_search_f32_ex(int k, int m, int n, const float *s_points, const float *r_points, int *idx_out,

@@ -113,6 +113,22 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
     return __fadd_rn(sum, __fmul_rn(diff, diff));
 }
 
+// point loads of the lane-per-ref scans (K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16) aligned
+// row; bf16 bits are widened exactly
+__device__ __forceinline__ float tk_ld1(const float *p) { return *p; }
+__device__ __forceinline__ float tk_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
+__device__ __forceinline__ float4 tk_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 tk_ld4(const uint16_t *p)
+{
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 bf16, widened exactly
+    float4 o;
+    o.x = __uint_as_float(v.x << 16);
+    o.y = __uint_as_float(v.x & 0xFFFF0000u);
+    o.z = __uint_as_float(v.y << 16);
+    o.w = __uint_as_float(v.y & 0xFFFF0000u);
+    return o;
+}
+
 // LDS-DMA (global_load_lds_*): 64 lanes x {16, 4} bytes from per-lane global addresses to
 // LDS at M0 + lane * size, no VGPR destination.  Inline asm on purpose: through the
 // builtin, hipcc (ROCm 7.2) treats every later ds_read as possibly aliasing the
@@ -346,5 +362,23 @@ int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const voi
                        int64_t base, nns_key *keys, nns_key *ws, hipStream_t st);
 int launch_topk_merge(nns_key *inout, const nns_key *other, int m, int kn, hipStream_t st);
 int launch_topk_unpack(const nns_key *keys, int m, int kn, int *idx, float *dist, hipStream_t st);
+
+// range_kernels.hip (K7: every ref within a squared radius, CSR output)
+struct RangePlan {
+    int qt;           // queries per workgroup
+    int qgroups;      // grid.x
+    int chunks;       // grid.y: contiguous ref ranges, every one non-empty
+    int per;          // refs per chunk (the last may hold fewer)
+    int lds;          // LDS bytes per workgroup
+    int tiles;        // tiles of the exclusive scan over the m query counts
+    size_t ws_bytes;  // workspace: per-(query, chunk) counts [m][chunks] (several chunks) + tile sums (several tiles)
+};
+int range_plan(int k, int m, int n, RangePlan *p);
+// count pass: lims[m + 1] (int64) and, with several chunks, the per-(query, chunk) start offsets in ws
+int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+                       int64_t *lims, void *ws, hipStream_t st);
+// fill pass: idx[lims[m]] (global indices), dist (optional) from the lims and ws of the count pass
+int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+                      int64_t base, const int64_t *lims, const void *ws, int *idx, float *dist, hipStream_t st);
 
 }  // namespace nns

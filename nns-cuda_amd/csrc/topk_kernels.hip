@@ -27,20 +27,6 @@ constexpr size_t kTopkWsBudgetKeys = (size_t)32 << 20;   // 256 MiB of split wor
 constexpr int kTopkTargetWgs = 2048;               // about 8 workgroups per CU
 constexpr int kTopkMinPerSplit = 2048;             // refs a split sees at least (so that its list warm-up amortises)
 
-__device__ __forceinline__ float tk_ld1(const float *p) { return *p; }
-__device__ __forceinline__ float tk_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ float4 tk_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 tk_ld4(const uint16_t *p)
-{
-    const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 bf16, widened exactly
-    float4 o;
-    o.x = __uint_as_float(v.x << 16);
-    o.y = __uint_as_float(v.x & 0xFFFF0000u);
-    o.z = __uint_as_float(v.y << 16);
-    o.w = __uint_as_float(v.y & 0xFFFF0000u);
-    return o;
-}
-
 // number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
 __device__ __forceinline__ int tk_rank(const nns_key *a, int len, nns_key v, bool or_equal)
 {

@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "nns_multi_last_exchange_ranks",
     "nns_index_search_topk", "nns_keys_topk_merge", "nns_keys_topk_unpack", "nns_search_f32_topk",
     "nns_search_bf16_topk", "nns_plan_topk",
+    "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
 )
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
@@ -125,6 +126,13 @@ def _load() -> ctypes.CDLL:
     lib.nns_search_f32_topk.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_u, c_int]
     lib.nns_search_bf16_topk.argtypes = lib.nns_search_f32_topk.argtypes
     lib.nns_plan_topk.argtypes = [c_int, c_int, c_int, c_int, c_int, c_vp, c_int]
+    lib.nns_index_range_count.argtypes = [c_vp, c_int, c_vp, ctypes.c_float, c_vp, c_vp]
+    lib.nns_index_range_fill.argtypes = [c_vp, c_int, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp]
+    lib.nns_search_f32_range.argtypes = [c_int, c_int, c_int, c_vp, c_vp, ctypes.c_float, c_vp,
+                                         ctypes.POINTER(ctypes.POINTER(c_int)),
+                                         ctypes.POINTER(ctypes.POINTER(ctypes.c_float)), c_u, c_int]
+    lib.nns_search_bf16_range.argtypes = lib.nns_search_f32_range.argtypes
+    lib.nns_plan_range.argtypes = [c_int, c_int, c_int, c_int, c_vp, c_int]
     lib.nns_device_count.argtypes = []
     lib.nns_strerror.argtypes = [c_int]
     lib.nns_strerror.restype = ctypes.c_char_p
@@ -187,6 +195,14 @@ def plan_topk(k: int, m: int, n: int, kn: int, bf16: bool = False) -> dict:
     out = np.zeros(6, np.int32)
     _check(lib.nns_plan_topk(k, m, n, kn, int(bf16), out.ctypes.data, 6), "nns_plan_topk")
     names = ("queries_per_wg", "splits", "per", "workgroups", "lds_bytes", "ws_keys")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def plan_range(k: int, m: int, n: int, bf16: bool = False) -> dict:
+    """nns_plan_range: the range search (K7) launch geometry for a shape (host only)."""
+    out = np.zeros(6, np.int32)
+    _check(lib.nns_plan_range(k, m, n, int(bf16), out.ctypes.data, 6), "nns_plan_range")
+    names = ("queries_per_wg", "chunks", "per", "workgroups", "lds_bytes", "ws_bytes")
     return dict(zip(names, (int(v) for v in out)))
 
 
@@ -351,6 +367,51 @@ def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: b
     return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa)
 
 
+def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa):
+    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
+        raise ValueError("query and reference dimensionality differ")
+    m, k = q.shape
+    n = r.shape[1] if refs_soa else r.shape[0]
+    lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
+    pidx = ctypes.POINTER(ctypes.c_int)()
+    pdist = ctypes.POINTER(ctypes.c_float)()
+    fn = lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
+    _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
+              ctypes.byref(pdist) if return_distances else None, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0),
+              device), "nns_search_range")
+    total = int(lims[-1])
+    try:
+        idx = np.ctypeslib.as_array(pidx, shape=(total,)).copy() if total else np.empty(0, np.int32)
+        dist = None
+        if return_distances:
+            dist = np.ctypeslib.as_array(pdist, shape=(total,)).copy() if total else np.empty(0, np.float32)
+    finally:
+        _libc.free(pidx)
+        if return_distances:
+            _libc.free(pdist)
+    return (lims, idx, dist) if return_distances else (lims, idx)
+
+
+def search_range(query_points, reference_points, radius2: float, *, return_distances: bool = False,
+                 path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """Every reference within squared radius ``radius2`` of each query (nns_search_f32_range), in CSR form:
+    (lims int64[m + 1], idx int32[lims[m]][, dist fp32[lims[m]]]); query i's hits are idx[lims[i]:lims[i + 1]] in
+    ascending index order, with their V0 distances (d <= radius2, NaN / +INF never)."""
+    q = _as_f32(query_points, "query_points")
+    r = _as_f32(reference_points, "reference_points")
+    return _search_range(q, r, radius2, False, return_distances, path, device, refs_soa)
+
+
+def search_range_bf16(query_bits, reference_bits, radius2: float, *, return_distances: bool = False,
+                      path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """search_range() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_range)."""
+    q = np.ascontiguousarray(query_bits, dtype=np.uint16)
+    r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
+    if q.ndim != 2 or r.ndim != 2:
+        raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
+    return _search_range(q, r, radius2, True, return_distances, path, device, refs_soa)
+
+
 # ---------------------------------------------------------------------------
 # device-resident API (torch tensors are only the owners of device memory)
 # ---------------------------------------------------------------------------
@@ -444,6 +505,55 @@ class Index:
         """The kn nearest refs of every query: int32 [m][kn] (-1 in unfilled slots), optionally fp32 distances."""
         keys = self.search_topk_keys(queries, kn, stream=stream)
         return keys_topk_unpack(keys, return_distances=return_distances, stream=stream)
+
+    def _check_queries(self, queries):
+        if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
+                or queries.shape[1] != self.k:
+            raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
+
+    def range_count(self, queries, radius2: float, lims=None, stream=None):
+        """Count pass of the range search: int64 lims [m + 1] (device); the fill's per-chunk offsets stay in the
+        index."""
+        import torch
+        self._check_queries(queries)
+        m = queries.shape[0]
+        if lims is None:
+            lims = torch.empty(m + 1, dtype=torch.int64, device=queries.device)
+        _check(lib.nns_index_range_count(self._h, m, queries.data_ptr(), float(radius2), lims.data_ptr(),
+                                         _stream_ptr(stream)), "nns_index_range_count")
+        return lims
+
+    def range_fill(self, queries, radius2: float, lims, total: Optional[int] = None, return_distances: bool = False,
+                   idx=None, dist=None, stream=None):
+        """Fill pass after range_count with the same queries and radius2: int32 idx [lims[m]] (and fp32 distances).
+        total: lims[m] if the caller has read it (otherwise it is read here, after waiting for `stream`, where the
+        count ran).  With no hits the buffers are empty and their null pointers are not written."""
+        import torch
+        self._check_queries(queries)
+        m = queries.shape[0]
+        if idx is None or (return_distances and dist is None):
+            if total is None:
+                if stream is not None:
+                    stream.synchronize()   # (a torch stream: the read below runs on the current one)
+                total = int(lims[-1].item())
+            if idx is None:
+                idx = torch.empty(total, dtype=torch.int32, device=queries.device)
+            if return_distances and dist is None:
+                dist = torch.empty(total, dtype=torch.float32, device=queries.device)
+        _check(lib.nns_index_range_fill(self._h, m, queries.data_ptr(), float(radius2), lims.data_ptr(), idx.data_ptr(),
+                                        dist.data_ptr() if dist is not None else None, _stream_ptr(stream)),
+               "nns_index_range_fill")
+        return (idx, dist) if return_distances else idx
+
+    def search_range(self, queries, radius2: float, return_distances: bool = False, stream=None):
+        """Every ref within squared radius radius2 of each query: (lims int64 [m + 1], idx int32 [lims[m]][, dist]),
+        torch tensors on the device.  Counts, reads lims[m] (one wait for the count), allocates and fills."""
+        lims = self.range_count(queries, radius2, stream=stream)
+        if stream is not None:
+            stream.synchronize()   # (a torch stream: the read below runs on the current one)
+        total = int(lims[-1].item())
+        out = self.range_fill(queries, radius2, lims, total=total, return_distances=return_distances, stream=stream)
+        return (lims,) + out if return_distances else (lims, out)
 
     def stats(self) -> dict:
         st = nns_stats()
