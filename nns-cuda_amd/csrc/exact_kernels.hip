@@ -686,14 +686,17 @@ static int launch_k1a(int m, int n, const float *q, const float *r, int64_t base
 // remembered: 4.1 vector instructions per pair instead of 9.1.  At the end of the range the workgroup merges its waves'
 // entries per query (LDS), takes a = the smallest chunk minimum, and — tau(a) bounding |s + |x'|^2 - V0's distance| from
 // both sides exactly as for the MFMA filter (finalize.hip; here an FMA chain of K steps behind an FMA-evaluated norm:
-// tau_consts' fp32 model with kt = 8 covers it) —
+// tau_consts' fp32 model with kt = 8 covers it; plus an absolute floor for roundings below FLT_MIN: k1f_tau,
+// nns_internal.h) —
 //   * evaluates V0's own arithmetic on the 2 x 16 refs of the best two chunks, 16 lanes side by side, reading the
 //     ORIGINAL coordinates: the (distance, index)-lexicographic minimum is V0's answer for this range, ties included,
 //     because every ref whose score is within tau(a) of a lies in one of those chunks —
 //   * unless the THIRD-best chunk minimum is within tau(a) too (three chunks within the filter's resolution: duplicates,
 //     lattices): then the whole workgroup scans the range for that query with V0's arithmetic (lane = ref), and if more
 //     than a few queries need it, or a ref is NaN / INF / huge (a score could overflow), every lane walks the range for
-//     its own queries exactly as K1a does.  Slower on such inputs, never different.
+//     its own queries exactly as K1a does.  Slower on such inputs, never different.  Clouds whose squared distances are
+//     subnormal take these paths too: there tau(a) is its absolute floor, a few subnormal ulps, and most chunk minima
+//     lie within it.
 // The cross-split stage is K1a's (returning atomic mins on exact keys, last workgroup writes), minus the index recovery.
 // Measured (profiles/r03_ab_k1f.txt, r03_k1f_timeline.txt): C2 49.6 -> 40.3 us.  The walk is 5.2 instructions per pair
 // (3 FMAs, 0.5 v_min3, the insert, one broadcast ds_read_b128 + its wait per ref and wave) and runs at the LDS's pace:
@@ -720,14 +723,6 @@ __device__ __forceinline__ nns_key row_min_key(nns_key v)
     v = key_min_dpp<0x124>(v);   // row_ror:4
     v = key_min_dpp<0x122>(v);   // row_ror:2
     return key_min_dpp<0x121>(v);   // row_ror:1
-}
-
-// tau(a) of the VALU filter in fp32, rounded up everywhere: tau_consts(kt = 8, mode 0) with (X + Y)^2 <= 2 (X^2 + Y^2):
-// c0 <= 62.2 u (X^2 + Y^2), c1 <= 20.1 u
-__device__ __forceinline__ float k1f_tau(float a, float x2, float y2)
-{
-    const float d = a + x2;
-    return 3.8185e-6f * (x2 + y2) + 1.9074e-6f * (d > 0.0f ? d : 0.0f);   // 2^-18 x 1.001, 2^-19
 }
 
 template <int K>
@@ -958,7 +953,7 @@ __global__ __launch_bounds__(512) void lowdim_filter_kernel(
                 insert(em2[e], ec2[e]);
                 a3 = fminf(a3, em3[e]);   // (a third minimum has no chunk: it only ever decides "ambiguous")
             }
-            const float thr = a1 + k1f_tau(a1, xn[u] * 1.00001f, y2 * 1.00001f);
+            const float thr = k1f_threshold(a1, xn[u], y2);   // (nns_internal.h: k1f_tau, its relative and absolute terms)
             s_cand[ql][0] = b1;
             s_cand[ql][1] = b2;
             s_fkey[ql] = NNS_KEY_NONE;

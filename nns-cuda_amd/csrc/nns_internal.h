@@ -274,6 +274,36 @@ __host__ __device__ inline float record_threshold(const TauConsts &t, float a)
     return a + (t.c0 + t.c1 * (d > 0.0f ? d : 0.0f)) * 1.002f;
 }
 
+// tau(a) of K1f, the vector-ALU filter of k <= 3 (exact_kernels.hip, lowdim_filter_kernel), in fp32, rounded up everywhere.
+// Its score is an FMA chain of 2K steps (K for the norm of y' = fl(r - c), K for -2 x'.y' on top of it), so the relative
+// part is tau_consts' model at kt = 2K <= 8 with (X + Y)^2 <= 2 (X^2 + Y^2): c0 <= 62.2 u (X^2 + Y^2), c1 <= 20.1 u.
+// x2, y2 >= X^2, Y^2 (the kernel passes its FMA-chain norms times 1.00001f).
+// The absolute part: a rounding whose RESULT lies below FLT_MIN is off by up to half a subnormal ulp, 2^-150, however
+// small the operands — a bound no relative term gives once the squares are subnormal (at the smallest scales the
+// relative part rounds to 0).  Additions and subtractions with a subnormal result are exact, so the centrings
+// x' = fl(q - c), y' = fl(r - c) and V0's adds add nothing; what does is every FMA of the two scores compared
+// (2 x 2K) and every product of V0's two distances (2 x K):  6K x 2^-150 = 3K x 2^-149 <= 9 x 2^-149 at K = 3.  The
+// fp32 evaluation below loses at most 2^-150 more per product with a subnormal result (two of them).  The floor is
+// 2^-144 = 32 x 2^-149, over three times the sum of both.  The kernel's sum fl(a + tau) rounds relative to |a| only
+// (exact while a + tau is subnormal), which the relative part's er term covers as in tau_consts.  At unit scale the floor
+// is 1e-38 of tau.  tests/test_tau_model.py holds the kernel's fp32 threshold against a + tau(a) + the absolute term
+// in extended precision, from subnormal norms up to 1e30.
+constexpr float kK1fTauFloor = 0x1p-144f;
+
+__host__ __device__ inline float k1f_tau(float a, float x2, float y2)
+{
+#pragma clang fp contract(off)
+    const float d = a + x2;
+    return 3.8185e-6f * (x2 + y2) + 1.9074e-6f * (d > 0.0f ? d : 0.0f) + kK1fTauFloor;   // 2^-18 x 1.001, 2^-19
+}
+
+// K1f's threshold of a query whose best chunk minimum is a (xn, y2: its FMA-chain norm, the workgroup's largest ref norm)
+__host__ __device__ inline float k1f_threshold(float a, float xn, float y2)
+{
+#pragma clang fp contract(off)
+    return a + k1f_tau(a, xn * 1.00001f, y2 * 1.00001f);
+}
+
 // device-side scalars shared between kernels of one index
 struct DevScalars {
     unsigned r_maxabs_bits;  // max |r| bits (NaN/INF/huge detection)

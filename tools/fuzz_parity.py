@@ -3,8 +3,8 @@
 
     python tools/fuzz_parity.py --seconds 240 --seed 1
 
-Random shapes (m, n, k), data families (uniform, clustered, duplicates, huge / tiny scale, offset
-clouds, planted NaN / INF), dtypes (fp32, bf16), paths (auto / mfma / exact) and shard counts; every
+Random shapes (m, n, k), data families (uniform, clustered, duplicates, huge / tiny / subnormal scale,
+offset clouds, planted NaN / INF), dtypes (fp32, bf16), paths (auto / mfma / exact) and shard counts; every
 result is compared index-for-index and distance-bit-for-bit with the V0 oracle.  Prints one line
 per failure and a summary; exit status 1 if anything differed.
 """
@@ -36,6 +36,11 @@ def make_cloud(rng, m, n, k, family):
     elif family == "tiny":
         q *= np.float32(1e-12)
         r *= np.float32(1e-12)
+    elif family == "subnormal":
+        # squared coordinates / distances below FLT_MIN (1e-19: both sides of it; 1e-23: every square rounds to 0)
+        s = np.float32(rng.choice([1e-19, 1e-20, 1e-21, 1e-22, 1e-23]))
+        q *= s
+        r *= s
     elif family == "offset":
         q += np.float32(1000.0)
         r += np.float32(1000.0)
@@ -56,7 +61,7 @@ def main():
     a = ap.parse_args()
     pkg, orc = graft.load_package(), graft.load_oracle()
     rng = np.random.default_rng(a.seed)
-    families = ["uniform", "clustered", "duplicates", "huge", "tiny", "offset", "specials"]
+    families = ["uniform", "clustered", "duplicates", "huge", "tiny", "subnormal", "offset", "specials"]
     t0 = time.time()
     cases = fails = 0
     last = t0
