@@ -1113,21 +1113,6 @@ __global__ __launch_bounds__(512) void lowdim_filter_kernel(
 // ---------------------------------------------------------------------------
 // K1b: lane = ref, query tile in LDS (broadcast reads)
 // ---------------------------------------------------------------------------
-// element access: fp32 as is; bf16 (raw uint16 bits) widened exactly to fp32
-__device__ __forceinline__ float ld1(const float *p) { return *p; }
-__device__ __forceinline__ float ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 ld4(const uint16_t *p)
-{
-    const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 bf16
-    float4 o;
-    o.x = __uint_as_float(v.x << 16);
-    o.y = __uint_as_float(v.x & 0xFFFF0000u);
-    o.z = __uint_as_float(v.y << 16);
-    o.w = __uint_as_float(v.y & 0xFFFF0000u);
-    return o;
-}
-
 template <int QT, int VEC, typename T>
 __global__ __launch_bounds__(256) void exact_lane_ref_kernel(
     int k, int n, const T *__restrict__ q, const T *__restrict__ r,
@@ -1147,7 +1132,7 @@ __global__ __launch_bounds__(256) void exact_lane_ref_kernel(
             float v = 0.0f;
             if (qslot < nq) {
                 const int qi = qlist ? qlist[qslot] : qslot;
-                v = ld1(q + (size_t)qi * k + t);
+                v = pt_ld1(q + (size_t)qi * k + t);
             }
             sq[e] = v;
         }
@@ -1162,31 +1147,8 @@ __global__ __launch_bounds__(256) void exact_lane_ref_kernel(
         }
         for (int64_t jl = (int64_t)blockIdx.x * 256 + tid; jl < n; jl += (int64_t)gridDim.x * 256) {   // (64-bit: the stride may carry past 2^31)
             const int j = (int)jl;
-            const T *rj = r + (size_t)j * k;
             float sum[QT];
-#pragma unroll
-            for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
-            if (VEC == 4) {
-                for (int t = 0; t < k; t += 4) {
-                    const float4 rv = ld4(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) {
-                        const float4 qv = *reinterpret_cast<const float4 *>(&sq[u * k + t]);
-                        float s = sum[u];
-                        s = v0_step(s, qv.x, rv.x);
-                        s = v0_step(s, qv.y, rv.y);
-                        s = v0_step(s, qv.z, rv.z);
-                        s = v0_step(s, qv.w, rv.w);
-                        sum[u] = s;
-                    }
-                }
-            } else {
-                for (int t = 0; t < k; ++t) {
-                    const float rv = ld1(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) sum[u] = v0_step(sum[u], sq[u * k + t], rv);
-                }
-            }
+            v0_lane_chains<QT, VEC, 1>(k, sq, r + (size_t)j * k, sum);
 #pragma unroll
             for (int u = 0; u < QT; ++u)
                 if (best[u] > sum[u]) {   // strict: first (lowest j) minimum of this lane
@@ -1265,7 +1227,7 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
             float v = 0.0f;
             if (qslot < nq) {
                 const int qi = qlist ? qlist[qslot] : qslot;
-                v = ld1(q + (size_t)qi * k + t);
+                v = pt_ld1(q + (size_t)qi * k + t);
             }
             sq[e] = v;
         }
@@ -1715,39 +1677,28 @@ static int launch_k1c(int k, int m, int n, const float *q, const float *r, int64
     return launch_k1c_q<4>(k, m, n, q, r, base, keys, mg, st);
 }
 
-template <int QT, typename T>
-static int launch_k1b_t(int k, int n, const T *q, const T *r, const int *qlist,
-                        const int *qcount, int mq, int groups, int64_t base, nns_key *keys,
-                        hipStream_t st)
+template <typename T>
+static int launch_k1b(int k, int n, const T *q, const T *r, const int *qlist,
+                      const int *qcount, int mq, int qt, int groups, int64_t base,
+                      nns_key *keys, hipStream_t st)
 {
     const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
-    const size_t lds = (size_t)QT * k * sizeof(float);
+    const bool tiled = (k % (16 / (int)sizeof(T)) == 0) && (((uintptr_t)r & 15) == 0);
     int xblocks = divup(n, 256);
     // about 8 workgroups per CU in total; refs are strided over gridDim.x
     int target = divup(2048, groups);
     if (target < 1) target = 1;
     if (xblocks > target) xblocks = target;
-    dim3 grid(xblocks, groups);
-    const bool tiled = (k % (16 / (int)sizeof(T)) == 0) && (((uintptr_t)r & 15) == 0);
-    if (tiled) {
-        auto kern = exact_lane_ref_tiled_kernel<QT, T>;
-        const size_t lds_t = lds + 4 * 64 * (8 * 16 + 16);
-        if (lds_t > 48 * 1024)
-            NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds_t, st, k, n, q, r, qlist, qcount, mq, base, keys);
-    } else if (vec) {
-        auto kern = exact_lane_ref_kernel<QT, 4, T>;
-        if (lds > 48 * 1024)
-            NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k, n, q, r, qlist, qcount, mq, base, keys);
-    } else {
-        auto kern = exact_lane_ref_kernel<QT, 1, T>;
-        if (lds > 48 * 1024)
-            NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, k, n, q, r, qlist, qcount, mq, base, keys);
-    }
-    NNS_HIP(hipGetLastError());
-    return NNS_OK;
+    const dim3 grid(xblocks, groups);
+    return with_qt<32, 8, 4, 1>(qt, [&](auto qtc) {
+        constexpr int QT = decltype(qtc)::value;
+        const size_t lds = (size_t)QT * k * sizeof(float);
+        if (tiled)
+            return launch_lds(exact_lane_ref_tiled_kernel<QT, T>, grid, dim3(256), lds + 4 * 64 * (8 * 16 + 16), st, k, n,
+                              q, r, qlist, qcount, mq, base, keys);
+        return launch_lds(vec ? exact_lane_ref_kernel<QT, 4, T> : exact_lane_ref_kernel<QT, 1, T>, grid, dim3(256), lds,
+                          st, k, n, q, r, qlist, qcount, mq, base, keys);
+    });
 }
 
 // query-tile width: as wide as the LDS tile (<= 64 KiB) and the registers allow
@@ -1759,19 +1710,6 @@ static int pick_qt(int k, int nq)
     if (qt >= 32) return 32;
     if (qt >= 8) return 8;
     return qt >= 4 ? 4 : 1;
-}
-
-template <typename T>
-static int launch_k1b(int k, int n, const T *q, const T *r, const int *qlist,
-                      const int *qcount, int mq, int qt, int groups, int64_t base,
-                      nns_key *keys, hipStream_t st)
-{
-    switch (qt) {
-    case 32: return launch_k1b_t<32, T>(k, n, q, r, qlist, qcount, mq, groups, base, keys, st);
-    case 8: return launch_k1b_t<8, T>(k, n, q, r, qlist, qcount, mq, groups, base, keys, st);
-    case 4: return launch_k1b_t<4, T>(k, n, q, r, qlist, qcount, mq, groups, base, keys, st);
-    default: return launch_k1b_t<1, T>(k, n, q, r, qlist, qcount, mq, groups, base, keys, st);
-    }
 }
 
 static int check_k(int k)

@@ -107,7 +107,7 @@ struct nns_index {
 
     // range search (K7): per-(query, chunk) offsets + scan tile sums, and what the last range count was run for (the
     // fill must match it)
-    void *range_ws = nullptr;
+    char *range_ws = nullptr;
     size_t range_ws_bytes = 0;
     bool range_counted = false;
     int range_m = 0;
@@ -461,6 +461,37 @@ static void profile_advance(nns_index *ix, int path)
     if (ix->ev_count < kEvRing) ++ix->ev_count;
 }
 
+extern "C++" {
+// grow an index-owned workspace to `need` elements (the old block may still be read by an earlier pass of this index:
+// back to the pool behind an event); false: the allocation failed, the index holds no workspace
+template <class T>
+static bool grow_index_ws(T **ws, size_t *have, size_t need, hipStream_t st)
+{
+    if (need <= *have) return true;
+    pool_free_after(*ws, st);
+    *ws = nullptr;
+    *have = 0;
+    if (pool_alloc(ws, need * sizeof(T)) != hipSuccess) return false;
+    *have = need;
+    return true;
+}
+
+// an exact-path pass of the index (top-K, range count / fill): run() between the profiling events, then the bookkeeping
+template <class F>
+static int index_exact_pass(nns_index *ix, int m, hipStream_t st, F &&run)
+{
+    const bool prof = ix->profile;
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
+    NNS_TRY(run());
+    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
+    ix->last_m = m;
+    ix->last_path = NNS_PATH_EXACT;
+    ix->searched = true;
+    profile_advance(ix, NNS_PATH_EXACT);
+    return NNS_OK;
+}
+}  // extern "C++"
+
 // idx_dev / dist_dev (optional): also leave the unpacked indices / distances (K1a writes them in its one
 // launch; every other path appends the unpack kernel)
 static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, nns_key *keys_dev, void *stream,
@@ -628,26 +659,13 @@ static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int k
     NNS_TRY(topk_plan(ix->k, m, ix->n, kn, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
-    if (p.ws_keys > ix->topk_ws_keys) {
-        // (the old block may still be read by an earlier search of this index: back to the pool behind an event)
-        pool_free_after(ix->topk_ws, st);
-        ix->topk_ws = nullptr;
-        ix->topk_ws_keys = 0;
-        if (pool_alloc(&ix->topk_ws, p.ws_keys * sizeof(nns_key)) != hipSuccess) {
-            set_error("nns_index_search_topk: split workspace allocation failed (%zu keys)", p.ws_keys);
-            return NNS_ERR_NOMEM;
-        }
-        ix->topk_ws_keys = p.ws_keys;
+    if (!grow_index_ws(&ix->topk_ws, &ix->topk_ws_keys, p.ws_keys, st)) {
+        set_error("nns_index_search_topk: split workspace allocation failed (%zu keys)", p.ws_keys);
+        return NNS_ERR_NOMEM;
     }
-    const bool prof = ix->profile;
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
-    NNS_TRY(launch_topk_search(p, ix->k, m, ix->n, kn, q_dev, ix->r_dev, ix->bf16, ix->base, keys_dev, ix->topk_ws, st));
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-    ix->last_m = m;
-    ix->last_path = NNS_PATH_EXACT;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_EXACT);
-    return NNS_OK;
+    return index_exact_pass(ix, m, st, [&] {
+        return launch_topk_search(p, ix->k, m, ix->n, kn, q_dev, ix->r_dev, ix->bf16, ix->base, keys_dev, ix->topk_ws, st);
+    });
 }
 
 int nns_index_search_topk(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, void *stream)
@@ -726,29 +744,17 @@ static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float
     NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
-    if (p.ws_bytes > ix->range_ws_bytes) {
-        // (the old block may still be read by an earlier pass of this index: back to the pool behind an event)
-        pool_free_after(ix->range_ws, st);
-        ix->range_ws = nullptr;
-        ix->range_ws_bytes = 0;
-        if (pool_alloc(&ix->range_ws, p.ws_bytes) != hipSuccess) {
-            set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
-            return NNS_ERR_NOMEM;
-        }
-        ix->range_ws_bytes = p.ws_bytes;
+    if (!grow_index_ws(&ix->range_ws, &ix->range_ws_bytes, p.ws_bytes, st)) {
+        set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
+        return NNS_ERR_NOMEM;
     }
-    const bool prof = ix->profile;
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
-    NNS_TRY(launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st));
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
+    NNS_TRY(index_exact_pass(ix, m, st, [&] {
+        return launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st);
+    }));
     ix->range_counted = true;
     ix->range_m = m;
     ix->range_q = q_dev;
     ix->range_r2 = radius2;
-    ix->last_m = m;
-    ix->last_path = NNS_PATH_EXACT;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_EXACT);
     return NNS_OK;
 }
 
@@ -765,17 +771,11 @@ static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float 
     NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
-    const bool prof = ix->profile;
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
-    if (idx_dev || dist_dev)
-        NNS_TRY(launch_range_fill(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, ix->base, lims_dev,
-                                  ix->range_ws, idx_dev, dist_dev, st));
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-    ix->last_m = m;
-    ix->last_path = NNS_PATH_EXACT;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_EXACT);
-    return NNS_OK;
+    return index_exact_pass(ix, m, st, [&] {
+        if (!idx_dev && !dist_dev) return (int)NNS_OK;
+        return launch_range_fill(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, ix->base, lims_dev,
+                                 ix->range_ws, idx_dev, dist_dev, st);
+    });
 }
 
 int nns_index_range_count(nns_index *ix, int m, const void *q_dev, float radius2, int64_t *lims_dev, void *stream)
@@ -1036,6 +1036,34 @@ struct HostCall {
         lib_stream_release(st);
     }
 };
+
+// The start of every whole call on its library stream: q and r allocated, then more() (the call's own device blocks),
+// both uploaded, dimension-major refs (NNS_REFS_SOA) transposed once into a point-major copy that *r_d then names
+template <class F>
+static int whole_call_upload(HostCall &call, const char *where, int k, int m, int n, const void *s_points,
+                             const void *r_points, size_t esz, unsigned flags, char **q_d, char **r_d, F &&more)
+{
+    const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz;
+    if (!call.alloc(q_d, qb) || !call.alloc(r_d, rb) || !more()) {
+        set_error("%s: device allocation failed", where);
+        return NNS_ERR_NOMEM;
+    }
+    if (call.copy(*q_d, s_points, qb, hipMemcpyHostToDevice) != hipSuccess ||
+        call.copy(*r_d, r_points, rb, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: H2D copy failed: %s", where, hipGetErrorString(hipGetLastError()));
+        return NNS_ERR_HIP;
+    }
+    if (flags & NNS_REFS_SOA) {
+        char *r_t = nullptr;
+        if (!call.alloc(&r_t, rb)) {
+            set_error("%s: device allocation failed (point-major copy)", where);
+            return NNS_ERR_NOMEM;
+        }
+        NNS_TRY(launch_soa_to_aos(k, n, *r_d, r_t, (int)esz, call.st));
+        *r_d = r_t;
+    }
+    return NNS_OK;
+}
 }  // namespace nns
 }  // extern "C++"
 
@@ -1281,36 +1309,19 @@ static int search_whole(const char *where, int k, int m, int n, const void *s_po
                         int kn, int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
     const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
-    const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz, rows = (size_t)m * (kn ? kn : 1);
+    const size_t rows = (size_t)m * (kn ? kn : 1);
     // kernels on a non-blocking stream of the library (nullptr if none can be made: the default stream then)
     HostCall call(lib_stream_acquire());
     const hipStream_t st = call.st;
-    char *q_d = nullptr, *r_d = nullptr, *r_t = nullptr;
+    char *q_d = nullptr, *r_d = nullptr;
     nns_key *keys = nullptr, *keys_tmp = nullptr;
     int *idx_d = nullptr;
     float *dist_d = nullptr;
-    if (!call.alloc(&q_d, qb) || !call.alloc(&r_d, rb) || !call.alloc(&keys, rows * sizeof(nns_key)) ||
-        (num_shards > 1 && !call.alloc(&keys_tmp, rows * sizeof(nns_key))) ||
-        !call.alloc(&idx_d, rows * sizeof(int)) ||
-        ((kn == 0 || dist_out) && !call.alloc(&dist_d, rows * sizeof(float)))) {
-        set_error("%s: device allocation failed", where);
-        return NNS_ERR_NOMEM;
-    }
-    if (call.copy(q_d, s_points, qb, hipMemcpyHostToDevice) != hipSuccess ||
-        call.copy(r_d, r_points, rb, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("%s: H2D copy failed: %s", where, hipGetErrorString(hipGetLastError()));
-        return NNS_ERR_HIP;
-    }
-    if (flags & NNS_REFS_SOA) {
-        // dimension-major refs: transpose once on the device, then shard the point-major copy
-        if (!call.alloc(&r_t, rb)) {
-            set_error("%s: device allocation failed (point-major copy)", where);
-            return NNS_ERR_NOMEM;
-        }
-        NNS_TRY(launch_soa_to_aos(k, n, r_d, r_t, (int)esz, st));
-        r_d = r_t;
-        flags &= ~(unsigned)NNS_REFS_SOA;
-    }
+    NNS_TRY(whole_call_upload(call, where, k, m, n, s_points, r_points, esz, flags, &q_d, &r_d, [&] {
+        return call.alloc(&keys, rows * sizeof(nns_key)) && (num_shards <= 1 || call.alloc(&keys_tmp, rows * sizeof(nns_key))) &&
+               call.alloc(&idx_d, rows * sizeof(int)) && ((kn != 0 && !dist_out) || call.alloc(&dist_d, rows * sizeof(float)));
+    }));
+    flags &= ~(unsigned)NNS_REFS_SOA;   // (the shards index the point-major copy)
     // top-K's shard indexes skip the MFMA filter's ref pre-pass (it reads the point-major refs only)
     const unsigned create_flags = kn ? NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync : flags;
     for (int s = 0; s < num_shards; ++s) {
@@ -1369,6 +1380,18 @@ static int search_host_impl(int k, int m, int n, const void *s_points, const voi
                         device);
 }
 
+// the flags of the whole calls that run the exact path only (`what`: top-K, range search)
+static int check_exact_only_flags(const char *where, const char *what, unsigned flags)
+{
+    const unsigned path = flags & NNS_PATH_MASK;
+    if ((path != NNS_PATH_AUTO && path != NNS_PATH_EXACT) || (flags & ~(unsigned)(NNS_PATH_MASK | NNS_REFS_SOA | NNS_PROFILE))) {
+        set_error("%s: flags 0x%x: %s accepts the auto / exact path, dimension-major refs and profiling only", where, flags,
+                  what);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
 static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
                                  int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
@@ -1379,11 +1402,7 @@ static int search_topk_host_impl(int k, int m, int n, const void *s_points, cons
         set_error("%s: m * kn too large for one call", where);
         return NNS_ERR_INVALID;
     }
-    const unsigned path = flags & NNS_PATH_MASK;
-    if ((path != NNS_PATH_AUTO && path != NNS_PATH_EXACT) || (flags & ~(unsigned)(NNS_PATH_MASK | NNS_REFS_SOA | NNS_PROFILE))) {
-        set_error("%s: flags 0x%x: top-K accepts the auto / exact path, dimension-major refs and profiling only", where, flags);
-        return NNS_ERR_UNSUPPORTED;
-    }
+    NNS_TRY(check_exact_only_flags(where, "top-K", flags));
     TopkPlan p{};
     NNS_TRY(topk_plan(k, m, n, kn, &p));   // (k beyond the exact path: before any device work)
     DeviceScope keep_device;
@@ -1401,31 +1420,15 @@ static int search_whole_range(const char *where, int k, int m, int n, const void
                               int device)
 {
     const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
-    const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz, lb = ((size_t)m + 1) * sizeof(int64_t);
+    const size_t lb = ((size_t)m + 1) * sizeof(int64_t);
     HostCall call(lib_stream_acquire());
     const hipStream_t st = call.st;
-    char *q_d = nullptr, *r_d = nullptr, *r_t = nullptr;
+    char *q_d = nullptr, *r_d = nullptr;
     int64_t *lims_d = nullptr;
     int *idx_d = nullptr;
     float *dist_d = nullptr;
-    if (!call.alloc(&q_d, qb) || !call.alloc(&r_d, rb) || !call.alloc(&lims_d, lb)) {
-        set_error("%s: device allocation failed", where);
-        return NNS_ERR_NOMEM;
-    }
-    if (call.copy(q_d, s_points, qb, hipMemcpyHostToDevice) != hipSuccess ||
-        call.copy(r_d, r_points, rb, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("%s: H2D copy failed: %s", where, hipGetErrorString(hipGetLastError()));
-        return NNS_ERR_HIP;
-    }
-    if (flags & NNS_REFS_SOA) {
-        // dimension-major refs: transpose once on the device into a point-major copy
-        if (!call.alloc(&r_t, rb)) {
-            set_error("%s: device allocation failed (point-major copy)", where);
-            return NNS_ERR_NOMEM;
-        }
-        NNS_TRY(launch_soa_to_aos(k, n, r_d, r_t, (int)esz, st));
-        r_d = r_t;
-    }
+    NNS_TRY(whole_call_upload(call, where, k, m, n, s_points, r_points, esz, flags, &q_d, &r_d,
+                              [&] { return call.alloc(&lims_d, lb); }));
     // (the exact path's index: no MFMA ref pre-pass, it reads the point-major refs only)
     NNS_TRY(index_create_impl(&call.ix, device, k, n, r_d, bf16, 0, NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync,
                               st));
@@ -1473,12 +1476,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     // (lims_out stands for the output buffer of the shared check)
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
     NNS_TRY(range_check_radius(where, radius2));
-    const unsigned path = flags & NNS_PATH_MASK;
-    if ((path != NNS_PATH_AUTO && path != NNS_PATH_EXACT) || (flags & ~(unsigned)(NNS_PATH_MASK | NNS_REFS_SOA | NNS_PROFILE))) {
-        set_error("%s: flags 0x%x: range search accepts the auto / exact path, dimension-major refs and profiling only",
-                  where, flags);
-        return NNS_ERR_UNSUPPORTED;
-    }
+    NNS_TRY(check_exact_only_flags(where, "range search", flags));
     RangePlan p{};
     NNS_TRY(range_plan(k, m, n, &p));   // (k beyond the exact path: before any device work)
     DeviceScope keep_device;

@@ -91,6 +91,53 @@ static inline ShardRange shard_range(int n, int shards, int s)
     return {(int)beg, beg + per <= n ? per : (beg < n ? (int)(n - beg) : 0)};
 }
 
+// ---- launch helpers ---------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, QT>{}) for the first QT of the list equal to qt; the last one takes any other value
+template <int QT, int... REST, class F>
+static inline int with_qt(int qt, F &&f)
+{
+    if constexpr (sizeof...(REST) == 0) return f(std::integral_constant<int, QT>{});
+    else return qt == QT ? f(std::integral_constant<int, QT>{}) : with_qt<REST...>(qt, f);
+}
+
+// launch kern with `lds` bytes of dynamic LDS (above 48 KiB the kernel's limit is raised first)
+template <typename... P, typename... A>
+static inline int launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args)
+{
+    if (lds > 48 * 1024)
+        NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+// The grid of a lane-per-ref scan (K6, K7; 256 lanes per workgroup, one ref per lane and round): the query-tile width
+// qt halves from qt0 while the fp32 query tile passes 64 KiB or qt * lds_per_query passes lds_max (0, 0: no further
+// limit), then while half the tile still holds all m queries.  The refs are split so that there are about 2048
+// workgroups (8 per CU), every split holds at least min_per refs and the workspace, ws_per_split bytes per split,
+// stays within ws_budget; every split is whole 256-ref rounds, and the recount leaves no split empty.
+struct LaneScanGrid {
+    int qt, qgroups, splits, per;
+};
+static inline LaneScanGrid lane_scan_grid(int k, int m, int n, int qt0, size_t lds_per_query, size_t lds_max,
+                                          int64_t min_per, size_t ws_per_split, size_t ws_budget)
+{
+    int qt = qt0;
+    while (qt > 1 && ((size_t)qt * k * sizeof(float) > 64 * 1024 || qt * lds_per_query > lds_max)) qt >>= 1;
+    while (qt > 1 && qt / 2 >= m) qt >>= 1;
+    const int qgroups = divup(m, qt);
+    int64_t splits = divup(2048, qgroups);
+    const int64_t by_refs = divup64(n, min_per);
+    if (splits > by_refs) splits = by_refs;
+    const int64_t by_ws = (int64_t)(ws_budget / ws_per_split);
+    if (splits > by_ws) splits = by_ws;
+    if (splits > 65535) splits = 65535;
+    if (splits < 1) splits = 1;
+    const int64_t per = divup64(divup64(n, splits), 256) * 256;
+    splits = divup64(n, per);
+    return {qt, qgroups, (int)splits, (int)(per < n ? per : n)};
+}
+
 // ---- packed keys --------------------------------------------------------------
 // (fp32 bits << 32) | index; distances are >= +0 so integer order == (distance,
 // index) lexicographic order == V0's rule (reference core.cu:44).
@@ -113,12 +160,12 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
     return __fadd_rn(sum, __fmul_rn(diff, diff));
 }
 
-// point loads of the lane-per-ref scans (K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16) aligned
-// row; bf16 bits are widened exactly
-__device__ __forceinline__ float tk_ld1(const float *p) { return *p; }
-__device__ __forceinline__ float tk_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ float4 tk_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float4 tk_ld4(const uint16_t *p)
+// point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16)
+// aligned row; bf16 bits are widened exactly
+__device__ __forceinline__ float pt_ld1(const float *p) { return *p; }
+__device__ __forceinline__ float pt_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
+__device__ __forceinline__ float4 pt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 pt_ld4(const uint16_t *p)
 {
     const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 bf16, widened exactly
     float4 o;
@@ -127,6 +174,54 @@ __device__ __forceinline__ float4 tk_ld4(const uint16_t *p)
     o.z = __uint_as_float(v.y << 16);
     o.w = __uint_as_float(v.y & 0xFFFF0000u);
     return o;
+}
+
+// ---- the lane-per-ref scan core (K1b, K6, K7) ----------------------------------------------------------------------
+// One lane holds one ref row rj; the fp32 query tile sq[QT][k] sits in LDS and is read by broadcast.  sum[u] = V0's
+// distance of query u to the ref: one t-ascending v0_step chain per query (VEC 4: a float4 of the row per step, k % 4 == 0
+// and the row 16- / 8-byte aligned; VEC 1: one value per step, the loop unrolled UNROLL times).
+template <int QT, int VEC, int UNROLL, typename T>
+__device__ __forceinline__ void v0_lane_chains(int k, const float *sq, const T *rj, float (&sum)[QT])
+{
+#pragma unroll
+    for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
+    if (VEC == 4) {
+        for (int t = 0; t < k; t += 4) {
+            const float4 rv = pt_ld4(rj + t);
+#pragma unroll
+            for (int u = 0; u < QT; ++u) {
+                const float4 qv = *reinterpret_cast<const float4 *>(&sq[u * k + t]);   // broadcast
+                float s = sum[u];
+                s = v0_step(s, qv.x, rv.x);
+                s = v0_step(s, qv.y, rv.y);
+                s = v0_step(s, qv.z, rv.z);
+                s = v0_step(s, qv.w, rv.w);
+                sum[u] = s;
+            }
+        }
+    } else {
+#pragma unroll UNROLL
+        for (int t = 0; t < k; ++t) {
+            const float rv = pt_ld1(rj + t);
+#pragma unroll
+            for (int u = 0; u < QT; ++u) sum[u] = v0_step(sum[u], sq[u * k + t], rv);
+        }
+    }
+}
+
+// K6 / K7's VEC 1 unroll: what the compiler chose for their loops before they shared v0_lane_chains (through the
+// helper it left QT = 16 rolled, 10 % slower at k = 3).  K1b's grid-stride scan passes 1: it was never unrolled.
+template <int QT>
+constexpr int kLaneScanUnroll = QT >= 8 ? 2 : QT == 4 ? 4 : 8;
+
+// the query tile of K6 / K7: queries q0 .. q0 + QT - 1 widened to fp32 into sq[QT][k], zeros past m
+template <int QT, int THREADS, typename T>
+__device__ __forceinline__ void load_query_tile(float *sq, const T *q, int q0, int m, int k)
+{
+    for (int e = threadIdx.x; e < QT * k; e += THREADS) {
+        const int u = e / k, t = e - u * k;
+        sq[e] = q0 + u < m ? pt_ld1(q + (size_t)(q0 + u) * k + t) : 0.0f;
+    }
 }
 
 // LDS-DMA (global_load_lds_*): 64 lanes x {16, 4} bytes from per-lane global addresses to

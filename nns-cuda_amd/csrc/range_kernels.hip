@@ -19,7 +19,6 @@ namespace nns {
 constexpr int kRangeThreads = 256;
 constexpr int kRangeWaves = kRangeThreads / 64;
 constexpr size_t kRangeWsBudget = (size_t)256 << 20;   // workspace cap (include/nns.h)
-constexpr int kRangeTargetWgs = 2048;                  // about 8 workgroups per CU
 constexpr int kRangeMinPerChunk = 1024;                // refs a chunk sees at least (its query tile load amortises)
 constexpr int kRangeMaxGridX = 1 << 20;                // query groups per grid row (2^28 lanes; the limit is 2^32)
 constexpr int kScanItems = 16;
@@ -57,10 +56,7 @@ __global__ __launch_bounds__(kRangeThreads) void range_scan_kernel(int k, int m,
     const int j0 = (int)((int64_t)c * per);
     const int j1 = (int64_t)j0 + per < n ? j0 + per : n;
 
-    for (int e = tid; e < QT * k; e += kRangeThreads) {
-        const int u = e / k, t = e - u * k;
-        sq[e] = q0 + u < m ? tk_ld1(q + (size_t)(q0 + u) * k + t) : 0.0f;
-    }
+    load_query_tile<QT, kRangeThreads>(sq, q, q0, m, k);
     if (FILL && tid < QT) {
         const bool live = q0 + tid < m;
         start[tid] = live ? lims[q0 + tid] + (chunks > 1 ? offs[(size_t)(q0 + tid) * chunks + c] : 0) : 0;
@@ -78,32 +74,7 @@ __global__ __launch_bounds__(kRangeThreads) void range_scan_kernel(int k, int m,
         float sum[QT];
 #pragma unroll
         for (int u = 0; u < QT; ++u) sum[u] = __builtin_nanf("");   // a lane past the chunk's end hits nothing
-        if (j < j1) {
-            const T *rj = r + (size_t)j * k;
-#pragma unroll
-            for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
-            if (VEC == 4) {
-                for (int t = 0; t < k; t += 4) {
-                    const float4 rv = tk_ld4(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) {
-                        const float4 qv = *reinterpret_cast<const float4 *>(&sq[u * k + t]);   // broadcast
-                        float s = sum[u];
-                        s = v0_step(s, qv.x, rv.x);
-                        s = v0_step(s, qv.y, rv.y);
-                        s = v0_step(s, qv.z, rv.z);
-                        s = v0_step(s, qv.w, rv.w);
-                        sum[u] = s;
-                    }
-                }
-            } else {
-                for (int t = 0; t < k; ++t) {
-                    const float rv = tk_ld1(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) sum[u] = v0_step(sum[u], sq[u * k + t], rv);
-                }
-            }
-        }
+        if (j < j1) v0_lane_chains<QT, VEC, kLaneScanUnroll<QT>>(k, sq, r + (size_t)j * k, sum);
         // (every lane of the workgroup reaches the ballots: the round count is workgroup-uniform)
         unsigned hits = 0;   // bit u: this lane's ref is a hit of query u
 #pragma unroll
@@ -272,49 +243,19 @@ int range_plan(int k, int m, int n, RangePlan *p)
         set_error("range search: k = %d exceeds the LDS query tile (k <= 16384)", k);
         return NNS_ERR_UNSUPPORTED;
     }
-    // query-tile width: 16 queries, fewer if the 64 KiB query tile runs out or there are fewer queries
-    int qt = 16;
-    while (qt > 1 && (size_t)qt * k * sizeof(float) > 64 * 1024) qt >>= 1;
-    while (qt > 1 && qt / 2 >= m) qt >>= 1;
-    const int qgroups = divup(m, qt);
+    // query-tile width: 16 queries; ref chunks worth their query tile
     const int tiles = divup(m, kScanTile);
     const size_t sums_bytes = tiles > 1 ? (size_t)tiles * sizeof(int64_t) : 0;
-    // ref chunks: enough workgroups to fill the chip, every chunk worth its query tile, workspace within budget
-    int64_t chunks = divup(kRangeTargetWgs, qgroups);
-    const int64_t by_refs = divup64(n, kRangeMinPerChunk);
-    if (chunks > by_refs) chunks = by_refs;
-    const int64_t by_ws = (int64_t)((kRangeWsBudget - sums_bytes) / ((size_t)m * sizeof(int)));
-    if (chunks > by_ws) chunks = by_ws;
-    if (chunks > 65535) chunks = 65535;
-    if (chunks < 1) chunks = 1;
-    // whole rounds per chunk; recount so that no chunk is empty
-    const int64_t per = divup64(divup64(n, chunks), kRangeThreads) * kRangeThreads;
-    chunks = divup64(n, per);
-    p->qt = qt;
-    p->qgroups = qgroups;
-    p->chunks = (int)chunks;
-    p->per = (int)(per < n ? per : n);
+    const LaneScanGrid g = lane_scan_grid(k, m, n, 16, 0, 0, kRangeMinPerChunk, (size_t)m * sizeof(int),
+                                          kRangeWsBudget - sums_bytes);
+    p->qt = g.qt;
+    p->qgroups = g.qgroups;
+    p->chunks = g.splits;
+    p->per = g.per;
     // (the query tile, then the static per-wave counts and the fill's segment starts / ends)
-    p->lds = (int)((size_t)qt * k * sizeof(float) + 2 * kRangeWaves * qt * sizeof(int) + 2 * qt * sizeof(int64_t));
+    p->lds = (int)((size_t)g.qt * k * sizeof(float) + 2 * kRangeWaves * g.qt * sizeof(int) + 2 * g.qt * sizeof(int64_t));
     p->tiles = tiles;
     p->ws_bytes = range_offs_bytes(*p, m) + sums_bytes;
-    return NNS_OK;
-}
-
-template <int QT, bool FILL, typename T>
-static int launch_range_scan_t(const RangePlan &p, int k, int m, int n, const T *q, const T *r, float radius2,
-                               int64_t base, int64_t *lims, int *offs, int *idx, float *dist, hipStream_t st)
-{
-    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
-    const size_t lds = (size_t)QT * k * sizeof(float);
-    auto kern = vec ? range_scan_kernel<QT, 4, T, FILL> : range_scan_kernel<QT, 1, T, FILL>;
-    if (lds > 48 * 1024)
-        NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned gx = p.qgroups < kRangeMaxGridX ? p.qgroups : kRangeMaxGridX;
-    const unsigned gz = (unsigned)divup(p.qgroups, (int)gx);
-    hipLaunchKernelGGL(kern, dim3(gx, p.chunks, gz), dim3(kRangeThreads), lds, st, k, m, n, p.per, p.chunks, radius2,
-                       q, r, base, lims, offs, idx, dist);
-    NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
 
@@ -323,13 +264,15 @@ static int launch_range_scan(const RangePlan &p, int k, int m, int n, const void
                              int64_t base, int64_t *lims, int *offs, int *idx, float *dist, hipStream_t st)
 {
     const T *qt = (const T *)q, *rt = (const T *)r;
-    switch (p.qt) {
-    case 16: return launch_range_scan_t<16, FILL, T>(p, k, m, n, qt, rt, radius2, base, lims, offs, idx, dist, st);
-    case 8: return launch_range_scan_t<8, FILL, T>(p, k, m, n, qt, rt, radius2, base, lims, offs, idx, dist, st);
-    case 4: return launch_range_scan_t<4, FILL, T>(p, k, m, n, qt, rt, radius2, base, lims, offs, idx, dist, st);
-    case 2: return launch_range_scan_t<2, FILL, T>(p, k, m, n, qt, rt, radius2, base, lims, offs, idx, dist, st);
-    default: return launch_range_scan_t<1, FILL, T>(p, k, m, n, qt, rt, radius2, base, lims, offs, idx, dist, st);
-    }
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    const unsigned gx = p.qgroups < kRangeMaxGridX ? p.qgroups : kRangeMaxGridX;
+    const unsigned gz = (unsigned)divup(p.qgroups, (int)gx);
+    return with_qt<16, 8, 4, 2, 1>(p.qt, [&](auto qtc) {
+        constexpr int QT = decltype(qtc)::value;
+        return launch_lds(vec ? range_scan_kernel<QT, 4, T, FILL> : range_scan_kernel<QT, 1, T, FILL>,
+                          dim3(gx, p.chunks, gz), dim3(kRangeThreads), (size_t)QT * k * sizeof(float), st, k, m, n,
+                          p.per, p.chunks, radius2, qt, rt, base, lims, offs, idx, dist);
+    });
 }
 
 int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,

@@ -23,8 +23,7 @@ constexpr int kTopkThreads = 256;
 constexpr int kTopkQueue = 512;                    // queue capacity per query (keys)
 constexpr int kTopkFlushAt = kTopkQueue - kTopkThreads;   // a queue this full is flushed before the next round
 constexpr size_t kTopkLdsMax = 160 * 1024;
-constexpr size_t kTopkWsBudgetKeys = (size_t)32 << 20;   // 256 MiB of split workspace at most
-constexpr int kTopkTargetWgs = 2048;               // about 8 workgroups per CU
+constexpr size_t kTopkWsBudget = (size_t)256 << 20;   // split workspace at most
 constexpr int kTopkMinPerSplit = 2048;             // refs a split sees at least (so that its list warm-up amortises)
 
 // number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
@@ -63,10 +62,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, i
     const int j0 = blockIdx.y * per;
     const int j1 = (int64_t)j0 + per < n ? j0 + per : n;
 
-    for (int e = tid; e < QT * k; e += kTopkThreads) {
-        const int u = e / k, t = e - u * k;
-        sq[e] = q0 + u < m ? tk_ld1(q + (size_t)(q0 + u) * k + t) : 0.0f;
-    }
+    load_query_tile<QT, kTopkThreads>(sq, q, q0, m, k);
     for (int e = tid; e < 2 * QT * kn; e += kTopkThreads) lists[e] = NNS_KEY_NONE;
     if (tid < QT) qcnt[tid] = 0;
     __syncthreads();
@@ -80,31 +76,8 @@ __global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, i
         const int j = j0 + rd * kTopkThreads + tid;
         int near_full = 0;
         if (j < j1) {
-            const T *rj = r + (size_t)j * k;
             float sum[QT];
-#pragma unroll
-            for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
-            if (VEC == 4) {
-                for (int t = 0; t < k; t += 4) {
-                    const float4 rv = tk_ld4(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) {
-                        const float4 qv = *reinterpret_cast<const float4 *>(&sq[u * k + t]);   // broadcast
-                        float s = sum[u];
-                        s = v0_step(s, qv.x, rv.x);
-                        s = v0_step(s, qv.y, rv.y);
-                        s = v0_step(s, qv.z, rv.z);
-                        s = v0_step(s, qv.w, rv.w);
-                        sum[u] = s;
-                    }
-                }
-            } else {
-                for (int t = 0; t < k; ++t) {
-                    const float rv = tk_ld1(rj + t);
-#pragma unroll
-                    for (int u = 0; u < QT; ++u) sum[u] = v0_step(sum[u], sq[u * k + t], rv);
-                }
-            }
+            v0_lane_chains<QT, VEC, kLaneScanUnroll<QT>>(k, sq, r + (size_t)j * k, sum);
 #pragma unroll
             for (int u = 0; u < QT; ++u) {
                 const nns_key key = make_key(sum[u], index_base + j);   // NaN / +INF -> NNS_KEY_NONE: never below thr
@@ -251,45 +224,16 @@ int topk_plan(int k, int m, int n, int kn, TopkPlan *p)
         set_error("top-K: k = %d exceeds the LDS query tile (k <= 16384)", k);
         return NNS_ERR_UNSUPPORTED;
     }
-    // query-tile width: 16 queries while the lists are short, 8 beyond; fewer if the query tile or LDS runs out
-    int qt = kn <= 16 ? 16 : 8;
-    while (qt > 1 && ((size_t)qt * k * sizeof(float) > 64 * 1024 || topk_lds_bytes(qt, k, kn) > kTopkLdsMax)) qt >>= 1;
-    while (qt > 1 && qt / 2 >= m) qt >>= 1;
-    const int qgroups = divup(m, qt);
-    // ref splits: enough workgroups to fill the chip, every split worth its list warm-up, workspace within budget
-    int64_t splits = divup(kTopkTargetWgs, qgroups);
-    const int64_t min_per = kn * 16 > kTopkMinPerSplit ? kn * 16 : kTopkMinPerSplit;
-    const int64_t by_refs = divup64(n, min_per);
-    if (splits > by_refs) splits = by_refs;
-    const int64_t by_ws = (int64_t)(kTopkWsBudgetKeys / ((size_t)m * kn));
-    if (splits > by_ws) splits = by_ws;
-    if (splits > 65535) splits = 65535;
-    if (splits < 1) splits = 1;
-    // whole rounds per split; recount so that no split is empty
-    int64_t per = divup64(divup64(n, splits), kTopkThreads) * kTopkThreads;
-    splits = divup64(n, per);
-    p->qt = qt;
-    p->qgroups = qgroups;
-    p->splits = (int)splits;
-    p->per = (int)(per < n ? per : n);
-    if (splits == 1) p->per = n;
-    p->lds = (int)(topk_lds_bytes(qt, k, kn) + qt * sizeof(int));
-    p->ws_keys = splits > 1 ? (size_t)splits * m * kn : 0;
-    return NNS_OK;
-}
-
-template <int QT, typename T>
-static int launch_topk_scan_t(const TopkPlan &p, int k, int m, int n, int kn, const T *q, const T *r, int64_t base,
-                              nns_key *out, hipStream_t st)
-{
-    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
-    const size_t lds = topk_lds_bytes(QT, k, kn);
-    const dim3 grid(p.qgroups, p.splits);
-    auto kern = vec ? topk_scan_kernel<QT, 4, T> : topk_scan_kernel<QT, 1, T>;
-    if (lds > 48 * 1024)
-        NNS_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, grid, dim3(kTopkThreads), lds, st, k, m, n, p.per, kn, q, r, base, out);
-    NNS_HIP(hipGetLastError());
+    // query-tile width: 16 queries while the lists are short, 8 beyond; ref splits worth their list warm-up
+    const LaneScanGrid g = lane_scan_grid(k, m, n, kn <= 16 ? 16 : 8, topk_lds_bytes(1, k, kn), kTopkLdsMax,
+                                          kn * 16 > kTopkMinPerSplit ? kn * 16 : kTopkMinPerSplit,
+                                          (size_t)m * kn * sizeof(nns_key), kTopkWsBudget);
+    p->qt = g.qt;
+    p->qgroups = g.qgroups;
+    p->splits = g.splits;
+    p->per = g.per;
+    p->lds = (int)(topk_lds_bytes(g.qt, k, kn) + g.qt * sizeof(int));
+    p->ws_keys = g.splits > 1 ? (size_t)g.splits * m * kn : 0;
     return NNS_OK;
 }
 
@@ -297,13 +241,12 @@ template <typename T>
 static int launch_topk_scan(const TopkPlan &p, int k, int m, int n, int kn, const T *q, const T *r, int64_t base,
                             nns_key *out, hipStream_t st)
 {
-    switch (p.qt) {
-    case 16: return launch_topk_scan_t<16, T>(p, k, m, n, kn, q, r, base, out, st);
-    case 8: return launch_topk_scan_t<8, T>(p, k, m, n, kn, q, r, base, out, st);
-    case 4: return launch_topk_scan_t<4, T>(p, k, m, n, kn, q, r, base, out, st);
-    case 2: return launch_topk_scan_t<2, T>(p, k, m, n, kn, q, r, base, out, st);
-    default: return launch_topk_scan_t<1, T>(p, k, m, n, kn, q, r, base, out, st);
-    }
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    return with_qt<16, 8, 4, 2, 1>(p.qt, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        return launch_lds(vec ? topk_scan_kernel<QT, 4, T> : topk_scan_kernel<QT, 1, T>, dim3(p.qgroups, p.splits),
+                          dim3(kTopkThreads), topk_lds_bytes(QT, k, kn), st, k, m, n, p.per, kn, q, r, base, out);
+    });
 }
 
 int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,

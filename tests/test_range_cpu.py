@@ -49,7 +49,7 @@ def range_case_id(c):
 
 
 def scan_vec(k, ptr, elem_bytes):
-    """The scan's ref load width for refs at address ptr (launch_range_scan_t's rule, as K6's)."""
+    """The scan's ref load width for refs at address ptr (launch_range_scan's rule, as K6's)."""
     return 4 if k % 4 == 0 and ptr % (4 * elem_bytes) == 0 else 1
 
 

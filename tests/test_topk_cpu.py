@@ -47,7 +47,7 @@ def scan_case_id(c):
 
 
 def scan_vec(k, ptr, elem_bytes):
-    """The scan's ref load width for refs at address ptr (launch_topk_scan_t's rule)."""
+    """The scan's ref load width for refs at address ptr (launch_topk_scan's rule)."""
     return 4 if k % 4 == 0 and ptr % (4 * elem_bytes) == 0 else 1
 
 
