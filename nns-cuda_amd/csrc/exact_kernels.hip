@@ -502,50 +502,39 @@ __global__ __launch_bounds__(64 * MAXNW) void exact_lane_query_kernel(
     K1A_STAMP(11);
 }
 
-// geometry of a K1a launch
-struct K1aPlan {
-    int qtiles, nw, splits, per;
-};
+// geometry of a K1a launch; without the merge workspace, one ref range per query tile — slower, still one launch
 template <int K>
-static K1aPlan k1a_plan(int m, int n)
+static void k1a_plan(int m, int n, bool have_ws, ExactPlan *p)
 {
     constexpr int CH = K1aChunk<K>::value;
-    K1aPlan p;
-    p.qtiles = divup(m, 64 * K1A_QPL);
+    p->kernel = EXACT_K1A;
+    p->qtiles = divup(m, 64 * K1A_QPL);
+    p->qt = 64 * K1A_QPL;
     // waves per workgroup: up to the target wave count with ONE ref range per query tile, each wave with at least
     // 4 chunks of work per LDS tile; normally at most 8 (four workgroups per CU: one's head / tail / barrier waits are another's issue slots;
     // 16-wave workgroups measured 4 % slower at C2 and 30 % slower on the 16-D scalar-ref form), 16 only where the
     // finer cut would need more than 256 ref ranges per query tile (few queries: m = 100 x n = 100000)
     int nw = 1, splits = 1;
     for (int cap = NNS_K1A_NW; cap <= K1A_MAXNW; cap *= 2) {
-        nw = divup(NNS_K1A_WAVES, p.qtiles);
+        nw = divup(NNS_K1A_WAVES, p->qtiles);
         if (nw > cap) nw = cap;
         while (nw > 1 && (int64_t)nw * 4 * CH > n) nw >>= 1;
         if (nw < 1) nw = 1;
         // ref splits: the rest of the way to the target, >= 16 refs per wave (small problems are launch-bound: a
         // finer cut spreads 1024 x 4096 x 3 over 128 workgroups instead of 32: 12 -> 8 us; 512 x 8192 x 16: 46 -> 26)
-        splits = divup(NNS_K1A_WAVES, p.qtiles * nw);
+        splits = divup(NNS_K1A_WAVES, p->qtiles * nw);
         const int max_splits = divup(n, (NNS_K1A_MIN_REFS_PER_WAVE) * nw);
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
         if (splits <= 256) break;
     }
-    p.nw = nw;
+    p->waves = nw;
     if (splits > 65535) splits = 65535;
+    if (!have_ws) splits = 1;
     int per = divup(n, splits);
     per = divup(per, CH) * CH;
-    p.per = per;
-    p.splits = divup(n, per);
-    return p;
-}
-
-// workspace of the cross-split merge, in keys (8-byte units): the accumulator + the counters
-template <int K>
-static size_t k1a_workspace_keys(int m, int n)
-{
-    const K1aPlan p = k1a_plan<K>(m, n);
-    if (p.splits <= 1) return 0;
-    return (size_t)m + ((size_t)p.qtiles * sizeof(int) + 7) / 8 + 1;
+    p->per = per;
+    p->splits = divup(n, per);
 }
 
 // K1f (below): the filter + exact re-rank form of this search for k <= 3
@@ -575,63 +564,55 @@ __global__ void lowdim_filter_kernel(int m, int n, int refs_per_split, const flo
 #ifndef NNS_K1F_WAVES
 #define NNS_K1F_WAVES 4096   // target number of waves in a K1f grid (4 per SIMD)
 #endif
+// K1a's plan, re-cut for K1f where that form pays: k <= 3, eight-wave workgroups with at least a few chunks per wave,
+// enough pairs to pay for the re-rank stage.  Ranges are whole 16-ref chunks; with several of them K1f needs the merge
+// workspace, which K1a's plan has then already claimed.  The workspace: the accumulator + an arrival counter per query tile.
 template <int K>
-static bool k1f_wanted(int m, int n, const K1aPlan &p)
+static void k1a_k1f_plan(int m, int n, bool have_ws, ExactPlan *p)
 {
-#ifdef NNS_K1F_OFF   // (A/B builds)
-    return false;
-#else
-    return K <= 3 && p.nw == 8 && p.per >= NNS_K1F_MIN_PER && (int64_t)m * n >= NNS_K1F_MIN_PAIRS;
-#endif
-}
-
-template <int K>
-static int launch_k1a(int m, int n, const float *q, const float *r, int64_t base,
-                      nns_key *keys, nns_key *ws, size_t ws_keys, bool ws_fresh, int *idx_out, float *dist_out,
-                      hipStream_t st)
-{
-    K1aPlan p = k1a_plan<K>(m, n);
-    K1aMerge mg{};
-    mg.idx_out = idx_out;
-    mg.dist_out = dist_out;
-    if (p.splits > 1) {
-        if (!ws || ws_keys < k1a_workspace_keys<K>(m, n)) {
-            // no workspace (allocation failed): one ref range per query tile — slower, still one launch
-            p.splits = 1;
-            p.per = divup(n, K1aChunk<K>::value) * K1aChunk<K>::value;
-        } else {
-            mg.acc = ws;
-            mg.cnt = reinterpret_cast<int *>(ws + m);
-            // accumulator and counters re-arm themselves; a fresh (or re-laid-out) workspace is armed once
-            if (ws_fresh) {
-                NNS_TRY(launch_keys_fill(mg.acc, m, NNS_KEY_NONE, st));
-                NNS_HIP(hipMemsetAsync(mg.cnt, 0, (size_t)p.qtiles * sizeof(int), st));
-            }
+    k1a_plan<K>(m, n, have_ws, p);
+    const bool merge = p->splits > 1;
+#ifndef NNS_K1F_OFF   // (A/B builds)
+    if (K <= 3 && p->waves == 8 && p->per >= NNS_K1F_MIN_PER && (int64_t)m * n >= NNS_K1F_MIN_PAIRS) {
+        // ~110 registers at k = 3: four waves per SIMD, two workgroups per CU — cut for ONE round of them
+        const int qtiles = divup(m, 64 * K1F_QPL);
+        int want = divup(NNS_K1F_WAVES, qtiles * 8);
+        const int maxs = divup(n, NNS_K1F_MIN_PER);
+        if (want > maxs) want = maxs;
+        if (want < 1) want = 1;
+        const int per = divup(divup(n, want), K1F_CH) * K1F_CH;
+        const int splits = divup(n, per);
+        if (splits <= 1 || merge) {
+            p->kernel = EXACT_K1F;
+            p->qtiles = qtiles;
+            p->splits = splits;
+            p->per = per;
+            p->qt = 64 * K1F_QPL;   // (eight waves, as K1a's plan)
         }
     }
+#endif
+    if (merge) {
+        p->ws_counters = p->qtiles;
+        p->ws_keys = (size_t)m + ((size_t)p->qtiles * sizeof(int) + 7) / 8 + 1;
+    }
+}
+
+// K1a or K1f, as planned
+template <int K>
+static int launch_k1a(const ExactPlan &p, int m, int n, const float *q, const float *r, int64_t base, nns_key *keys,
+                      nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out, hipStream_t st)
+{
+    K1aMerge mg{};
     mg.splits = p.splits;
-    // k <= 3, eight-wave workgroups with at least a few chunks per wave, enough pairs to pay for the re-rank stage:
-    // the filter + exact re-rank form (K1f).  Same grid, same merge workspace; ranges are whole 16-ref chunks.
-    bool use_f = false;
-    int per_f = 0;
-    if constexpr (K <= 3) {
-        if (k1f_wanted<K>(m, n, p)) {
-            // ~110 registers at k = 3: four waves per SIMD, two workgroups per CU — cut for ONE round of them; a
-            // workgroup holds 64 x K1F_QPL queries (the counters of the merge workspace are per 128 queries: enough)
-            const int qtf = divup(m, 64 * K1F_QPL);
-            int want = divup(NNS_K1F_WAVES, qtf * 8);
-            const int maxs = divup(n, NNS_K1F_MIN_PER);
-            if (want > maxs) want = maxs;
-            if (want < 1) want = 1;
-            const int per = divup(divup(n, want), K1F_CH) * K1F_CH;
-            const int splits = divup(n, per);
-            if (splits <= 1 || mg.acc) {   // (the merge workspace does not depend on the cut)
-                use_f = true;
-                per_f = per;
-                p.qtiles = qtf;
-                p.splits = splits;
-                mg.splits = splits;
-            }
+    mg.idx_out = idx_out;
+    mg.dist_out = dist_out;
+    if (p.ws_keys) {
+        mg.acc = ws;
+        mg.cnt = reinterpret_cast<int *>(ws + m);
+        // accumulator and counters re-arm themselves; a fresh (or re-laid-out) workspace is armed once
+        if (ws_fresh) {
+            NNS_TRY(launch_keys_fill(mg.acc, m, NNS_KEY_NONE, st));
+            NNS_HIP(hipMemsetAsync(mg.cnt, 0, (size_t)p.ws_counters * sizeof(int), st));
         }
     }
 #ifdef NNS_K1A_STAMPS
@@ -642,15 +623,14 @@ static int launch_k1a(int m, int n, const float *q, const float *r, int64_t base
     mg.stamps = stamp ? stamps_dev : nullptr;
     if (stamp) NNS_HIP(hipMemsetAsync(stamps_dev, 0, nwg * 64 * sizeof(unsigned long long), st));
 #endif
-    if (use_f) {
+    const dim3 grid(p.qtiles, p.splits), block(64 * p.waves);
+    if (p.kernel == EXACT_K1F) {
         if constexpr (K <= 3)
-            hipLaunchKernelGGL((lowdim_filter_kernel<K>), dim3(p.qtiles, p.splits), dim3(512), 0, st, m, n, per_f, q, r, base, keys, mg);
-    } else if (p.nw <= 8)
-        hipLaunchKernelGGL((exact_lane_query_kernel<K, 8>), dim3(p.qtiles, p.splits), dim3(64 * p.nw), 0, st,
-                           m, n, p.per, q, r, base, keys, mg);
+            hipLaunchKernelGGL((lowdim_filter_kernel<K>), grid, block, 0, st, m, n, p.per, q, r, base, keys, mg);
+    } else if (p.waves <= 8)
+        hipLaunchKernelGGL((exact_lane_query_kernel<K, 8>), grid, block, 0, st, m, n, p.per, q, r, base, keys, mg);
     else
-        hipLaunchKernelGGL((exact_lane_query_kernel<K, K1A_MAXNW>), dim3(p.qtiles, p.splits), dim3(64 * p.nw), 0, st,
-                           m, n, p.per, q, r, base, keys, mg);
+        hipLaunchKernelGGL((exact_lane_query_kernel<K, K1A_MAXNW>), grid, block, 0, st, m, n, p.per, q, r, base, keys, mg);
     NNS_HIP(hipGetLastError());
 #ifdef NNS_K1A_STAMPS
     if (stamp) {
@@ -659,7 +639,7 @@ static int launch_k1a(int m, int n, const float *q, const float *r, int64_t base
         NNS_HIP(hipMemcpy(h.data(), stamps_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull;
         for (size_t w = 0; w < nwg; ++w) t0 = std::min(t0, h[w * 64]);
-        fprintf(stderr, "k1a stamps: %d qtiles x %d splits x %d waves, per %d (x10 ns since the first entry; min / median / max over workgroups)\n", p.qtiles, p.splits, p.nw, p.per);
+        fprintf(stderr, "k1a stamps: %d qtiles x %d splits x %d waves, per %d (x10 ns since the first entry; min / median / max over workgroups)\n", p.qtiles, p.splits, p.waves, p.per);
         for (int i = 0; i < 48; ++i) {
             std::vector<unsigned long long> v;
             for (size_t w = 0; w < nwg; ++w) if (h[w * 64 + i]) v.push_back(h[w * 64 + i] - t0);
@@ -1622,13 +1602,6 @@ __global__ __launch_bounds__(64 * NW) void exact_stream_rows_kernel(int n, int m
                            // latency and the merge's atomic round trips are per workgroup (1 x 1 M x 16, HIP events on
                            // one device: 2048 workgroups of 4 waves 33.8 us, 1024 24.9, 512 19.0; 256 of 8 waves 16.8)
 #endif
-static bool k1c_shape(int k, int m, const float *r)
-{
-    if (m < 1 || m > kStreamMaxQ) return false;
-    if (k == 1 || k == 2 || k == 3) return true;
-    return (k == 4 || k == 8 || k == 16 || k == 32) && (((uintptr_t)r & 15) == 0);
-}
-
 // workgroups of a K1c launch
 static int k1c_workgroups(int k, int n)
 {
@@ -1640,76 +1613,52 @@ static int k1c_workgroups(int k, int n)
     return (int)wgs;
 }
 
-template <int QT>
-static int launch_k1c_q(int k, int m, int n, const float *q, const float *r, int64_t base, nns_key *keys, const StreamMerge &mg,
-                        hipStream_t st)
-{
-    constexpr int U = NNS_K1C_U, NW = NNS_K1C_NW;
-    const dim3 grid((unsigned)k1c_workgroups(k, n)), block(64 * NW);
-    const float4 *r4 = reinterpret_cast<const float4 *>(r);
-    switch (k) {
-    case 1: hipLaunchKernelGGL((exact_stream_rows_kernel<1, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
-    case 2: hipLaunchKernelGGL((exact_stream_rows_kernel<2, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
-    case 3: hipLaunchKernelGGL((exact_stream_rows_kernel<3, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
-    case 4: hipLaunchKernelGGL((exact_stream_kernel<1, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
-    case 8: hipLaunchKernelGGL((exact_stream_kernel<2, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
-    case 16: hipLaunchKernelGGL((exact_stream_kernel<4, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
-    default: hipLaunchKernelGGL((exact_stream_kernel<8, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
-    }
-    NNS_HIP(hipGetLastError());
-    return NNS_OK;
-}
-
-static int launch_k1c(int k, int m, int n, const float *q, const float *r, int64_t base, nns_key *keys, nns_key *ws,
-                      bool ws_fresh, int *idx_out, float *dist_out, hipStream_t st)
+static int launch_k1c(const ExactPlan &p, int k, int m, int n, const float *q, const float *r, int64_t base, nns_key *keys,
+                      nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out, hipStream_t st)
 {
     StreamMerge mg;
     mg.acc = ws;
     mg.cnt = reinterpret_cast<int *>(ws + kStreamShards * kStreamMaxQ);
     mg.idx_out = idx_out;
     mg.dist_out = dist_out;
-    if (ws_fresh && k1c_workgroups(k, n) > 1) {   // accumulators and counters re-arm themselves; a fresh workspace is armed once
+    if (ws_fresh && p.ws_counters) {   // accumulators and counters re-arm themselves; a fresh workspace is armed once
         hipLaunchKernelGGL(stream_arm_kernel, dim3(1), dim3(64), 0, st, mg.acc, mg.cnt);
         NNS_HIP(hipGetLastError());
     }
-    if (m == 1) return launch_k1c_q<1>(k, m, n, q, r, base, keys, mg, st);
-    if (m == 2) return launch_k1c_q<2>(k, m, n, q, r, base, keys, mg, st);
-    return launch_k1c_q<4>(k, m, n, q, r, base, keys, mg, st);
-}
-
-template <typename T>
-static int launch_k1b(int k, int n, const T *q, const T *r, const int *qlist,
-                      const int *qcount, int mq, int qt, int groups, int64_t base,
-                      nns_key *keys, hipStream_t st)
-{
-    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
-    const bool tiled = (k % (16 / (int)sizeof(T)) == 0) && (((uintptr_t)r & 15) == 0);
-    int xblocks = divup(n, 256);
-    // about 8 workgroups per CU in total; refs are strided over gridDim.x
-    int target = divup(2048, groups);
-    if (target < 1) target = 1;
-    if (xblocks > target) xblocks = target;
-    const dim3 grid(xblocks, groups);
-    return with_qt<32, 8, 4, 1>(qt, [&](auto qtc) {
-        constexpr int QT = decltype(qtc)::value;
-        const size_t lds = (size_t)QT * k * sizeof(float);
-        if (tiled)
-            return launch_lds(exact_lane_ref_tiled_kernel<QT, T>, grid, dim3(256), lds + 4 * 64 * (8 * 16 + 16), st, k, n,
-                              q, r, qlist, qcount, mq, base, keys);
-        return launch_lds(vec ? exact_lane_ref_kernel<QT, 4, T> : exact_lane_ref_kernel<QT, 1, T>, grid, dim3(256), lds,
-                          st, k, n, q, r, qlist, qcount, mq, base, keys);
+    const dim3 grid(p.splits), block(64 * p.waves);
+    const float4 *r4 = reinterpret_cast<const float4 *>(r);
+    return with_qt<1, 2, 4>(p.qt, [&](auto qtc) {
+        constexpr int QT = decltype(qtc)::value, U = NNS_K1C_U, NW = NNS_K1C_NW;
+        switch (k) {
+        case 1: hipLaunchKernelGGL((exact_stream_rows_kernel<1, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
+        case 2: hipLaunchKernelGGL((exact_stream_rows_kernel<2, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
+        case 3: hipLaunchKernelGGL((exact_stream_rows_kernel<3, QT, U, NW>), grid, block, 0, st, n, m, q, r, base, keys, mg); break;
+        case 4: hipLaunchKernelGGL((exact_stream_kernel<1, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
+        case 8: hipLaunchKernelGGL((exact_stream_kernel<2, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
+        case 16: hipLaunchKernelGGL((exact_stream_kernel<4, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
+        default: hipLaunchKernelGGL((exact_stream_kernel<8, QT, U, NW>), grid, block, 0, st, n, m, q, r4, base, keys, mg); break;
+        }
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
     });
 }
 
-// query-tile width: as wide as the LDS tile (<= 64 KiB) and the registers allow
-static int pick_qt(int k, int nq)
+template <typename T>
+static int launch_k1b(const ExactPlan &p, int k, int n, const T *q, const T *r, const int *qlist, const int *qcount,
+                      int mq, int64_t base, nns_key *keys, hipStream_t st)
 {
-    int qt = 32;
-    while (qt > 1 && (size_t)qt * k * 4 > 64 * 1024) qt >>= 1;
-    while (qt > 1 && qt / 2 >= nq) qt >>= 1;
-    if (qt >= 32) return 32;
-    if (qt >= 8) return 8;
-    return qt >= 4 ? 4 : 1;
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    const bool tiled = (k % (16 / (int)sizeof(T)) == 0) && (((uintptr_t)r & 15) == 0);
+    const dim3 grid(p.ref_wgs, p.qtiles), block(64 * p.waves);
+    return with_qt<32, 8, 4, 1>(p.qt, [&](auto qtc) {
+        constexpr int QT = decltype(qtc)::value;
+        const size_t lds = (size_t)QT * k * sizeof(float);
+        if (tiled)
+            return launch_lds(exact_lane_ref_tiled_kernel<QT, T>, grid, block, lds + 4 * 64 * (8 * 16 + 16), st, k, n,
+                              q, r, qlist, qcount, mq, base, keys);
+        return launch_lds(vec ? exact_lane_ref_kernel<QT, 4, T> : exact_lane_ref_kernel<QT, 1, T>, grid, block, lds,
+                          st, k, n, q, r, qlist, qcount, mq, base, keys);
+    });
 }
 
 static int check_k(int k)
@@ -1721,151 +1670,77 @@ static int check_k(int k)
     return NNS_OK;
 }
 
+// K1b's grid for nq queries in at most max_groups query groups (grid.y strides over the rest): the query-tile width
+// as wide as the LDS tile (<= 64 KiB) and the registers allow, about 8 workgroups per CU in total, the refs strided
+// over grid.x
+static void k1b_plan(int k, int n, int nq, int max_groups, ExactPlan *p)
+{
+    int qt = 32;
+    while (qt > 1 && (size_t)qt * k * 4 > 64 * 1024) qt >>= 1;
+    while (qt > 1 && qt / 2 >= nq) qt >>= 1;
+    p->kernel = EXACT_K1B;
+    p->qt = qt >= 32 ? 32 : qt >= 8 ? 8 : qt >= 4 ? 4 : 1;
+    p->qtiles = divup(nq, p->qt);
+    if (p->qtiles > max_groups) p->qtiles = max_groups;
+    p->splits = 0;
+    p->per = n;
+    p->waves = 4;
+    const int target = divup(2048, p->qtiles);
+    p->ref_wgs = divup(n, 256);
+    if (p->ref_wgs > target) p->ref_wgs = target;
+}
+
 static bool k1a_dim(int k) { return k == 1 || k == 2 || k == 3 || k == 4 || k == 8 || k == 16; }
 
-size_t exact_workspace_keys(int k, int m, int n)
+int exact_plan(int k, int m, int n, bool bf16, bool refs_aligned, bool have_ws, ExactPlan *p)
 {
-    if (m <= kStreamMaxQ && (k <= 4 || k == 8 || k == 16 || k == 32)) return kStreamWsKeys;   // K1c (if the refs are aligned)
-    if (m < 64 || !k1a_dim(k)) return 0;
-    switch (k) {
-    case 1: return k1a_workspace_keys<1>(m, n);
-    case 2: return k1a_workspace_keys<2>(m, n);
-    case 3: return k1a_workspace_keys<3>(m, n);
-    case 4: return k1a_workspace_keys<4>(m, n);
-    case 8: return k1a_workspace_keys<8>(m, n);
-    default: return k1a_workspace_keys<16>(m, n);
-    }
-}
-
-// the geometry launch_exact_search would use (host only; nns_plan_exact): v[0] = kernel (0 K1a, 1 K1f, 2 K1b, 3 K1c),
-// v[1] = query tiles (grid.x), v[2] = ref ranges (grid.y), v[3] = refs per range, v[4] = waves per workgroup,
-// v[5] = queries per workgroup.  `aligned`: the refs are 16-byte aligned (K1c's condition); `have_ws`: the merge
-// workspace could be allocated.
-template <int K>
-static void exact_plan_k1a(int m, int n, bool have_ws, int *v)
-{
-    K1aPlan p = k1a_plan<K>(m, n);
-    v[0] = 0;
-    v[5] = 64 * K1A_QPL;
-    if (p.splits > 1 && !have_ws) {
-        p.splits = 1;
-        p.per = divup(n, K1aChunk<K>::value) * K1aChunk<K>::value;
-    }
-    if constexpr (K <= 3) {
-        if (k1f_wanted<K>(m, n, p)) {   // (the same re-cut as launch_k1a)
-            const int qtf = divup(m, 64 * K1F_QPL);
-            int want = divup(NNS_K1F_WAVES, qtf * 8);
-            const int maxs = divup(n, NNS_K1F_MIN_PER);
-            if (want > maxs) want = maxs;
-            if (want < 1) want = 1;
-            const int per = divup(divup(n, want), K1F_CH) * K1F_CH;
-            const int splits = divup(n, per);
-            if (splits <= 1 || (have_ws && p.splits > 1)) {
-                v[0] = 1;
-                v[5] = 64 * K1F_QPL;
-                p.qtiles = qtf;
-                p.splits = splits;
-                p.per = per;
-                p.nw = 8;
-            }
-        }
-    }
-    v[1] = p.qtiles;
-    v[2] = p.splits;
-    v[3] = p.per;
-    v[4] = p.nw;
-}
-
-int exact_plan(int k, int m, int n, bool aligned, bool have_ws, int *v)
-{
-    if (m >= 64 && k1a_dim(k)) {
-        switch (k) {
-        case 1: exact_plan_k1a<1>(m, n, have_ws, v); break;
-        case 2: exact_plan_k1a<2>(m, n, have_ws, v); break;
-        case 3: exact_plan_k1a<3>(m, n, have_ws, v); break;
-        case 4: exact_plan_k1a<4>(m, n, have_ws, v); break;
-        case 8: exact_plan_k1a<8>(m, n, have_ws, v); break;
-        default: exact_plan_k1a<16>(m, n, have_ws, v); break;
-        }
-        return NNS_OK;
-    }
-    if (m <= kStreamMaxQ && have_ws && (k <= 3 || (aligned && (k == 4 || k == 8 || k == 16 || k == 32)))) {
-        v[0] = 3;
-        v[1] = 1;
-        v[2] = k1c_workgroups(k, n);
-        v[3] = divup(n, v[2]);
-        v[4] = 8;
-        v[5] = m;
+    *p = ExactPlan{};
+    // K1a needs enough queries to fill lanes; its query lives in K registers
+    if (!bf16 && m >= 64 && k1a_dim(k))
+        return with_qt<1, 2, 3, 4, 8, 16>(k, [&](auto kc) {
+            k1a_k1f_plan<decltype(kc)::value>(m, n, have_ws, p);
+            return (int)NNS_OK;
+        });
+    // a handful of queries over short rows: the HBM-streaming form, one launch (needs its merge workspace)
+    if (!bf16 && m <= kStreamMaxQ && have_ws && (k <= 3 || (refs_aligned && (k == 4 || k == 8 || k == 16 || k == 32)))) {
+        p->kernel = EXACT_K1C;
+        p->qtiles = 1;
+        p->splits = k1c_workgroups(k, n);
+        p->per = divup(n, p->splits);
+        p->waves = NNS_K1C_NW;
+        p->qt = m;
+        p->ws_keys = kStreamWsKeys;
+        p->ws_counters = p->splits > 1 ? kStreamShards + 1 : 0;   // (one workgroup merges nothing)
         return NNS_OK;
     }
     NNS_TRY(check_k(k));
-    const int qt = pick_qt(k, m);
-    int groups = divup(m, qt);
-    if (groups > 4096) groups = 4096;
-    v[0] = 2;
-    v[1] = groups;
-    v[2] = 0;   // (K1b's grid over the refs is chosen at launch)
-    v[3] = n;
-    v[4] = 4;
-    v[5] = qt;
+    k1b_plan(k, n, m, 4096, p);
     return NNS_OK;
 }
 
-int launch_exact_search(int k, int m, int n, const float *q, const float *r,
-                        int64_t index_base, nns_key *keys, nns_key *ws, size_t ws_keys, bool ws_fresh,
-                        int *idx_out, float *dist_out, hipStream_t st)
+int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int bf16,
+                        int64_t index_base, nns_key *keys, nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out,
+                        hipStream_t st)
 {
-    // K1a needs enough queries to fill lanes; its query lives in K registers
-    if (m >= 64) {
-        switch (k) {
-        case 1: return launch_k1a<1>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        case 2: return launch_k1a<2>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        case 3: return launch_k1a<3>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        case 4: return launch_k1a<4>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        case 8: return launch_k1a<8>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        case 16: return launch_k1a<16>(m, n, q, r, index_base, keys, ws, ws_keys, ws_fresh, idx_out, dist_out, st);
-        default: break;
-        }
-    }
-    // a handful of queries over short rows: the HBM-streaming form, one launch (needs its merge workspace)
-    if (k1c_shape(k, m, r) && ws && ws_keys >= kStreamWsKeys)
-        return launch_k1c(k, m, n, q, r, index_base, keys, ws, ws_fresh, idx_out, dist_out, st);
-    NNS_TRY(check_k(k));
+    if (p.kernel == EXACT_K1A || p.kernel == EXACT_K1F)
+        return with_qt<1, 2, 3, 4, 8, 16>(k, [&](auto kc) {
+            return launch_k1a<decltype(kc)::value>(p, m, n, (const float *)q, (const float *)r, index_base, keys, ws,
+                                                   ws_fresh, idx_out, dist_out, st);
+        });
+    if (p.kernel == EXACT_K1C)
+        return launch_k1c(p, k, m, n, (const float *)q, (const float *)r, index_base, keys, ws, ws_fresh, idx_out,
+                          dist_out, st);
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    const int qt = pick_qt(k, m);
-    int groups = divup(m, qt);
-    if (groups > 4096) groups = 4096;   // grid.y strides over the rest
-    NNS_TRY(launch_k1b<float>(k, n, q, r, nullptr, nullptr, m, qt, groups, index_base, keys, st));
+    if (bf16)
+        NNS_TRY(launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, nullptr, nullptr, m, index_base, keys, st));
+    else
+        NNS_TRY(launch_k1b(p, k, n, (const float *)q, (const float *)r, nullptr, nullptr, m, index_base, keys, st));
     if (idx_out) NNS_TRY(launch_keys_unpack(keys, m, idx_out, dist_out, st));
     return NNS_OK;
 }
 
-int launch_exact_search_bf16(int k, int m, int n, const uint16_t *q, const uint16_t *r,
-                             int64_t index_base, nns_key *keys, hipStream_t st)
-{
-    NNS_TRY(check_k(k));
-    NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    const int qt = pick_qt(k, m);
-    int groups = divup(m, qt);
-    if (groups > 4096) groups = 4096;
-    return launch_k1b<uint16_t>(k, n, q, r, nullptr, nullptr, m, qt, groups, index_base, keys, st);
-}
-
-int launch_exact_listed_bf16(int k, int n, const uint16_t *q, const uint16_t *r, const int *qlist,
-                             const int *qcount, int max_listed, int64_t index_base, nns_key *keys,
-                             hipStream_t st)
-{
-    if (max_listed <= 0) return NNS_OK;
-    NNS_TRY(check_k(k));
-    const int qt = pick_qt(k, max_listed >= 32 ? 32 : max_listed);
-    int groups = divup(max_listed, qt);
-    if (groups > 8) groups = 8;
-    return launch_k1b<uint16_t>(k, n, q, r, qlist, qcount, 0, qt, groups, index_base, keys, st);
-}
-
-int launch_exact_listed(int k, int n, const float *q, const float *r, const int *qlist,
-                        const int *qcount, int max_listed, int64_t index_base,
-                        nns_key *keys, hipStream_t st)
+int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, const int *qlist, const int *qcount,
+                        int max_listed, int64_t index_base, nns_key *keys, hipStream_t st)
 {
     if (max_listed <= 0) return NNS_OK;
     NNS_TRY(check_k(k));
@@ -1873,10 +1748,10 @@ int launch_exact_listed(int k, int n, const float *q, const float *r, const int 
     // grid of 8 query-group rows strides over however many 32-query groups there
     // are, so a handful of ambiguous queries and a pathological all-ambiguous
     // batch both keep ~2048 workgroups busy.
-    const int qt = pick_qt(k, max_listed >= 32 ? 32 : max_listed);
-    int groups = divup(max_listed, qt);
-    if (groups > 8) groups = 8;
-    return launch_k1b<float>(k, n, q, r, qlist, qcount, 0, qt, groups, index_base, keys, st);
+    ExactPlan p{};
+    k1b_plan(k, n, max_listed, 8, &p);
+    if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);
+    return launch_k1b(p, k, n, (const float *)q, (const float *)r, qlist, qcount, 0, index_base, keys, st);
 }
 
 }  // namespace nns

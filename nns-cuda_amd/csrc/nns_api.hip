@@ -58,6 +58,11 @@ static bool small_exact(int k, int64_t m, int64_t n)
     if (k == 16) return m * n <= ((int64_t)1 << 25) || (n < 8192 && m * n <= ((int64_t)1 << 26));
     return false;
 }
+// the AUTO path takes the exact kernels: too few queries for the filter's tiles, or a small problem K1a does faster
+static bool auto_exact(unsigned flags, int k, int64_t m, int64_t n, int bf16)
+{
+    return (flags & NNS_PATH_MASK) == NNS_PATH_AUTO && (m < kTinyM || (!bf16 && small_exact(k, m, n)));
+}
 // deepest dimensionality the MFMA filter tiles (bf16 operands; fp32 operands: 256)
 static const int kMaxFilterK = 1024;
 
@@ -492,12 +497,11 @@ static int index_exact_pass(nns_index *ix, int m, hipStream_t st, F &&run)
 }
 }  // extern "C++"
 
-// idx_dev / dist_dev (optional): also leave the unpacked indices / distances (K1a writes them in its one
-// launch; every other path appends the unpack kernel)
+// idx_dev / dist_dev (optional): also leave the unpacked indices / distances (K1a, K1f and K1c write them in their
+// one launch; K1b and the filter path append the unpack kernel)
 static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, nns_key *keys_dev, void *stream,
                              int *idx_dev = nullptr, float *dist_dev = nullptr)
 {
-    bool unpacked = false;
     if (ix && ix->bf16 != bf16) {
         set_error("nns_index_search: query dtype does not match the index (%s index)", ix->bf16 ? "bf16" : "fp32");
         return NNS_ERR_INVALID;
@@ -516,43 +520,26 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
     ix->last_m = m;
     ix->last_stream = st;
 
-    // A handful of queries cannot fill MFMA tiles (they are padded to 256): the ref stream
-    // is then HBM-bound and the exact lane-per-ref kernel is the faster path (AUTO only).
-    const bool tiny = (ix->flags & NNS_PATH_MASK) == NNS_PATH_AUTO && (m < kTinyM || (!bf16 && small_exact(ix->k, m, ix->n)));
-    if (ix->path != NNS_PATH_MFMA || ix->refs_bad || tiny) {
-        if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
-        if (bf16)
-            NNS_TRY(launch_exact_search_bf16(ix->k, m, ix->n, (const uint16_t *)q_dev, (const uint16_t *)ix->r_dev,
-                                             ix->base, keys_dev, st));
-        else
-        {
-            const size_t need = exact_workspace_keys(ix->k, m, ix->n);
-            if (need > ix->exact_ws_keys) {
-                pool_free_after(ix->exact_ws, st);
-                ix->exact_ws = nullptr;
-                ix->exact_ws_keys = 0;
-                if (pool_alloc(&ix->exact_ws, need * sizeof(nns_key)) == hipSuccess) {
-                    ix->exact_ws_keys = need;
-                    ix->exact_ws_fresh = true;
-                } else {
-                    (void)hipGetLastError();   // no workspace: K1a runs one ref range per query tile
-                }
+    if (ix->path != NNS_PATH_MFMA || ix->refs_bad || auto_exact(ix->flags, ix->k, m, ix->n, bf16))
+        return index_exact_pass(ix, m, st, [&] {
+            const bool aligned = ((uintptr_t)ix->r_dev & 15) == 0;
+            ExactPlan p{};
+            NNS_TRY(exact_plan(ix->k, m, ix->n, bf16 != 0, aligned, true, &p));
+            const bool grows = p.ws_keys > ix->exact_ws_keys;
+            if (!grow_index_ws(&ix->exact_ws, &ix->exact_ws_keys, p.ws_keys, st)) {
+                (void)hipGetLastError();   // no workspace: K1a runs one ref range per query tile, K1c becomes K1b
+                NNS_TRY(exact_plan(ix->k, m, ix->n, bf16 != 0, aligned, false, &p));
+            } else if (grows) {
+                ix->exact_ws_fresh = true;
             }
             // (the workspace layout depends on m: a different m re-lays the counters out -> zero them again)
             if (m != ix->exact_ws_m) ix->exact_ws_fresh = true;
             ix->exact_ws_m = m;
-            NNS_TRY(launch_exact_search(ix->k, m, ix->n, (const float *)q_dev, (const float *)ix->r_dev, ix->base,
-                                        keys_dev, ix->exact_ws, ix->exact_ws_keys, ix->exact_ws_fresh, idx_dev, dist_dev, st));
+            NNS_TRY(launch_exact_search(p, ix->k, m, ix->n, q_dev, ix->r_dev, bf16, ix->base, keys_dev, ix->exact_ws,
+                                        ix->exact_ws_fresh, idx_dev, dist_dev, st));
             ix->exact_ws_fresh = false;
-            unpacked = idx_dev != nullptr;
-        }
-        if (idx_dev && !unpacked) NNS_TRY(launch_keys_unpack(keys_dev, m, idx_dev, dist_dev, st));
-        if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-        ix->last_path = NNS_PATH_EXACT;
-        ix->searched = true;
-        profile_advance(ix, NNS_PATH_EXACT);
-        return NNS_OK;
-    }
+            return (int)NNS_OK;
+        });
 
     NNS_TRY(ensure_query_ws(ix, m, st));
     const FilterGeom &g = ix->geom;
@@ -591,12 +578,8 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
     NNS_TRY(launch_finalize(g, ix->k, m, ix->n, q_dev, ix->r_dev, ix->lists, ix->counts, ix->qnorm,
                             ix->scal, ix->base, keys_dev, ix->amb_list, ix->multi_list, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_FINAL], st);
-    if (bf16)
-        NNS_TRY(launch_exact_listed_bf16(ix->k, ix->n, (const uint16_t *)q_dev, (const uint16_t *)ix->r_dev,
-                                         ix->amb_list, &ix->scal->amb_count, m, ix->base, keys_dev, st));
-    else
-        NNS_TRY(launch_exact_listed(ix->k, ix->n, (const float *)q_dev, (const float *)ix->r_dev, ix->amb_list,
-                                    &ix->scal->amb_count, m, ix->base, keys_dev, st));
+    NNS_TRY(launch_exact_listed(ix->k, ix->n, q_dev, ix->r_dev, bf16, ix->amb_list, &ix->scal->amb_count, m, ix->base,
+                                keys_dev, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_RERANK], st);
     if (idx_dev) NNS_TRY(launch_keys_unpack(keys_dev, m, idx_dev, dist_dev, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
@@ -1083,8 +1066,9 @@ int nns_plan_exact(int k, int m, int n, int refs_aligned, int have_workspace, in
 {
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if ((int64_t)m > kMaxPoints || (int64_t)n > kMaxPoints) return NNS_ERR_INVALID;
-    int v[6] = {0, 0, 0, 0, 0, 0};
-    NNS_TRY(exact_plan(k, m, n, refs_aligned != 0, have_workspace != 0, v));
+    ExactPlan p{};
+    NNS_TRY(exact_plan(k, m, n, false, refs_aligned != 0, have_workspace != 0, &p));
+    const int v[6] = {p.kernel, p.qtiles, p.splits, p.per, p.waves, p.qt};
     memcpy(out, v, sizeof(v));
     return NNS_OK;
 }
@@ -1255,7 +1239,7 @@ namespace nns {
 // for nns_multi.hip: one GPU's shard of nns_search_*_multi takes the same overlapped upload
 bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes)
 {
-    if ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && (m < kTinyM || (!bf16 && small_exact(k, m, n)))) flags |= NNS_PATH_EXACT;
+    if (auto_exact(flags, k, m, n, bf16)) flags |= NNS_PATH_EXACT;
     return chunked_pays(k, m, n, bf16, flags, rbytes);
 }
 int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
@@ -1367,7 +1351,7 @@ static int search_host_impl(int k, int m, int n, const void *s_points, const voi
     NNS_TRY(ensure_device_ok(device));
     if (num_shards < 1) num_shards = 1;
     if (num_shards > n) num_shards = n;   // the reference clamps GPUs to n (core.cu:771-772)
-    if ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && (m < kTinyM || (!bf16 && small_exact(k, m, n)))) flags |= NNS_PATH_EXACT;
+    if (auto_exact(flags, k, m, n, bf16)) flags |= NNS_PATH_EXACT;
     if (num_shards == 1) {
         const int src = search_host_small(k, m, n, s_points, r_points, bf16, idx_out, dist_out, flags, device);
         if (src != NNS_ERR_UNSUPPORTED) return src;

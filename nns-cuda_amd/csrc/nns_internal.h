@@ -416,27 +416,32 @@ int launch_keys_fill(nns_key *keys, int m, nns_key value, hipStream_t st);
 int launch_keys_min(nns_key *inout, const nns_key *other, int m, hipStream_t st);
 int launch_keys_unpack(const nns_key *keys, int m, int *idx, float *dist, hipStream_t st);
 int launch_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset, hipStream_t st);
-// exact search of all m queries (K1a lane=query when k is small, else K1b)
-// ws: workspace of ws_keys keys (exact_workspace_keys) for K1a's in-kernel second stage; ws_fresh: it was
-// (re)allocated since the last launch (its arrival counters are then zeroed once; they re-arm themselves).
-// idx_out / dist_out (optional): also write the unpacked indices / distances (K1a: same launch).
-size_t exact_workspace_keys(int k, int m, int n);
-// the exact path's launch geometry for a shape (host only: nns_plan_exact)
-int exact_plan(int k, int m, int n, bool aligned, bool have_ws, int *v6);
-int launch_exact_search(int k, int m, int n, const float *q, const float *r,
-                        int64_t index_base, nns_key *keys, nns_key *ws, size_t ws_keys, bool ws_fresh,
-                        int *idx_out, float *dist_out, hipStream_t st);
+// exact search of all m queries (K1: the nearest ref per query); the kernel codes are nns_plan_exact's
+enum { EXACT_K1A = 0, EXACT_K1F = 1, EXACT_K1B = 2, EXACT_K1C = 3 };
+struct ExactPlan {
+    int kernel;         // EXACT_K1A (lane = query), K1F (its filter + re-rank form), K1B (lane = ref), K1C (few queries)
+    int qtiles;         // query tiles (K1a / K1f: grid.x; K1b: query groups, grid.y; K1c: 1)
+    int splits;         // ref ranges (K1a / K1f: grid.y; K1c: its workgroups; K1b: 0, its refs are strided over ref_wgs)
+    int per;            // refs per range (the last may hold fewer)
+    int waves;          // waves per workgroup
+    int qt;             // queries per workgroup (K1b: the query-tile width QT)
+    int ref_wgs;        // K1b: workgroups over the refs (grid.x)
+    size_t ws_keys;     // merge workspace, in keys (0: none is used)
+    int ws_counters;    // arrival counters that a fresh workspace has zeroed before the launch (0: nothing to arm)
+};
+// the plan of a search; have_ws: the merge workspace can be had (K1a falls back to one ref range per query tile
+// without it, K1c to K1b); refs_aligned: the refs are 16-byte aligned (K1c's condition for k >= 4)
+int exact_plan(int k, int m, int n, bool bf16, bool refs_aligned, bool have_ws, ExactPlan *p);
+// ws: p.ws_keys keys for the in-kernel cross-workgroup merge; ws_fresh: it was (re)allocated or re-laid out since
+// the last launch (it is then armed once; it re-arms itself).  idx_out / dist_out (optional): also write the unpacked
+// indices / distances (K1a, K1f, K1c: same launch).
+int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int bf16,
+                        int64_t index_base, nns_key *keys, nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out,
+                        hipStream_t st);
 // exact scan of the queries listed in qlist[0 .. *qcount) (device memory); keys
 // of listed queries must hold NNS_KEY_NONE on entry (atomic-min merge).
-int launch_exact_listed(int k, int n, const float *q, const float *r,
-                        const int *qlist, const int *qcount, int max_listed,
-                        int64_t index_base, nns_key *keys, hipStream_t st);
-
-int launch_exact_search_bf16(int k, int m, int n, const uint16_t *q, const uint16_t *r,
-                             int64_t index_base, nns_key *keys, hipStream_t st);
-int launch_exact_listed_bf16(int k, int n, const uint16_t *q, const uint16_t *r, const int *qlist,
-                             const int *qcount, int max_listed, int64_t index_base, nns_key *keys,
-                             hipStream_t st);
+int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, const int *qlist, const int *qcount,
+                        int max_listed, int64_t index_base, nns_key *keys, hipStream_t st);
 
 // prep_kernels.hip (K2)
 int prep_workspace_bytes(int kt, size_t *bytes);
