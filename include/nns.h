@@ -103,6 +103,13 @@ enum {
                           * use) also on short streams, where AUTO records ref TILES (a lane's two best tiles, or one
                           * record per tile within its threshold) and lets K5 evaluate the tile's rows — same results
                           * either way; lets tests and A/B runs drive both forms at any size */
+    NNS_FILTER_F32 = 1024, /* MFMA filter, fp32 points: fp32 operands (v_mfma_f32_32x32x2_f32) instead of the default
+                          * split-bf16 operands (each centred value as hi = rn_bf16(v) plus lo = rn_bf16(v - hi), the
+                          * dot product as hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16, 3/16 of the fp32 MFMA
+                          * work, with tau widened by ~3 * 2^-15 |x'||y'|).  Same indices and distances either way;
+                          * for A/B runs and tests of the fp32-operand filter.  With bf16 points or with
+                          * NNS_FILTER_BF16: NNS_ERR_INVALID.  k > 256 has no fp32 tile: AUTO still takes the
+                          * bf16-operand filter there, NNS_PATH_MFMA returns NNS_ERR_UNSUPPORTED */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -334,15 +341,18 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,
  * v_mfma_f32_32x32x2_f32 (compared by the tests with a host fmaf() chain);
  * bf16 = 1: v_mfma_f32_32x32x16_bf16, bf16 = 2: four 16x16 tiles of v_mfma_f32_16x16x32_bf16
  * (the bf16 filter's shape and lane mapping), on the values cast to bf16 (compared with
- * fp64).  These are the error models behind the filter's proof margin tau. */
+ * fp64); bf16 = 3: the split chain of fp32 values (hi = rn_bf16(v), lo = rn_bf16(v - hi);
+ * hi.hi + hi.lo + lo.hi per 16-dim step on v_mfma_f32_32x32x16_bf16, the default filter
+ * form of fp32 points).  These are the error models behind the filter's proof margin tau. */
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0,
                       float *out);
 /* Diagnostic (host only, no device needed): the launch geometry the MFMA filter would use for a k-D search of
  * m queries over n refs.  out[0..11] = {tile depth kt, bf16 operands, fp32 points rounded to bf16 operands,
  * candidate lists per query, m_pad, n_pad, ring slots in total, ref-range splits (grid.y), slots per split,
  * query groups (grid.x), refs per ring slot, queries per workgroup}; with out_len >= 14 also {lanes of a query
- * share thresholds, records per ref tile} (the short-stream forms).  NNS_ERR_UNSUPPORTED beyond the deepest
- * tile.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split). */
+ * share thresholds, records per ref tile} (the short-stream forms); with out_len >= 15 also {fp32 points through
+ * split-bf16 operands} (the geometry fields are the same for both fp32-point forms).  NNS_ERR_UNSUPPORTED beyond
+ * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split). */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f
@@ -358,9 +368,14 @@ int nns_plan_exact(int k, int m, int n, int refs_aligned, int have_workspace, in
 int nns_selftest_lane_share(int tile16, const float *in64, float *out64);
 /* Diagnostic (host only): the constants of the proof margin tau(a) = c0 + c1 * max(a + x2, 0) the
  * filter and K5 use for a query of squared norm qnorm2 against refs of maximum squared norm ymax2 at
- * tile depth kt; mode 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands.
+ * tile depth kt; mode 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points
+ * as split-bf16 operands.
  * out3 = {c0, c1, x2}.  Lets the tests hold the measured MFMA error against the model. */
 int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3);
+/* The operand form of the index's MFMA filter, as its tau mode: 0 fp32 operands (NNS_FILTER_F32, or a depth without
+ * the split form), 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points as split-bf16 operands;
+ * -1 on the exact path.  Host only. */
+int nns_index_filter_form(nns_index *ix, int *form_out);
 
 /* ---- the exchange of the one-process-per-GPU form ----------------------------
  * What V8/V9's gather + host re-rank (core.cu:821-852, 1025-1056) becomes when every GPU

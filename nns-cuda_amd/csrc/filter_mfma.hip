@@ -230,6 +230,42 @@ using OpF32K64 = OpF32T<8, NNS_F_QB_F32>;    // KT = 64: 32 < k <= 64 without pa
 // a ring slot holds one 32-ref block (32 KiB), and the ring turns twice as often per MFMA
 using OpF32K256 = OpF32T<32, 1>;
 
+// Split-bf16 operands for fp32 points (the default for them; NNS_FILTER_F32 keeps OpF32T): every centred value v is
+// h = rn_bf16(v) plus l = rn_bf16(v - h) (v - h is exact in fp32), and x'.y' is taken as the three products
+// qh.rh + qh.rl + ql.rh on v_mfma_f32_32x32x16_bf16 (bf16 products are exact in fp32; the dropped terms are
+// ~3 * 2^-16 sum |x'_t y'_t|: tau mode 3, nns_internal.h).  The K3 geometry unchanged: the 32x32x16 C layout is the
+// 32x32x2 f32 one (a lane = one query column, 16 ref rows), and a 16-dim k-step is TWO 1 KiB fragments — hi, then
+// lo — of 32 points x 16 dims x 2 B, so a block at each depth has the bytes, fragment steps and resident query
+// registers of the fp32 block (KT = 8 * SPB).  Query fragment b of a block is qh (b even) / ql (b odd) of k-step
+// b / 2; the MFMAs of ref fragment b: hi (b even) x qh, ql; lo (b odd) x qh — 3 MFMAs x 32 cycles per k-step and
+// query block against 8 x 64 of OpF32T.
+template <int SPB, int QB_>
+struct OpSplitT {
+    static constexpr int kSPB = SPB;
+    static constexpr bool kTile16 = false;
+    static constexpr bool kSplit = true;
+    static constexpr bool kDmaBurst = false;  // (the bf16 operators' schedule: intervals ~5x shorter than OpF32T's)
+    static constexpr bool kLag = SPB >= 4;    // (the lag of half a block keeps hi / lo pairs together: SPB / 2 is even)
+    static constexpr bool kTauInRegs = true;
+    using Acc = AccSet;
+    static constexpr int kQB = QB_;
+    static constexpr int kNW = NNS_F_NW_F32;
+    static constexpr int kPrefetch = NNS_F_PF;   // fragments in flight ahead of the MFMAs (2 x 32 or 4 x 32 cycles each)
+    // The compiler builtin, as OpF32T / OpBF16T32T use, not OpBF16T's in-place asm: with the 32x32 tile's two
+    // 16-register accumulators hipcc keeps every accumulator in one tuple (no extra copies against OpF32T, no
+    // scratch: tests/test_split_filter_cpu.py), and its hazard recognizer places the wait states in front of the
+    // epilogue's reads, which asm MFMAs would leave to hand-placed fences.
+    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    }
+};
+using OpSplitK16 = OpSplitT<2, NNS_F_QB_F32>;
+using OpSplitK32 = OpSplitT<4, NNS_F_QB_F32>;
+using OpSplitK64 = OpSplitT<8, NNS_F_QB_F32>;
+using OpSplit = OpSplitT<16, NNS_F_QB_F32>;   // KT = 128: C3
+using OpSplitK256 = OpSplitT<32, 1>;
+
 // bf16, KT = 256, 16 fragment steps per 32-ref block either way; two MFMA shapes:
 //
 // OpBF16 (the product): v_mfma_f32_16x16x32_bf16.  Same flops per cycle as the 32x32x16 form,
@@ -391,6 +427,11 @@ using OpBF16Active = OpBF16T32;
 using OpBF16K512Active = OpBF16K512;
 #endif
 
+template <class OP, class = void>
+struct is_split_op : std::false_type {};
+template <class OP>
+struct is_split_op<OP, std::void_t<decltype(OP::kSplit)>> : std::bool_constant<OP::kSplit> {};
+
 // min over the lanes that carry the same query: l ^ 32 (32x32 tiles), and l ^ 16 too (16x16 tiles).  Row
 // swaps (v_permlane32_swap / v_permlane16_swap, gfx950), not ds_bpermute: no LDS round trip on the slow
 // path.  swap(t, t) returns {old t with its upper rows replaced by the partner's, and vice versa}: the min of
@@ -419,7 +460,8 @@ struct FilterArgs {
     CandEntry *lists;       // [splits][m_pad/32][kCandCap][64 lanes]
     int *counts;            // [splits][m_pad/32][64 lanes]
     int total_slots, slots_per_split, m_pad, kt;
-    int bf16;               // tau mode: 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands
+    int bf16;               // tau mode: 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands,
+                            // 3 fp32 points as split-bf16 operands (OpSplitT)
     int share_thr;          // short streams: a query's lanes adopt the smallest of their thresholds
     int tile_rec;           // short streams: ONE record per (lane, ref tile) — (tile minimum, first ref of the lane's
                             // rows) — instead of one per score within the threshold; K5 re-ranks the lane's rows
@@ -429,7 +471,7 @@ struct FilterArgs {
 };
 
 template <class OP>
-__global__ __launch_bounds__(OP::kNW * 64) void filter_kernel(const FilterArgs a)
+__device__ __forceinline__ void filter_main(const FilterArgs &a)
 {
     constexpr int F_NW = OP::kNW;
     constexpr int SPB = OP::kSPB;                      // fragment steps per image block
@@ -872,10 +914,23 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_kernel(const FilterArgs a
         if constexpr (T16) {
             // (16x16 tiles go through t16_step)
         } else {
-            static_for<QB>([&](auto qc) __attribute__((always_inline)) {
-                constexpr int qb = decltype(qc)::value;
-                acc.template at<qb>() = OP::mma(frag, bq[qb][b], acc.template at<qb>());
-            });
+            if constexpr (is_split_op<OP>::value) {
+                // ref hi fragment x (qh, ql) of the k-step; ref lo fragment x qh
+                static_for<QB>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int qb = decltype(qc)::value;
+                    if constexpr (b % 2 == 0) {
+                        acc.template at<qb>() = OP::mma(frag, bq[qb][b], acc.template at<qb>());
+                        acc.template at<qb>() = OP::mma(frag, bq[qb][b + 1], acc.template at<qb>());
+                    } else {
+                        acc.template at<qb>() = OP::mma(frag, bq[qb][b - 1], acc.template at<qb>());
+                    }
+                });
+            } else {
+                static_for<QB>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int qb = decltype(qc)::value;
+                    acc.template at<qb>() = OP::mma(frag, bq[qb][b], acc.template at<qb>());
+                });
+            }
         }
     };
 
@@ -1244,6 +1299,18 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_kernel(const FilterArgs a
 #endif
 }
 
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
+// the split-bf16 operators (OpSplitT) under a kernel name of their own
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_split_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
+
 // ---- self-test: one 32x32 tile through the same MFMA k-order as the filter --------
 // out[i][j] = accumulate over the image's k order of a[i][.] * b[j][.] seeded with c0[i];
 // a, b are [32][kt] fp32 (bf16 mode: values must be bf16-representable).  Lets the tests
@@ -1271,6 +1338,23 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
                 bv[e] = (__bf16)b[i * kt + 16 * s + 8 * h + e];
             }
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+        }
+    } else if (bf16 == 3) {
+        // the split chain of OpSplitT: v = h + l, h = rn_bf16(v), l = rn_bf16(v - h); per 16-dim k-step (same lane
+        // order as bf16 == 1) ah.bh, ah.bl (the ref hi fragment's two MFMAs), then al.bh (the lo fragment's)
+        for (int s = 0; s < kt / 16; ++s) {
+            bf16x8 ah, al, bh, bl;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float av = a[i * kt + 16 * s + 8 * h + e], bv = b[i * kt + 16 * s + 8 * h + e];
+                ah[e] = (__bf16)av;
+                al[e] = (__bf16)__fsub_rn(av, (float)ah[e]);
+                bh[e] = (__bf16)bv;
+                bl[e] = (__bf16)__fsub_rn(bv, (float)bh[e]);
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
         }
     } else {
         // bf16 == 2: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
@@ -1329,7 +1413,15 @@ constexpr int64_t kShareThrMaxTiles = 2048;
 #endif
 constexpr int64_t kTileRecMaxTiles = NNS_F_TILEREC_MAX;
 
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref)
+// Depths at which fp32 points take the split-bf16 operands (OpSplitT) unless NNS_FILTER_F32 is given: all five, each
+// won a same-device A/B at 65536 x 1048576 (filter 3.3x at KT 16, 3.4x at 32, 3.7x at 64 and 128, 3.5x at 256, keys
+// bit-equal: profiles/split_ab_depths.jsonl)
+constexpr bool split_depth(int kt)
+{
+    return kt == 16 || kt == 32 || kt == 64 || kt == 128 || kt == 256;
+}
+
+int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
     int kt = 0;
@@ -1354,6 +1446,8 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     }
     g->bf16 = bf16 ? 1 : 0;
     g->mixed = mixed ? 1 : 0;
+    // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
+    g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;
     g->kt = kt;
     g->lpq = (bf16 && kt <= 512 && kt != 384 && OpBF16Active::kTile16) ? 4 : 2;
     // queries per workgroup
@@ -1434,7 +1528,10 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
 template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
-    auto kern = filter_kernel<OP>;
+    auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
+        if constexpr (is_split_op<OP>::value) return filter_split_kernel<OP>;
+        else return filter_kernel<OP>;
+    }();
     // + 2 KiB per wave for the lanes' tau constants
     constexpr int lds_bytes = F_LDS_BYTES + OP::kNW * ((OP::kTile16 && OP::kQB > 2) ? 4096 : 2048);
     // > 64 KiB of dynamic LDS needs the opt-in, once per device
@@ -1466,7 +1563,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
     a.slots_per_split = g.slots_per_split;
     a.m_pad = g.m_pad;
     a.kt = g.kt;
-    a.bf16 = g.mixed ? 2 : g.bf16;
+    a.bf16 = g.mixed ? 2 : g.split ? 3 : g.bf16;
     a.share_thr = g.share_thr;   // (filter_plan)
     a.tile_rec = g.tile_rec;
 #ifdef NNS_DIAG
@@ -1485,6 +1582,11 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
                              : g.kt == 640  ? launch_filter_t<OpBF16K640>(g, a, st)
                              : g.kt == 384  ? launch_filter_t<OpBF16K384>(g, a, st)
                                            : launch_filter_t<OpBF16Active>(g, a, st))
+                          : g.split ? (g.kt == 16    ? launch_filter_t<OpSplitK16>(g, a, st)
+                                       : g.kt == 32  ? launch_filter_t<OpSplitK32>(g, a, st)
+                                       : g.kt == 64  ? launch_filter_t<OpSplitK64>(g, a, st)
+                                       : g.kt == 256 ? launch_filter_t<OpSplitK256>(g, a, st)
+                                                     : launch_filter_t<OpSplit>(g, a, st))
                           : (g.kt == 16    ? launch_filter_t<OpF32K16>(g, a, st)
                              : g.kt == 32  ? launch_filter_t<OpF32K32>(g, a, st)
                              : g.kt == 64  ? launch_filter_t<OpF32K64>(g, a, st)

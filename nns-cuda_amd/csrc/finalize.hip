@@ -19,6 +19,8 @@
 //                                       and checked against fp64 by the tests)
 //       e2 = 2.5u (X + Y)^2            the single rounding of x' = fl(x-c), y' = fl(y-c)
 //                                       (0 on the bf16 path: no centring)
+// (split-bf16 operands of fp32 points, tau mode 3: e3 also carries the dropped lo x lo / rounding terms and an
+//  absolute floor for subnormal operand parts and products — tau_consts, DESIGN.md "Exactness")
 // and V0's own fp32 value d0_j (core.cu:38-43: k+1 roundings per term) satisfies
 // |d0_j - D_j| <= g D_j.  Hence with
 //     tau(a) = 2 (e3 + e2) + 2g/(1-g) (max(a + X^2, 0) + e3 + e2)
@@ -317,7 +319,7 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
                     const CandEntry *lists, const int *counts, const float *qnorm, DevScalars *scal,
                     int64_t index_base, nns_key *keys, int *amb_list, int *multi_list, hipStream_t st)
 {
-    const int mode = g.mixed ? 2 : g.bf16;        // tau mode (nns_internal.h)
+    const int mode = g.mixed ? 2 : g.split ? 3 : g.bf16;   // tau mode (nns_internal.h)
     const bool data_bf16 = g.bf16 && !g.mixed;    // element type of q / r
     if (g.splits >= 4) {   // few queries, many lists per query: one wave per query
         if (data_bf16)

@@ -82,6 +82,8 @@ struct nns_index {
     bool profile = false;
     bool refs_bad = false;
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
+    bool split = false;            // fp32 points without NNS_FILTER_BF16 / NNS_FILTER_F32: split-bf16 operands where
+                                   // filter_plan enables them (geom.split)
 
     // MFMA path, ref side
     FilterGeom geom{};
@@ -179,6 +181,26 @@ int order_after_default_stream(hipStream_t st)
 }  // namespace nns
 }  // extern "C++"
 
+// The filter's operand form, the one rule for nns_index_create* and nns_plan_filter: *mixed = fp32 points through
+// bf16-rounded operands (NNS_FILTER_BF16; AUTO beyond the deepest fp32 tile, k > 256: the alternative is the VALU
+// scan), *split = fp32 points through split-bf16 operands (the default elsewhere; NNS_FILTER_F32 keeps fp32
+// operands; filter_plan applies it at the depths where it pays).  The two operand flags are for fp32 points and
+// exclude each other.
+static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
+{
+    if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32)) && bf16) {
+        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands) apply to fp32 points (bf16 points use the bf16 filter)");
+        return NNS_ERR_INVALID;
+    }
+    if ((flags & NNS_FILTER_BF16) && (flags & NNS_FILTER_F32)) {
+        set_error("NNS_FILTER_BF16 and the fp32-operand flag exclude each other");
+        return NNS_ERR_INVALID;
+    }
+    *mixed = !bf16 && ((flags & NNS_FILTER_BF16) || ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && k > 256 && k <= kMaxFilterK));
+    *split = !bf16 && !*mixed && !(flags & NNS_FILTER_F32);
+    return NNS_OK;
+}
+
 static int prep_refs(nns_index *ix, hipStream_t st)
 {
     const FilterGeom &g = ix->geom;
@@ -193,7 +215,7 @@ static int prep_refs(nns_index *ix, hipStream_t st)
                              &ix->scal->r_maxabs_bits, st));
     NNS_TRY(launch_prep_image(ix->k, g.kt, ix->n, g.n_pad, (const float *)ix->r_dev, ix->mean, -2.0f,
                               INFINITY, (float *)ix->rimg, ix->rnorm, &ix->scal->ymax2_bits, nullptr, st,
-                              ix->mixed));
+                              g.split ? 2 : ix->mixed ? 1 : 0));
     return NNS_OK;
 }
 
@@ -281,18 +303,13 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     ix->bf16 = bf16;
     ix->profile = (flags & NNS_PROFILE) != 0;
     ix->last_stream = st;
-    if (flags & NNS_FILTER_BF16) {
-        if (bf16) {
-            set_error("NNS_FILTER_BF16 applies to fp32 points (bf16 points already use the bf16 filter)");
+    {
+        const int frc = operand_form(k, bf16 != 0, flags, &ix->mixed, &ix->split);
+        if (frc != NNS_OK) {
             delete ix;   // nothing allocated or enqueued yet
-            return NNS_ERR_INVALID;
+            return frc;
         }
-        ix->mixed = true;
     }
-
-    // fp32 points beyond the deepest fp32 tile (256): AUTO takes the bf16-operand filter — the re-rank makes
-    // the result bits identical, and the alternative is the VALU scan
-    if ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && !bf16 && k > 256 && k <= kMaxFilterK) ix->mixed = true;
     const int kmax = (bf16 || ix->mixed) ? kMaxFilterK : 256;   // deepest tile of the MFMA filter
     int path = flags & NNS_PATH_MASK;
     // crossover: from k = 8 the MFMA filter (KT = 16 / 32 tile) beats 3k VALU ops per pair; bf16 tiles
@@ -336,7 +353,9 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             ix->ev_valid = true;
         }
         if (path == NNS_PATH_MFMA) {
-            if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0)) != NNS_OK) break;
+            if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split)) !=
+                NNS_OK)
+                break;
             const FilterGeom &g = ix->geom;
             size_t ws = 0;
             prep_workspace_bytes(g.kt, &ws);
@@ -419,7 +438,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st)
 {
     FilterGeom g = ix->geom;
     FilterGeom gq{};
-    NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0));
+    NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
     (void)g;
     if (gq.m_pad > ix->m_cap) {
@@ -554,7 +573,8 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
                                        nullptr, &ix->scal->q_maxabs_bits, st));
     else
         NNS_TRY(launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f,
-                                  (float *)ix->qimg, ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st, ix->mixed));
+                                  (float *)ix->qimg, ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st,
+                                  g.split ? 2 : ix->mixed ? 1 : 0));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_QPREP], st);
     NNS_TRY(launch_filter(g, ix->qimg, ix->rimg, ix->rnorm, ix->qnorm, ix->scal, ix->lists, ix->counts, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_FILTER], st);
@@ -879,9 +899,17 @@ int nns_index_near_ties(nns_index *ix, int *ids_out, int cap, int *count_out)
     return NNS_OK;
 }
 
+int nns_index_filter_form(nns_index *ix, int *form_out)
+{
+    if (!ix || !form_out) return NNS_ERR_INVALID;
+    const FilterGeom &g = ix->geom;
+    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // = the tau mode
+    return NNS_OK;
+}
+
 int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3)
 {
-    if (kt <= 0 || mode < 0 || mode > 2 || !out3) return NNS_ERR_INVALID;
+    if (kt <= 0 || mode < 0 || mode > 3 || !out3) return NNS_ERR_INVALID;
     const TauConsts t = tau_consts(kt, qnorm2, ymax2, mode);
     out3[0] = t.c0;
     out3[1] = t.c1;
@@ -909,7 +937,7 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset, v
 
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0, float *out)
 {
-    if (kt <= 0 || (kt & 15) || (bf16 == 2 && (kt & 31)) || bf16 < 0 || bf16 > 2 || !a || !b || !c0 || !out)
+    if (kt <= 0 || (kt & 15) || (bf16 == 2 && (kt & 31)) || bf16 < 0 || bf16 > 3 || !a || !b || !c0 || !out)
         return NNS_ERR_INVALID;
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(0));
@@ -1053,12 +1081,13 @@ static int whole_call_upload(HostCall &call, const char *where, int k, int m, in
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len)
 {
     if (!out || out_len < 12 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
-    const bool mixed = !bf16_points && ((flags & NNS_FILTER_BF16) || (k > 256 && (flags & NNS_PATH_MASK) == NNS_PATH_AUTO));
+    bool mixed = false, split = false;
+    NNS_TRY(operand_form(k, bf16_points != 0, flags, &mixed, &split));
     FilterGeom g{};
-    NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0));
-    const int v[14] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
-                       g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec};
-    memcpy(out, v, (out_len >= 14 ? 14 : 12) * sizeof(int));
+    NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split));
+    const int v[15] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
+                       g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split};
+    memcpy(out, v, (out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
     return NNS_OK;
 }
 
@@ -1160,7 +1189,8 @@ static int search_host_small(int k, int m, int n, const void *s_points, const vo
 // nns_keys_min: the answer is the unsharded one bit for bit.  No threads, no pinned memory.
 //
 // When it pays: four shards cost ~0.25 ms of launches, so the search must be worth >= 0.5 ms (estimated from the
-// measured rates: fp32 MFMA 140 TF, bf16-operand tiles 1.4 PF, exact VALU kernels 45 Tflop/s at 3k flop per pair).
+// measured rates: fp32 MFMA 140 TF, split-bf16 operands 600 T fp32-equivalent, bf16-operand tiles 1.4 PF, exact VALU
+// kernels 45 Tflop/s at 3k flop per pair).
 constexpr size_t kChunkMinBytes = (size_t)8 << 20;
 static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes)
 {
@@ -1175,7 +1205,9 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
         int kt = bf16 ? 128 : 16;
         while (kt < k) kt *= 2;
         const bool bf16_ops = bf16 || k > 256 || (flags & NNS_FILTER_BF16);
-        est_s = 2.0 * kt * (double)m * (double)n / (bf16_ops ? 1.4e15 : 140e12);
+        // fp32 points: split-bf16 operands unless NNS_FILTER_F32 (3 bf16 MFMAs per 16 dims: ~5x the fp32 operands' rate)
+        const bool split_ops = !bf16_ops && !(flags & NNS_FILTER_F32);
+        est_s = 2.0 * kt * (double)m * (double)n / (bf16_ops ? 1.4e15 : split_ops ? 600e12 : 140e12);
     }
     return est_s >= 0.5e-3;
 }

@@ -272,6 +272,7 @@ struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
+    int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
     int kt;               // K of the tile (k padded up with zeros)
     int m_pad;            // queries padded to the workgroup's query count
     int n_pad;            // refs padded to a whole ring slot
@@ -308,7 +309,8 @@ struct TauConsts {
     float c0, c1, x2;
 };
 
-// mode: 0 fp32 operands, 1 bf16 points (operands exact), 2 fp32 points ROUNDED to bf16 operands
+// mode: 0 fp32 operands, 1 bf16 points (operands exact), 2 fp32 points ROUNDED to bf16 operands, 3 fp32 points as
+// SPLIT bf16 operands (hi + lo, three products: OpSplitT)
 __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax2, int mode)
 {
     const bool bf16 = mode != 0;
@@ -318,7 +320,22 @@ __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax
     const double X = sqrt(X2), Y = sqrt(Y2);
     const double gk = (kt + 2) * u / (1.0 - (kt + 2) * u);   // V0's own rounding (k+1 per term)
     double e3, e2;
-    if (!bf16) {
+    if (mode == 3) {
+        // Split operands (derivation: DESIGN.md, "Exactness"), a = u_b = 2^-8: v = h + l + d with h = rn_bf16(v),
+        // l = rn_bf16(v - h), |h| <= (1 + a)|v|, |l| <= a (1 + a)|v|, |d| <= a^2 |v|.  qh.rh + qh.rl + ql.rh drops
+        // qh.d_r + ql.rl + ql.d_r + d_q.v, at most a^2 (3 + 4a + 2a^2) |x'_t v_t| <= 3 * 2^-16 (1 + 2^-6) |x'_t v_t|,
+        // summed <= 3 * 2^-15 (1 + 2^-6) X Y (v = -2 y').  Products exact in fp32; the seeded accumulation of
+        // 3 kt / 16 MFMAs = 3 kt products under the 32x32x16 model above (2u per add) on
+        // sum |products| <= (1 + a)^2 (1 + 2a) sum |x'_t v_t| <= (1 + 2^-5) 2 X Y.  Absolute floor: an operand part below 2^-126 (subnormal: flushed or
+        // not by the MFMA) is off by < 2^-126 — 2^-124 (|x'_t| + |v_t|) per element covers all three products, summed
+        // <= 2^-124 sqrt(kt) (X + 2 Y) — and a product or an add with a result below 2^-126 loses < 2^-126 each.
+        const double na = 3.0 * kt + 3.0 * (kt / 16) + 2.0;
+        const double gs = 2.0 * na * u / (1.0 - 2.0 * na * u);
+        const double et = 3.0 * 0x1p-15 * (1.0 + 0x1p-6) * X * Y;
+        const double ef = 0x1p-124 * sqrt((double)kt) * (X + 2.0 * Y) + (7.0 * kt + 4.0) * 0x1p-126;
+        e3 = gs * (Y2 + (1.0 + 0x1p-5) * 2.0 * X * Y) + 2.0 * u * Y2 + et + ef;
+        e2 = 2.5 * u * (X + Y) * (X + Y);   // x' = fl(x - c), y' = fl(y - c), as on the fp32 path
+    } else if (!bf16) {
         // fp32 MFMA = k-ordered fmaf chain of kt steps seeded with the rounded norm
         e3 = gk * (Y2 + 2.0 * X * Y) + 2.0 * u * Y2;
         e2 = 2.5 * u * (X + Y) * (X + Y);   // x' = fl(x - c), y' = fl(y - c)
@@ -450,7 +467,7 @@ int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws,
 int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts,
                       const float *mean, float scale, float pad_norm,
                       float *img, float *norms, unsigned *max_norm_bits,
-                      unsigned *maxabs_bits, hipStream_t st, bool out_bf16 = false);
+                      unsigned *maxabs_bits, hipStream_t st, int form = 0);
 
 // bf16 points (raw uint16 bits) -> bf16 tile image [blk][16][64 lanes][8 bf16], value * scale
 // (scale = 1 or -2, exact), fp32 norms of the UNcentred points, max-|v| word
@@ -463,7 +480,8 @@ int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, con
                            unsigned *maxabs_bits, hipStream_t st);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false);
+int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
+                bool split = false);
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
                   hipStream_t st);

@@ -146,6 +146,10 @@ int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws, f
 // BF = 1 (NNS_FILTER_BF16, fp32 points through the bf16 filter): the same centring and fp32 norms, but
 // the image holds the centred, scaled values ROUNDED to bf16 (RNE) in the 16x16x32 operand order of
 // image_bf16_kernel (order 1).  KT = 256 only.
+// BF = 2 (split-bf16 operands, the filter's OpSplitT): the same centring and fp32 norms; every centred, scaled
+// value v becomes h = rn_bf16(v) and l = rn_bf16(v - h) (v - h is exact in fp32), written as two 1 KiB
+// fragments per 16-dim k-step in the v_mfma_f32_32x32x16_bf16 operand order (lane = 32 hl + i, dims
+// 16 s + 8 hl .. + 7): fragment 2 s = hi, 2 s + 1 = lo.  The block keeps the fp32 image's bytes (KT / 8 fragments).
 template <int KT, int BF = 0>
 __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float *__restrict__ pts,
                                                     const float *__restrict__ mean, float scale,
@@ -233,7 +237,27 @@ __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float
         }
     }
 
-    if constexpr (BF != 0) {
+    if constexpr (BF == 2) {
+        uint4 *outb = reinterpret_cast<uint4 *>(img + (size_t)blk * 32 * KT);
+        for (int f = tid; f < (KT / 8) * 64; f += 256) {
+            const int s2 = f >> 6, lane = f & 63;
+            const int i = lane & 31, d0 = 16 * (s2 >> 1) + 8 * (lane >> 5);
+            const bool lo_part = (s2 & 1) != 0;
+            unsigned w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                unsigned short p[2];
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const float v = tile[i * LD + d0 + 2 * e + c] * scale;   // scale +1 / -2: exact
+                    const __bf16 hv = (__bf16)v;                              // RNE; NaN stays NaN
+                    p[c] = __builtin_bit_cast(unsigned short, lo_part ? (__bf16)__fsub_rn(v, (float)hv) : hv);
+                }
+                w[e] = (unsigned)p[0] | ((unsigned)p[1] << 16);
+            }
+            outb[f] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    } else if constexpr (BF != 0) {
         static_assert(BF == 0 || KT == 256 || KT == 128, "the bf16 operand image is 128 or 256 deep");
         // fragment f = NKS * tile + k-step; lane l: point 16 tile + (l & 15), dims 32 ks + 8 (l >> 4) .. + 7
         constexpr int NKS = KT / 32;
@@ -435,10 +459,39 @@ __global__ __launch_bounds__(256) void image_deep_kernel(int k, int npts, const 
 
 int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, const float *mean,
                       float scale, float pad_norm, float *img, float *norms,
-                      unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, bool out_bf16)
+                      unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form)
 {
     const int blocks = npts_pad / 32;
-    if (out_bf16) {
+    if (form == 2) {   // split-bf16 operands at the fp32 depths
+        switch (kt) {
+        case 16:
+            hipLaunchKernelGGL((image_kernel<16, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                               norms, max_norm_bits, maxabs_bits);
+            break;
+        case 32:
+            hipLaunchKernelGGL((image_kernel<32, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                               norms, max_norm_bits, maxabs_bits);
+            break;
+        case 64:
+            hipLaunchKernelGGL((image_kernel<64, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                               norms, max_norm_bits, maxabs_bits);
+            break;
+        case 128:
+            hipLaunchKernelGGL((image_kernel<128, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                               norms, max_norm_bits, maxabs_bits);
+            break;
+        case 256:
+            hipLaunchKernelGGL((image_kernel<256, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                               norms, max_norm_bits, maxabs_bits);
+            break;
+        default:
+            set_error("prep: unsupported split-operand tile K %d", kt);
+            return NNS_ERR_UNSUPPORTED;
+        }
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
+    }
+    if (form == 1) {
         if (kt != 1024 && kt != 768 && kt != 640 && kt != 512 && kt != 384 && kt != 256 && kt != 128) {
             set_error("prep: the bf16 operand image is 128, 256, 384, 512, 640, 768 or 1024 deep (kt = %d)", kt);
             return NNS_ERR_UNSUPPORTED;

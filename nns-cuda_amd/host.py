@@ -32,6 +32,7 @@ NNS_MULTI_FORCE_COLLECTIVE = 256
 NNS_KEY_NONE = 0x7F80000000000000
 
 NNS_RECORDS_PER_REF = 512
+NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -46,7 +47,7 @@ ABI_SYMBOLS = (
     "nns_trim", "nns_warmup", "nns_shutdown", "nns_search_bf16_multi",
     "nns_index_near_ties", "nns_tau_consts", "nns_index_search_indices", "nns_selftest_lane_share", "nns_plan_filter", "nns_plan_exact",
     "nns_comm_unique_id", "nns_comm_create", "nns_comm_size", "nns_comm_allreduce_min", "nns_comm_destroy",
-    "nns_multi_last_exchange_ranks",
+    "nns_multi_last_exchange_ranks", "nns_index_filter_form",
     "nns_index_search_topk", "nns_keys_topk_merge", "nns_keys_topk_unpack", "nns_search_f32_topk",
     "nns_search_bf16_topk", "nns_plan_topk",
     "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
@@ -115,6 +116,7 @@ def _load() -> ctypes.CDLL:
     lib.nns_tau_consts.argtypes = [c_int, ctypes.c_float, ctypes.c_float, c_int, c_vp]
     lib.nns_selftest_lane_share.argtypes = [c_int, c_vp, c_vp]
     lib.nns_plan_filter.argtypes = [c_int, c_int, c_int, c_int, c_u, c_vp, c_int]
+    lib.nns_index_filter_form.argtypes = [c_vp, ctypes.POINTER(c_int)]
     lib.nns_plan_exact.argtypes = [c_int, c_int, c_int, c_int, c_int, c_vp, c_int]
     lib.nns_keys_min.argtypes = [c_vp, c_vp, c_int, c_vp]
     lib.nns_keys_unpack.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
@@ -159,8 +161,9 @@ def _check(status: int, where: str) -> None:
         raise NNSError(status, where, detail)
 
 
-def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: bool = False) -> np.ndarray:
-    """out[i][j] of one 32x32 MFMA tile (diagnostic, see include/nns.h)."""
+def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: int = 0) -> np.ndarray:
+    """out[i][j] of one 32x32 MFMA tile (diagnostic, see include/nns.h).  bf16: 0 fp32, 1 bf16 32x32x16, 2 bf16
+    16x16x32, 3 the split chain of fp32 values."""
     a = np.ascontiguousarray(a, np.float32)
     b = np.ascontiguousarray(b, np.float32)
     c0 = np.ascontiguousarray(c0, np.float32)
@@ -172,11 +175,12 @@ def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: bool = Fal
 
 
 def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0) -> dict:
-    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only)."""
-    out = np.zeros(14, np.int32)
-    _check(lib.nns_plan_filter(k, m, n, int(bf16), flags, out.ctypes.data, 14), "nns_plan_filter")
+    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  "split": 1 when fp32 points
+    take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0)."""
+    out = np.zeros(15, np.int32)
+    _check(lib.nns_plan_filter(k, m, n, int(bf16), flags, out.ctypes.data, 15), "nns_plan_filter")
     names = ("kt", "bf16", "mixed", "lpq", "m_pad", "n_pad", "total_slots", "splits", "slots_per_split", "qgroups",
-             "slot_pts", "queries_per_wg", "share_thr", "tile_rec")
+             "slot_pts", "queries_per_wg", "share_thr", "tile_rec", "split")
     return dict(zip(names, (int(v) for v in out)))
 
 
@@ -432,8 +436,9 @@ class Index:
     """One prepared, device-resident shard of reference points (nns_index)."""
 
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
-                 soa: bool = False, filter_bf16: bool = False):
-        """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device."""
+                 soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False):
+        """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
+        filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones."""
         import torch
         if refs.dtype not in (torch.float32, torch.bfloat16) or refs.dim() != 2 or not refs.is_contiguous() \
                 or not refs.is_cuda:
@@ -443,7 +448,7 @@ class Index:
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
-            | (NNS_FILTER_BF16 if filter_bf16 else 0)
+            | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0)
         h = ctypes.c_void_p()
         create = lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
@@ -558,7 +563,13 @@ class Index:
     def stats(self) -> dict:
         st = nns_stats()
         _check(lib.nns_index_stats(self._h, ctypes.byref(st)), "nns_index_stats")
-        return st.asdict()
+        d = st.asdict()
+        # the filter's operand form the index uses: "split" (split-bf16, fp32 points by default), "fp32"
+        # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16); None: exact path
+        form = ctypes.c_int(-1)
+        _check(lib.nns_index_filter_form(self._h, ctypes.byref(form)), "nns_index_filter_form")
+        d["filter_form"] = {-1: None, 0: "fp32", 1: "bf16", 2: "bf16", 3: "split"}[form.value]
+        return d
 
     def near_ties(self) -> np.ndarray:
         """Query numbers of the last search that K5 decided among > 1 candidates within tau."""

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Split-bf16 vs fp32 filter operands (fp32 points), same device, same data.
+
+usage: probe_split.py ab [k ...]      per-depth A/B at 65536 x 1048576 (default k = 16 32 64 128 256): the two forms
+                                      alternate, 3 runs of 5 timed searches each; filter_ms (HIP events, NNS_PROFILE) and
+                                      wall ms per search, keys of the two forms compared bit for bit
+       probe_split.py c3 split|f32 N  N C3 searches (65536 x 1048576 x 128) of one form (rocprofv3 / PMC runs)
+       probe_split.py cluster         tight Gaussian clusters at 65536 x 1048576 x 128: exact-scan (ambiguous) and
+                                      multi-candidate queries of each operand form
+       probe_split.py denorm          does v_mfma_f32_32x32x16_bf16 flush bf16 denormal operands? (MFMA self-test)
+One JSON object per line on stdout."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import __graft_entry__ as graft  # noqa: E402
+
+pkg = graft.load_package()
+M, N = 65536, 1048576
+
+
+def uniform(m, n, k, seed=1000):
+    q = torch.empty((m, k), dtype=torch.float32, device="cuda")
+    r = torch.empty((n, k), dtype=torch.float32, device="cuda")
+    pkg.fill_uniform(q, seed, 0)
+    pkg.fill_uniform(r, seed, m * k)
+    return q, r
+
+
+def timed(ix, q, keys, steps):
+    ix.stats()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ix.search_keys(q, keys)
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / steps * 1e3
+    st = ix.stats()
+    return wall, st["filter_ms"], st
+
+
+def ab(ks):
+    for k in ks:
+        q, r = uniform(M, N, k)
+        ixs = {f: pkg.Index(r, path="mfma", profile=True, filter_f32=(f == "f32")) for f in ("split", "f32")}
+        keys = {f: torch.empty(M, dtype=torch.int64, device="cuda") for f in ixs}
+        for f, ix in ixs.items():
+            ix.search_keys(q, keys[f])
+        res = {f: {"wall_ms": [], "filter_ms": []} for f in ixs}
+        for _ in range(3):
+            for f, ix in ixs.items():
+                w, fm, st = timed(ix, q, keys[f], 5)
+                res[f]["wall_ms"].append(round(w, 3))
+                res[f]["filter_ms"].append(round(fm, 3))
+                res[f]["ambiguous"] = st["ambiguous"]
+                res[f]["form"] = st["filter_form"]
+        same = bool(torch.equal(keys["split"], keys["f32"]))
+        fs, ff = np.median(res["split"]["filter_ms"]), np.median(res["f32"]["filter_ms"])
+        print(json.dumps({"probe": "ab", "m": M, "n": N, "k": k, "kt": ixs["split"].stats()["k_tile"], **res,
+                          "filter_speedup_median": round(float(ff / fs), 3), "keys_equal": same}), flush=True)
+        for ix in ixs.values():
+            ix.close()
+        del q, r
+        torch.cuda.empty_cache()
+
+
+def c3(form, steps):
+    q, r = uniform(M, N, 128)
+    ix = pkg.Index(r, path="mfma", filter_f32=(form == "f32"))
+    keys = torch.empty(M, dtype=torch.int64, device="cuda")
+    ix.search_keys(q, keys)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ix.search_keys(q, keys)
+    torch.cuda.synchronize()
+    print(json.dumps({"probe": "c3", "form": form, "steps": steps,
+                      "wall_ms": round((time.perf_counter() - t0) / steps * 1e3, 3)}), flush=True)
+    ix.close()
+
+
+def clustered(m, n, k, clusters, sigma, seed=5):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    centres = torch.rand((clusters, k), generator=g, device="cuda")
+    rc = torch.randint(0, clusters, (n,), generator=g, device="cuda")
+    qc = torch.randint(0, clusters, (m,), generator=g, device="cuda")
+    r = (centres[rc] + sigma * torch.randn((n, k), generator=g, device="cuda")).contiguous()
+    q = (centres[qc] + sigma * torch.randn((m, k), generator=g, device="cuda")).contiguous()
+    return q, r
+
+
+def cluster():
+    for sigma in (0.03, 0.01, 0.003):
+        q, r = clustered(M, N, 128, 1024, sigma)
+        out = {}
+        keys0 = None
+        for f, kw in (("split", {}), ("f32", {"filter_f32": True}), ("bf16", {"filter_bf16": True})):
+            ix = pkg.Index(r, path="mfma", **kw)
+            keys = ix.search_keys(q)
+            torch.cuda.synchronize()
+            st = ix.stats()
+            out[f] = {"ambiguous": st["ambiguous"], "multi_candidate": st["multi_candidate"]}
+            if keys0 is None:
+                keys0 = keys.clone()
+            else:
+                out[f]["keys_equal_split"] = bool(torch.equal(keys, keys0))
+            ix.close()
+        print(json.dumps({"probe": "cluster", "m": M, "n": N, "k": 128, "clusters": 1024, "sigma": sigma, **out}),
+              flush=True)
+        del q, r
+        torch.cuda.empty_cache()
+
+
+def denorm():
+    kt = 16
+    a = np.zeros((32, kt), np.float32)
+    b = np.zeros((32, kt), np.float32)
+    a[:, 0] = np.float32(2.0 ** -130)          # a bf16 denormal (exact in bf16: 2^-133 spacing)
+    b[:, 0] = np.float32(2.0 ** 100)           # product 2^-30: far above FLT_MIN
+    a[:, 1] = np.float32(2.0 ** -100)          # normal x normal with a product below FLT_MIN (2^-140)
+    b[:, 1] = np.float32(2.0 ** -40)
+    out = pkg.selftest_mfma(a, b, np.zeros(32, np.float32), bf16=1)
+    a2 = np.zeros((32, kt), np.float32)
+    a2[:, 1] = a[:, 1]
+    b2 = np.zeros((32, kt), np.float32)
+    b2[:, 1] = b[:, 1]
+    out2 = pkg.selftest_mfma(a2, b2, np.zeros(32, np.float32), bf16=1)
+    print(json.dumps({"probe": "denorm", "denormal_operand_product": float(out[0, 0]), "expected_if_kept": 2.0 ** -30,
+                      "flushes_denormal_operands": bool(abs(float(out[0, 0])) < 2.0 ** -100),
+                      "subnormal_product_alone": float(out2[0, 0]), "expected_subnormal": 2.0 ** -140,
+                      "flushes_subnormal_products": bool(out2[0, 0] == 0)}), flush=True)
+
+
+if __name__ == "__main__":
+    what = sys.argv[1]
+    if what == "ab":
+        ab([int(x) for x in sys.argv[2:]] or [16, 32, 64, 128, 256])
+    elif what == "c3":
+        c3(sys.argv[2], int(sys.argv[3]))
+    elif what == "cluster":
+        cluster()
+    elif what == "denorm":
+        denorm()
+    else:
+        raise SystemExit(__doc__)
