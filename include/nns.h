@@ -110,6 +110,12 @@ enum {
                           * for A/B runs and tests of the fp32-operand filter.  With bf16 points or with
                           * NNS_FILTER_BF16: NNS_ERR_INVALID.  k > 256 has no fp32 tile: AUTO still takes the
                           * bf16-operand filter there, NNS_PATH_MFMA returns NNS_ERR_UNSUPPORTED */
+    NNS_FILTER_SPLIT_EAGER = 2048, /* MFMA filter, fp32 points on split-bf16 operands: the EAGER schedule (all three
+                          * products of every tile) and image layout at every depth, instead of the lazy schedule the
+                          * library takes where it measured faster (KT = 128 on long streams: the two cross products only on
+                          * tiles whose hi-hi minimum is within B of the lane's threshold).  Same candidate lists' meaning,
+                          * same indices and distances; for A/B runs, tests, and data so tightly clustered that most tiles
+                          * refine.  NNS_ERR_INVALID with bf16 points, NNS_FILTER_BF16 or NNS_FILTER_F32 */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -346,13 +352,18 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,
  * form of fp32 points).  These are the error models behind the filter's proof margin tau. */
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0,
                       float *out);
+/* The same tile in the order of the lazy split filter: the kt / 16 hi.hi MFMAs first — out_hh (optional) = the
+ * accumulator at that point — then hi.lo and lo.hi of every 16-dim step on the same accumulator: out. */
+int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *c0, float *out, float *out_hh);
 /* Diagnostic (host only, no device needed): the launch geometry the MFMA filter would use for a k-D search of
  * m queries over n refs.  out[0..11] = {tile depth kt, bf16 operands, fp32 points rounded to bf16 operands,
  * candidate lists per query, m_pad, n_pad, ring slots in total, ref-range splits (grid.y), slots per split,
  * query groups (grid.x), refs per ring slot, queries per workgroup}; with out_len >= 14 also {lanes of a query
  * share thresholds, records per ref tile} (the short-stream forms); with out_len >= 15 also {fp32 points through
- * split-bf16 operands} (the geometry fields are the same for both fp32-point forms).  NNS_ERR_UNSUPPORTED beyond
- * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split). */
+ * split-bf16 operands} (the geometry fields are the same for both fp32-point forms); with out_len >= 16 also {the split
+ * operands run the lazy schedule} (0 with NNS_FILTER_SPLIT_EAGER, at depths without the lazy kernel and on the
+ * short-stream record forms; the other fields do not depend on it).  NNS_ERR_UNSUPPORTED beyond
+ * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 / NNS_FILTER_SPLIT_EAGER with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split). */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f
@@ -372,6 +383,10 @@ int nns_selftest_lane_share(int tile16, const float *in64, float *out64);
  * as split-bf16 operands.
  * out3 = {c0, c1, x2}.  Lets the tests hold the measured MFMA error against the model. */
 int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3);
+/* Diagnostic (host only): B of the lazy split filter — the bound on how far a pair's three-product score can lie below
+ * its hi.hi partial score (cross products + their accumulation + the rounding of thr + B), for a query of squared norm
+ * qnorm2 against refs of maximum squared norm ymax2 at tile depth kt.  out1 = B. */
+int nns_split_lazy_bound(int kt, float qnorm2, float ymax2, float *out1);
 /* The operand form of the index's MFMA filter, as its tau mode: 0 fp32 operands (NNS_FILTER_F32, or a depth without
  * the split form), 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points as split-bf16 operands;
  * -1 on the exact path.  Host only. */

@@ -427,6 +427,51 @@ using OpBF16Active = OpBF16T32;
 using OpBF16K512Active = OpBF16K512;
 #endif
 
+// Lazy split ("lazy split"): the split operands in a schedule that runs the two cross products only where the result
+// needs them.  The kernel uses a score to ask "is the minimum of this 32 x 32 tile within the lane's threshold?"; the
+// cross products qh.rl + ql.rh move a score by at most B (split_lazy_bound, nns_internal.h: ~2^-6 |x'||y'|), so a tile
+// whose hi-hi scores all lie above thr + B is retired after ONE product per k-step.  A flagged tile (wave-uniform, the
+// slow path of the eager form plus a few per cent of the tiles early in a stream) continues the SAME accumulator with
+// the 2 * KT / 16 cross MFMAs — rh re-read from the ring slot, rl loaded straight from the lo region of K2's lazy image
+// — and then runs record_all on the three-product scores as the eager kernel does.  Only the hi fragments stream
+// through LDS: a 64-ref slot is kSlotSteps = 16 fragment steps (16 KiB), and the LDS the lo halves no longer take makes
+// the ring eight slots deep (an interval is a third of the eager one, the DMA latency is not).
+// kSPB = HI fragments per block (KT / 16); the resident query operands are the eager ones (qh, ql per k-step).
+template <int SPB, int QB_>
+struct OpLazySplitT {
+    static constexpr int kSPB = SPB;
+    static constexpr int kSlotSteps = 16;
+    static constexpr int kRingDepth = 8;
+    static constexpr bool kLazy = true;
+    static constexpr bool kTile16 = false;
+    static constexpr bool kDmaBurst = false;
+    static constexpr bool kLag = SPB >= 4;
+    static constexpr bool kTauInRegs = true;
+    using Acc = AccSet;
+    static constexpr int kQB = QB_;
+    static constexpr int kNW = NNS_F_NW_F32;
+    static constexpr int kPrefetch = NNS_F_PF;
+    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    }
+};
+using OpLazySplit = OpLazySplitT<8, NNS_F_QB_F32>;   // KT = 128: C3
+
+template <class OP, class = void>
+struct is_lazy_op : std::false_type {};
+template <class OP>
+struct is_lazy_op<OP, std::void_t<decltype(OP::kLazy)>> : std::bool_constant<OP::kLazy> {};
+// fragment steps of a ring slot, ring depth: 32 and F_D unless the operator says otherwise
+template <class OP, class = void>
+struct slot_steps : std::integral_constant<int, 32> {};
+template <class OP>
+struct slot_steps<OP, std::void_t<decltype(OP::kSlotSteps)>> : std::integral_constant<int, OP::kSlotSteps> {};
+template <class OP, class = void>
+struct ring_depth : std::integral_constant<int, 4> {};
+template <class OP>
+struct ring_depth<OP, std::void_t<decltype(OP::kRingDepth)>> : std::integral_constant<int, OP::kRingDepth> {};
+
 template <class OP, class = void>
 struct is_split_op : std::false_type {};
 template <class OP>
@@ -454,6 +499,8 @@ __device__ __forceinline__ float share_min(float t)
 struct FilterArgs {
     const float4 *qimg;     // [m_pad/32][16][64] 16-byte fragments
     const char *rimg;       // [n_pad/32][16 KiB]
+    const char *rimg_lo;    // lazy image layout (K2 form 3): rimg holds the blocks' hi fragments back to back, rimg_lo the lo
+                            // fragments with the same block indexing; nullptr: the eager layout (hi, lo interleaved per k-step)
     const float *rnorm;     // [n_pad]
     const float *qnorm;     // [m_pad]
     const DevScalars *scal;
@@ -482,16 +529,27 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // norms of all its blocks.  In general lcm(SPB, 32) steps: 40 steps (640-deep) = 5 slots = 4 blocks.
     constexpr int SUP_GCD = SPB % 32 == 0 ? 32 : (SPB % 16 == 0 ? 16 : (SPB % 8 == 0 ? 8 : 1));
     // (24 steps, 384-deep: 3 slots = 4 blocks.)  "Deep" = the block does not divide the slot.
-    constexpr bool DEEP = 32 % SPB != 0;
+    // The lazy split operator streams hi fragments only: its slots are SPS = 16 steps in a ring of 8 (see OpLazySplitT);
+    // everywhere else SPS = 32, F_D = 4.
+    constexpr bool LAZY = is_lazy_op<OP>::value;
+    constexpr int SPS = slot_steps<OP>::value;
+    constexpr int F_D = ring_depth<OP>::value;
+    constexpr int F_SLOT_COORD = SPS * 1024;           // image bytes of one ring slot
+    constexpr int F_SLOT_NORM = LAZY ? 1024 : nns::F_SLOT_NORM;
+    constexpr int F_SLOT_BYTES = F_SLOT_COORD + F_SLOT_NORM;
+    constexpr int F_LDS_BYTES = F_D * F_SLOT_BYTES;
+    static_assert(F_LDS_BYTES == nns::F_LDS_BYTES, "every operator's ring takes the same LDS (launch_filter_t)");
+    constexpr bool DEEP = SPS % SPB != 0;
+    static_assert(SPS == 32 || !DEEP, "blocks straddling slots: 32-step slots only");
     constexpr int SUP_SLOTS = DEEP ? SPB / SUP_GCD : 1;
-    constexpr int SUP_BLKS = DEEP ? 32 / SUP_GCD : 32 / SPB;
+    constexpr int SUP_BLKS = DEEP ? 32 / SUP_GCD : SPS / SPB;
     constexpr int SPBLK = SUP_SLOTS;                   // (name kept: slots of a deep block's super-period)
-    constexpr int BPS = DEEP ? 1 : 32 / SPB;           // image blocks per ring slot (shallow tiles)
+    constexpr int BPS = DEEP ? 1 : SPS / SPB;          // image blocks per ring slot (shallow tiles)
     constexpr int BLK_BYTES = SPB * 1024;
     constexpr int SLOT_REFS = 32 * SUP_BLKS;           // norms DMAed with a slot
     constexpr int F_PPW = F_SLOT_COORD / 1024 / F_NW;   // 1 KiB DMA pieces per wave per slot
-    static_assert((32 % SPB == 0 && SPB >= 2) || SPB == 64 || SPB == 48 || SPB == 40 || SPB == 24, "a slot is 32 fragment steps");
-    static_assert(SUP_SLOTS * 32 == SUP_BLKS * SPB, "a super-period is whole slots and whole blocks");
+    static_assert((SPS % SPB == 0 && SPB >= 2) || SPB == 64 || SPB == 48 || SPB == 40 || SPB == 24, "a slot is SPS fragment steps");
+    static_assert(SUP_SLOTS * SPS == SUP_BLKS * SPB, "a super-period is whole slots and whole blocks");
     static_assert(SPBLK == 1 || (!OP::kLag && !OP::kTile16), "blocks straddling slots: lock-step 32x32 tiles only");
     static_assert(SLOT_REFS == 32 || SLOT_REFS == 64 || SLOT_REFS == 128 || SLOT_REFS == 256 || SLOT_REFS == 512,
                   "norm pieces: one dword per lane, or dwordx4 pieces of 256 norms");
@@ -504,7 +562,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // vmcnt(0) for half their cycles at the deep tiles).  Lock-step operators are done with slot s - 1 at the
     // barrier that opens interval s, so they fill slot s + 3 = s - 1 (mod 4) and wait with a COUNTED vmcnt that
     // leaves the youngest slot's pieces in flight across the barrier: TWO intervals of latency cover.
-    constexpr int AHEAD = (OP::kLag || F_DMA_AHEAD_MAX < 3) ? 2 : 3;
+    // The lazy ring of eight: lagging partners may fill slot s + 6 at most; NNS_F_LAZY_AHEAD slots ahead (A/B builds: 2 .. 6).
+#ifndef NNS_F_LAZY_AHEAD
+#define NNS_F_LAZY_AHEAD 4
+#endif
+    constexpr int AHEAD = LAZY ? NNS_F_LAZY_AHEAD : (OP::kLag || F_DMA_AHEAD_MAX < 3) ? 2 : 3;
+    static_assert(AHEAD >= 2 && AHEAD <= F_D - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
 #ifndef NNS_F_NORM_ONE
 #define NNS_F_NORM_ONE 1
 #endif
@@ -526,13 +589,17 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     constexpr bool T16 = OP::kTile16;
     constexpr int NS = T16 ? 2 * QB : QB;
     constexpr int QPS = T16 ? 16 : 32;          // queries per state
-    constexpr int NBQ = T16 ? SPB / 2 : SPB;    // resident operand fragments per state
+    constexpr int QFB = LAZY ? 2 * SPB : SPB;   // query fragments per 32-query block (lazy: qh and ql of each hi step)
+    constexpr int NBQ = T16 ? SPB / 2 : QFB;    // resident operand fragments per state
 
     // ---- resident B operands: this wave's QB x 32 queries, all of K (128 VGPRs at QB = 2) ----
     float4 bq[NS][NBQ];
     TauConsts tc[NS];
+    float bnd[NS];   // lazy split: B, how far a pair's three-product score can lie below its hi-hi score
+#pragma unroll
+    for (int st = 0; st < NS; ++st) bnd[st] = 0.0f;
     {
-        const float4 *src = a.qimg + (size_t)qblk0 * (SPB * 64) + lane;
+        const float4 *src = a.qimg + (size_t)qblk0 * (QFB * 64) + lane;
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
 #pragma unroll
@@ -543,6 +610,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                                     __uint_as_float(a.scal->ymax2_bits), a.bf16);
             else
                 tc[st] = TauConsts{0.0f, 0.0f, 0.0f};
+            if constexpr (LAZY)
+                bnd[st] = split_lazy_bound(a.kt, a.qnorm[qblk0 * 32 + st * QPS + (lane & (QPS - 1))],
+                                           __uint_as_float(a.scal->ymax2_bits));
         }
     }
     // Pin the loads here: hipcc must wait for them BEFORE the ring starts, not with a
@@ -556,6 +626,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             else
                 asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
         asm volatile("" : "+v"(tc[st].c0), "+v"(tc[st].c1), "+v"(tc[st].x2));
+        if constexpr (LAZY) asm volatile("" : "+v"(bnd[st]));
     }
     // The tau constants of the lane's states live in LDS behind the ring (2 KiB per wave, read only on
     // the slow path) instead of 3 registers per state; c1 depends on the tile depth alone and is
@@ -589,6 +660,16 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         const unsigned dst = lds_base + (s & (F_D - 1)) * F_SLOT_BYTES;
         if (p < F_PPW) {
             const int piece = wave * F_PPW + p;
+            if constexpr (is_split_op<OP>::value) {
+                if (a.rimg_lo) {
+                    // an eager kernel on the lazy image (the short-stream record forms of an index whose long streams run
+                    // the lazy kernel): LDS fragment `piece` = block piece / SPB, k-step (piece % SPB) / 2, hi (even) or lo
+                    const int pb = piece / SPB, pf = piece % SPB;
+                    const char *reg = (pf & 1) ? a.rimg_lo : a.rimg;
+                    dma16(reg + ((gslot * BPS + pb) * (SPB / 2) + (pf >> 1)) * 1024 + lane * 16, dst + piece * 1024);
+                    return;
+                }
+            }
             dma16(a.rimg + gslot * F_SLOT_COORD + piece * 1024 + lane * 16, dst + piece * 1024);
         } else if (NORM_ONE && ((int)gslot & (F_NW - 1)) != wave) {
             // the slot's norms are ONE wave's business, the waves taking turns slot by slot (round 1 - 3: every wave copied
@@ -610,6 +691,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 
     // ---- per-lane record state ---------------------------------------------------------
     float thr[NS];
+    float thrw[NS];   // lazy split: fl(thr + B), what a tile's hi-hi minimum is tested against
     int cnt[NS];
     // candidate lists are stored [split][state unit][entry][lane] (unit = the 64 lanes' lists of
     // one query block / query tile) so that both the appends of a wave and K5's per-query reads
@@ -617,7 +699,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     const size_t lblk0 = (size_t)blockIdx.y * (a.m_pad / QPS) + (size_t)qblk0 * (32 / QPS);
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
-        thr[st] = __builtin_inff();
+        thr[st] = thrw[st] = __builtin_inff();
 #if defined(NNS_DIAG) && defined(NNS_F_THR_NEGINF)   // timing experiment: the fast path alone (results are wrong)
         thr[st] = -__builtin_inff();
 #endif
@@ -728,6 +810,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         if (a.share_thr) t = share_min<T16>(t);
         // (a finite threshold: "x <= thr" then also excludes the +INF scores of padding refs)
         thr[st] = fminf(t, 3.4028234663852886e38f);
+        if constexpr (LAZY) thrw[st] = thr[st] + bnd[st];
     };
     // Slow path, step 2: one finished score x of ref j: append to the state's candidate ring (thr is finite
     // here — tighten clamps it — so "x <= thr" also excludes the +INF scores of padding refs).  `roomy`
@@ -774,6 +857,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             const float t4 = fminf(fminf(t[12], t[13]), t[14]);
             return fminf(fminf(fminf(t0, t1), t[15]), fminf(fminf(t2, t3), t4));
         }
+    };
+    auto frag_ptr = [&](const char *slot, int blk, int f) __attribute__((always_inline)) {
+        return (reinterpret_cast<const float4 *>(slot + (DEEP ? 0 : blk * BLK_BYTES)) + lane) + f * 64;
     };
     // slow path of one state: every score of the block against the lane's threshold
 #ifdef NNS_DIAG
@@ -877,7 +963,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         }
     };
     // record collection at the end of a ref block
-    auto epilogue = [&](const typename OP::Acc &acc, int blk_global) __attribute__((always_inline)) {
+    // (slot, blk: where the block's hi fragments still sit in the ring — the lazy form's refinement re-reads them)
+    auto epilogue = [&](typename OP::Acc &acc, int blk_global, const char *slot, int blk) __attribute__((always_inline)) {
         if constexpr ((kAblate & 2) != 0) {   // diagnostic: keep the accumulators alive, collect nothing
             static_for<NS>([&](auto st_c) __attribute__((always_inline)) {
                 constexpr int st = decltype(st_c)::value;
@@ -900,6 +987,30 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #ifdef NNS_DIAG
                 ++diag_tiles;
 #endif
+                if constexpr (LAZY) {
+                    // tm is the minimum of the HI-HI scores; no three-product score of the tile is below tm - B, so a tile
+                    // with tm > thr + B holds nothing within thr.  A flagged tile gets its cross products now, on the
+                    // same accumulator: rh x ql from the ring slot, rl x qh from the lo region of the image (plain
+                    // loads: the wait behind them also waits for older ring DMA pieces, as the !roomy branch's does)
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(tm <= thrw[st]) != 0ull, 0)) {
+                        const float4 *lo = reinterpret_cast<const float4 *>(a.rimg_lo) + (size_t)blk_global * (SPB * 64) + lane;
+                        float4 rl[SPB];
+#pragma unroll
+                        for (int b = 0; b < SPB; ++b) rl[b] = lo[b * 64];
+                        // (all of them in flight before the first is used: ONE round trip.  Left to itself hipcc rotates
+                        //  two registers through load - wait - MFMA, a round trip per k-step, with the workgroup waiting
+                        //  at the next slot barrier)
+#pragma unroll
+                        for (int b = 0; b < SPB; ++b) asm volatile("" : "+v"(rl[b].x), "+v"(rl[b].y), "+v"(rl[b].z), "+v"(rl[b].w));
+                        static_for<SPB>([&](auto b_c) __attribute__((always_inline)) {
+                            constexpr int b = decltype(b_c)::value;
+                            const float4 rh = *frag_ptr(slot, blk, b);
+                            acc.template at<st>() = OP::mma(rh, bq[st][2 * b + 1], acc.template at<st>());
+                            acc.template at<st>() = OP::mma(rl[b], bq[st][2 * b], acc.template at<st>());
+                        });
+                        record_all(acc, blk_global, st_c);
+                    }
+                } else
 #ifdef NNS_F_NOEXPECT
                 if (__builtin_amdgcn_ballot_w64(tm <= thr[st]) != 0ull)   // rare: ~ln(n) tiles per lane
 #else
@@ -914,7 +1025,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         if constexpr (T16) {
             // (16x16 tiles go through t16_step)
         } else {
-            if constexpr (is_split_op<OP>::value) {
+            if constexpr (LAZY) {
+                // the fast path: ref hi fragment of k-step b x qh
+                static_for<QB>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int qb = decltype(qc)::value;
+                    acc.template at<qb>() = OP::mma(frag, bq[qb][2 * b], acc.template at<qb>());
+                });
+            } else if constexpr (is_split_op<OP>::value) {
                 // ref hi fragment x (qh, ql) of the k-step; ref lo fragment x qh
                 static_for<QB>([&](auto qc) __attribute__((always_inline)) {
                     constexpr int qb = decltype(qc)::value;
@@ -1024,7 +1141,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     constexpr int PF = OP::kPrefetch;
     constexpr int RING = PF < 4 ? 4 : 8;
     constexpr int LAGOFF = SPB / 2;
-    static_assert(PF < RING && 32 % RING == 0 && (!OP::kLag || PF <= LAGOFF), "prefetch ring");
+    static_assert(PF < RING && SPS % RING == 0 && (!OP::kLag || PF <= LAGOFF), "prefetch ring");
     typename OP::Acc acc;
     if constexpr (T16) {
         const f32x4 inf4 = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
@@ -1037,10 +1154,6 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         for (int r = 0; r < 16; ++r) acc.v0[r] = acc.v1[r] = __builtin_inff();
     }
     float4 fr[RING];
-
-    auto frag_ptr = [&](const char *slot, int blk, int f) __attribute__((always_inline)) {
-        return (reinterpret_cast<const float4 *>(slot + (DEEP ? 0 : blk * BLK_BYTES)) + lane) + f * 64;
-    };
 
     using I0c = std::integral_constant<int, 0>;
     using I1c = std::integral_constant<int, 1>;
@@ -1059,11 +1172,11 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             constexpr int t = decltype(tc_)::value;
             constexpr int u = t - LAG * LAGOFF;
             // (fragment u of a slot sits at u KiB whatever the block depth: block * SPB + step = u)
-            if constexpr (u < 0) fr[t % RING] = *frag_ptr(prev, 0, 32 + u);
-            else if constexpr (u < 32) fr[t % RING] = *frag_ptr(cur, 0, u);
-            else fr[t % RING] = *frag_ptr(nxt, 0, u - 32);   // (last interval: stale slot, unused)
+            if constexpr (u < 0) fr[t % RING] = *frag_ptr(prev, 0, SPS + u);
+            else if constexpr (u < SPS) fr[t % RING] = *frag_ptr(cur, 0, u);
+            else fr[t % RING] = *frag_ptr(nxt, 0, u - SPS);   // (last interval: stale slot, unused)
         };
-        static_for<32>([&](auto tc_) __attribute__((always_inline)) {
+        static_for<SPS>([&](auto tc_) __attribute__((always_inline)) {
             constexpr int t = decltype(tc_)::value;
             constexpr int u = t - LAG * LAGOFF;
             // block (of the slot / of the super-period) and operand / k position inside it
@@ -1077,7 +1190,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #ifdef NNS_F_DMA_SAMEPHASE
                 constexpr int d0 = 2;
 #else
-                constexpr int d0 = DPH == 0 ? 2 : 16;
+                constexpr int d0 = DPH == 0 ? 2 : SPS / 2;
 #endif
 #ifdef NNS_F_DMA_SP
                 constexpr int sp = NNS_F_DMA_SP;
@@ -1087,7 +1200,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                 // apart loses everywhere: profiles/r03_ab_dma_burst.txt)
                 constexpr int sp = (T16 && SPB == 16 && QB == 2) ? 1 : ((F_PPW + F_NP) * 2 <= 14 ? 2 : 1);
 #endif
-                static_assert(d0 + sp * (F_PPW + F_NP) <= 32, "DMA pieces must fit the interval");
+                static_assert(d0 + sp * (F_PPW + F_NP) <= SPS, "DMA pieces must fit the interval");
                 // fp32 operators issue a slot's pieces BACK TO BACK at one step (round 3, second session): a lone LDS-DMA piece
                 // costs its SIMD ~130 cycles of MFMA issue, a burst of them far less per piece (tools/ubench/chain_loop.hip:
                 // 36.8 -> 25.2 ms); C3 118.3 -> 117.6 ms (OP::kDmaBurst: by tile depth).  The bf16 operators keep one piece per step: bursts cost THEM 1 - 6 %
@@ -1130,9 +1243,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                             epilogue_top2(acc, blk0_global + blk);
                         }
                     } else if constexpr (u < 0) {
-                        if (!first) epilogue(acc, blk0_global - 1);
+                        if (!first) epilogue(acc, blk0_global - 1, prev, BPS - 1);
                     } else {
-                        epilogue(acc, blk0_global + blk);
+                        epilogue(acc, blk0_global + blk, cur, blk);
                     }
                 }
             }
@@ -1154,9 +1267,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     static_assert((F_D & (F_D - 1)) == 0, "ring depth must be a power of two");
 
     // prologue: slots 0 .. AHEAD - 1 in flight; confirm slot 0; start interval 0's first fragments
-    issue(0);
-    issue(1);
-    if constexpr (AHEAD == 3) issue(2);
+    static_for<AHEAD>([&](auto s_c) __attribute__((always_inline)) { issue(decltype(s_c)::value); });
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * F_PPS) : "memory");
     __builtin_amdgcn_s_barrier();
     if constexpr (T16) seed16(ring(0), 0, I0c{});   // the first block's tile-0 norms
@@ -1259,7 +1370,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             mma_all(acc, fr[t % RING], std::integral_constant<int, SPB - LAGOFF + t>{});
         });
         if (top2) epilogue_top2(acc, (slot0 + ns) * BPS - 1);
-        else epilogue(acc, (slot0 + ns) * BPS - 1);
+        else epilogue(acc, (slot0 + ns) * BPS - 1, lastp, BPS - 1);
     }
     if constexpr (!T16) if (top2) {
         // record form 2: three entries per lane state — (best tile's minimum, first ref of the lane's rows of that tile),
@@ -1311,6 +1422,13 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_split_kernel(const Filter
     filter_main<OP>(a);
 }
 
+// the lazy split operators (OpLazySplitT)
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_lazy_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
+
 // ---- self-test: one 32x32 tile through the same MFMA k-order as the filter --------
 // out[i][j] = accumulate over the image's k order of a[i][.] * b[j][.] seeded with c0[i];
 // a, b are [32][kt] fp32 (bf16 mode: values must be bf16-representable).  Lets the tests
@@ -1355,6 +1473,32 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+        }
+    } else if (bf16 == 4) {
+        // the lazy order of OpLazySplitT: the kt / 16 hi-hi MFMAs (partial result to out + 1024), then per k-step al.bh
+        // (ref hi x query lo) and ah.bl on the same accumulator.  (a = query rows, b = ref rows as above.)
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int s = 0; s < kt / 16; ++s) {
+                bf16x8 ah, al, bh, bl;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float av = a[i * kt + 16 * s + 8 * h + e], bv = b[i * kt + 16 * s + 8 * h + e];
+                    ah[e] = (__bf16)av;
+                    al[e] = (__bf16)__fsub_rn(av, (float)ah[e]);
+                    bh[e] = (__bf16)bv;
+                    bl[e] = (__bf16)__fsub_rn(bv, (float)bh[e]);
+                }
+                if (pass == 0) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+                } else {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+                }
+            }
+            if (pass == 0) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) out[1024 + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[r];
+            }
         }
     } else {
         // bf16 == 2: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
@@ -1421,7 +1565,14 @@ constexpr bool split_depth(int kt)
     return kt == 16 || kt == 32 || kt == 64 || kt == 128 || kt == 256;
 }
 
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split)
+// Depths at which the split operands run the lazy schedule (OpLazySplitT) unless NNS_FILTER_SPLIT_EAGER is given: KT = 128
+// (C3: profiles/lazy_ab_depths.jsonl).  The other depths keep the eager kernels until a same-device A/B shows a win.
+constexpr bool lazy_depth(int kt)
+{
+    return kt == 128;
+}
+
+int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
     int kt = 0;
@@ -1513,6 +1664,11 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     // bf16 tiles: their epilogue has no vector slots to spare), 2 the lane's two best tiles, branch-free (short streams,
     // 32 x 32 tiles: every fp32 depth and the 768- / 1024-deep bf16-operand tiles)
     g->tile_rec = (stream_tiles <= kTileRecMaxTiles && g->splits >= 4 && !per_ref) ? (g->lpq == 4 ? 1 : 2) : 0;
+    // The lazy schedule: an index of a lazy depth keeps its image in the lazy layout whatever the query count (the
+    // layout is fixed when the index is built); a search runs the lazy kernel where its records are per score, and the
+    // eager kernel — reading the same image — on the short-stream record forms, where nearly every tile refines anyway.
+    g->lazy_img = (g->split && lazy_depth(kt) && !split_eager) ? 1 : 0;
+    g->lazy = (g->lazy_img && g->tile_rec == 0) ? 1 : 0;
 #ifdef NNS_F_NOTOP2
     if (g->tile_rec == 2) g->tile_rec = 1;
 #endif
@@ -1529,7 +1685,8 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (is_split_op<OP>::value) return filter_split_kernel<OP>;
+        if constexpr (is_lazy_op<OP>::value) return filter_lazy_kernel<OP>;
+        else if constexpr (is_split_op<OP>::value) return filter_split_kernel<OP>;
         else return filter_kernel<OP>;
     }();
     // + 2 KiB per wave for the lanes' tau constants
@@ -1554,6 +1711,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
     FilterArgs a;
     a.qimg = reinterpret_cast<const float4 *>(qimg);
     a.rimg = reinterpret_cast<const char *>(rimg);
+    a.rimg_lo = g.lazy_img ? a.rimg + (size_t)g.n_pad * g.kt * 2 : nullptr;
     a.rnorm = rnorm;
     a.qnorm = qnorm;
     a.scal = scal;
@@ -1582,6 +1740,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
                              : g.kt == 640  ? launch_filter_t<OpBF16K640>(g, a, st)
                              : g.kt == 384  ? launch_filter_t<OpBF16K384>(g, a, st)
                                            : launch_filter_t<OpBF16Active>(g, a, st))
+                          : g.lazy ? launch_filter_t<OpLazySplit>(g, a, st)
                           : g.split ? (g.kt == 16    ? launch_filter_t<OpSplitK16>(g, a, st)
                                        : g.kt == 32  ? launch_filter_t<OpSplitK32>(g, a, st)
                                        : g.kt == 64  ? launch_filter_t<OpSplitK64>(g, a, st)

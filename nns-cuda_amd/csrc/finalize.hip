@@ -48,6 +48,20 @@
 //  (iii) every fp32 operation above is monotone non-decreasing in a, so t >= a ==> Tf(t) >= Tf(a), and
 //       fl(1.002 tau_fl) >= tau_fl gives Tf(a) >= T5(a): a lane's threshold — the minimum of Tf over the tile minima
 //       it has seen, all >= the query's final minimum a — never drops below T5(a); whatever K5 selects was recorded.
+//
+// The lazy split filter's B (split_lazy_bound; K5 does not need it).  The lazy kernel tests a tile's HI-HI scores
+// s_hh (the accumulator after the kt/16 qh.rh MFMAs) against fl(thr + B) and finishes only flagged tiles with the cross
+// MFMAs, on the same accumulator: s_3 = s_hh + (computed qh.rl + ql.rh).  With a = 2^-8, |h| <= (1+a)|v|,
+// |l| <= a(1+a)|v| and v = -2y':
+//     s_hh - s_3 <= |qh.rl + ql.rh|                       <= 2a (1+a)^2 sum |x'_t v_t| <= 2a (1+a)^2 2XY
+//                 + the 2kt + 2kt/16 adds behind the partial, 2u each on |partial sums| <= Y^2 + (1 + 2^-5) 2XY
+//                 + mode 3's absolute floor (parts, products, adds below 2^-126).
+// fl(thr + B) is ONE rounding at the score's magnitude, as in (ii): |thr + B| <= (X + Y)^2 (1 + small), and B carries
+// 2u ((X + Y)^2 + ...) for it, so fl(thr + B) >= thr + (the three terms above).  Hence a tile with min s_hh > fl(thr + B)
+// has no s_3 <= thr, contributes nothing in the eager kernel either, and running minimum, thresholds and recorded set
+// are the eager kernel's up to summation order (the mode-3 accumulation model is order-free).  B ~ 2^-6 XY: half of
+// mode 2's margin, 2^7 times mode 3's tau — it only decides which tiles are refined, never what is recorded.
+// (tests/test_lazy_split_cpu.py: the split emulated exactly, both sums in the lazy order, fl(thr + B) in fp32.)
 #include "nns_internal.h"
 
 namespace nns {

@@ -188,12 +188,17 @@ int order_after_default_stream(hipStream_t st)
 // exclude each other.
 static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
 {
-    if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32)) && bf16) {
-        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands) apply to fp32 points (bf16 points use the bf16 filter)");
+    if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) && bf16) {
+        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16 points use the bf16 filter)");
         return NNS_ERR_INVALID;
     }
     if ((flags & NNS_FILTER_BF16) && (flags & NNS_FILTER_F32)) {
         set_error("NNS_FILTER_BF16 and the fp32-operand flag exclude each other");
+        return NNS_ERR_INVALID;
+    }
+    // (the eager flag chooses among the split kernels: with another operand form there is nothing to choose)
+    if ((flags & NNS_FILTER_SPLIT_EAGER) && (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32))) {
+        set_error("the eager-split flag selects a schedule of the split operands: not with NNS_FILTER_BF16 or the fp32-operand flag");
         return NNS_ERR_INVALID;
     }
     *mixed = !bf16 && ((flags & NNS_FILTER_BF16) || ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && k > 256 && k <= kMaxFilterK));
@@ -215,7 +220,7 @@ static int prep_refs(nns_index *ix, hipStream_t st)
                              &ix->scal->r_maxabs_bits, st));
     NNS_TRY(launch_prep_image(ix->k, g.kt, ix->n, g.n_pad, (const float *)ix->r_dev, ix->mean, -2.0f,
                               INFINITY, (float *)ix->rimg, ix->rnorm, &ix->scal->ymax2_bits, nullptr, st,
-                              g.split ? 2 : ix->mixed ? 1 : 0));
+                              g.lazy_img ? 3 : g.split ? 2 : ix->mixed ? 1 : 0));
     return NNS_OK;
 }
 
@@ -353,7 +358,8 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             ix->ev_valid = true;
         }
         if (path == NNS_PATH_MFMA) {
-            if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split)) !=
+            if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
+                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0)) !=
                 NNS_OK)
                 break;
             const FilterGeom &g = ix->geom;
@@ -438,7 +444,8 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st)
 {
     FilterGeom g = ix->geom;
     FilterGeom gq{};
-    NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split));
+    NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split,
+                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
     (void)g;
     if (gq.m_pad > ix->m_cap) {
@@ -917,6 +924,13 @@ int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3)
     return NNS_OK;
 }
 
+int nns_split_lazy_bound(int kt, float qnorm2, float ymax2, float *out1)
+{
+    if (kt <= 0 || !out1) return NNS_ERR_INVALID;
+    *out1 = split_lazy_bound(kt, qnorm2, ymax2);
+    return NNS_OK;
+}
+
 int nns_keys_min(nns_key *inout_dev, const nns_key *other_dev, int m, void *stream)
 {
     if (!inout_dev || !other_dev || m <= 0) return NNS_ERR_INVALID;
@@ -935,14 +949,26 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset, v
     return launch_fill_uniform(dev, count, seed, offset, (hipStream_t)stream);
 }
 
+static int selftest_mfma_impl(int kt, int bf16, const float *a, const float *b, const float *c0, float *out, float *out_hh);
+
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0, float *out)
 {
-    if (kt <= 0 || (kt & 15) || (bf16 == 2 && (kt & 31)) || bf16 < 0 || bf16 > 3 || !a || !b || !c0 || !out)
+    return selftest_mfma_impl(kt, bf16, a, b, c0, out, nullptr);
+}
+
+int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *c0, float *out, float *out_hh)
+{
+    return selftest_mfma_impl(kt, 4, a, b, c0, out, out_hh);
+}
+
+static int selftest_mfma_impl(int kt, int bf16, const float *a, const float *b, const float *c0, float *out, float *out_hh)
+{
+    if (kt <= 0 || (kt & 15) || (bf16 == 2 && (kt & 31)) || bf16 < 0 || bf16 > 4 || !a || !b || !c0 || !out)
         return NNS_ERR_INVALID;
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(0));
     float *d = nullptr;
-    const size_t na = (size_t)32 * kt, total = 2 * na + 32 + 1024;
+    const size_t na = (size_t)32 * kt, total = 2 * na + 32 + 2048;   // (mode 4: the hi-hi partial behind the result)
     NNS_HIP(pool_alloc(&d, total * sizeof(float)));
     int rc = NNS_OK;
     if (hipMemcpy(d, a, na * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -951,6 +977,9 @@ int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const fl
         rc = NNS_ERR_HIP;
     if (rc == NNS_OK) rc = launch_mfma_selftest(kt, bf16, d, d + na, d + 2 * na, d + 2 * na + 32, nullptr);
     if (rc == NNS_OK && hipMemcpy(out, d + 2 * na + 32, 1024 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = NNS_ERR_HIP;
+    if (rc == NNS_OK && bf16 == 4 && out_hh &&
+        hipMemcpy(out_hh, d + 2 * na + 32 + 1024, 1024 * 4, hipMemcpyDeviceToHost) != hipSuccess)
         rc = NNS_ERR_HIP;
     if (rc == NNS_ERR_HIP) set_error("nns_selftest_mfma: %s", hipGetErrorString(hipGetLastError()));
     pool_free(d);
@@ -1084,10 +1113,11 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
     bool mixed = false, split = false;
     NNS_TRY(operand_form(k, bf16_points != 0, flags, &mixed, &split));
     FilterGeom g{};
-    NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split));
-    const int v[15] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
-                       g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split};
-    memcpy(out, v, (out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
+    NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split,
+                        (flags & NNS_FILTER_SPLIT_EAGER) != 0));
+    const int v[16] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
+                       g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split, g.lazy};
+    memcpy(out, v, (out_len >= 16 ? 16 : out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
     return NNS_OK;
 }
 

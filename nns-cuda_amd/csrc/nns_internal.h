@@ -273,6 +273,8 @@ struct FilterGeom {
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
     int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
+    int lazy;             // split = 1: the lazy schedule (OpLazySplitT: cross products only on tiles near the threshold)
+    int lazy_img;         // split = 1: the ref image is in the lazy layout (hi fragments | lo fragments; K2 form 3)
     int kt;               // K of the tile (k padded up with zeros)
     int m_pad;            // queries padded to the workgroup's query count
     int n_pad;            // refs padded to a whole ring slot
@@ -368,6 +370,33 @@ __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax
     t.c1 = (float)(c1 * (1.0 + 1e-6));
     t.x2 = (float)(X2 * (1.0 + 1e-6));
     return t;
+}
+
+// B of the lazy split filter (OpLazySplitT): an upper bound, per query, on s_hh - s_3 — how far the finished
+// three-product score of a (query, ref) pair can lie BELOW the score its accumulator held after the hi-hi products
+// alone — plus the rounding of the kernel's fl(thr + B).  A tile whose hi-hi minimum is above fl(thr + B) has no
+// three-product score within thr.  Same X, Y, a = 2^-8 and operand bounds as tau_consts' mode 3 (v = -2 y'):
+//   cross products  |qh.rl + ql.rh| <= sum (|qh_t||rl_t| + |ql_t||rh_t|) <= 2a (1 + a)^2 sum |x'_t v_t| <= 2a (1 + a)^2 2XY;
+//   their accumulation: 2 kt products in 2 kt / 16 MFMAs continue the accumulator, 2u per add (the order-free model of
+//     mode 3) on partial sums of magnitude <= Y^2 + sum |products| <= Y^2 + (1 + 2^-5) 2XY;
+//   the absolute floor of mode 3 for operand parts, products and adds below 2^-126 (all three products' worth);
+//   fl(thr + B): one rounding at the magnitude of the score, |thr + B| <= (X + Y)^2 (1 + small) — 2u (X + Y)^2 as
+//     tau_consts' er term (the spare u covers tau, B and e3 riding on thr).
+// (The hi-hi partial's own accumulation error is in neither s_hh nor s_3 twice: both are values of the same accumulator.)
+__host__ __device__ inline float split_lazy_bound(int kt, float qnorm2, float ymax2)
+{
+    const double u = 5.9604644775390625e-08;   // 2^-24
+    const double a = 0x1p-8;
+    const double X2 = (double)qnorm2 * (1.0 + 4.0 * u);
+    const double Y2 = (double)ymax2 * (1.0 + 4.0 * u);
+    const double X = sqrt(X2), Y = sqrt(Y2);
+    const double cross = 2.0 * a * (1.0 + a) * (1.0 + a) * 2.0 * X * Y;
+    const double nb = 2.0 * kt + 2.0 * (kt / 16) + 2.0;
+    const double gb = 2.0 * nb * u / (1.0 - 2.0 * nb * u);
+    const double acc = gb * (Y2 + (1.0 + 0x1p-5) * 2.0 * X * Y);
+    const double ef = 0x1p-124 * sqrt((double)kt) * (X + 2.0 * Y) + (7.0 * kt + 4.0) * 0x1p-126;
+    const double er = 2.0 * u * ((X + Y) * (X + Y) + cross + acc + ef);
+    return (float)((cross + acc + ef + er + 1e-30) * (1.0 + 1e-6));
 }
 
 __host__ __device__ inline float tau_of(const TauConsts &t, float a)
@@ -469,6 +498,8 @@ int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts,
                       float *img, float *norms, unsigned *max_norm_bits,
                       unsigned *maxabs_bits, hipStream_t st, int form = 0);
 
+// form: 0 fp32 image, 1 bf16-rounded operands, 2 split-bf16 operands (hi, lo fragment per k-step), 3 the same values in
+// the lazy layout: the hi fragments of all blocks ([npts_pad / 32][kt / 16] KiB), then the lo fragments likewise
 // bf16 points (raw uint16 bits) -> bf16 tile image [blk][16][64 lanes][8 bf16], value * scale
 // (scale = 1 or -2, exact), fp32 norms of the UNcentred points, max-|v| word
 // dimension-major [k][n] -> point-major [n][k] (the inverse of the reference's mat_inv_kernel,
@@ -480,8 +511,10 @@ int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, con
                            unsigned *maxabs_bits, hipStream_t st);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
+// split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
-                bool split = false);
+                bool split = false, bool split_eager = false);
+// rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
                   hipStream_t st);

@@ -237,8 +237,10 @@ __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float
         }
     }
 
-    if constexpr (BF == 2) {
-        uint4 *outb = reinterpret_cast<uint4 *>(img + (size_t)blk * 32 * KT);
+    if constexpr (BF == 2 || BF == 3) {
+        // BF = 3, the lazy layout of the same values: fragment s of the block's hi parts at [blk][s], of its lo parts at
+        // [gridDim.x + blk][s] (one launch covers the whole padded point set: gridDim.x blocks), KT / 16 fragments each
+        uint4 *outb = reinterpret_cast<uint4 *>(img + (BF == 2 ? (size_t)blk * 32 * KT : 0));
         for (int f = tid; f < (KT / 8) * 64; f += 256) {
             const int s2 = f >> 6, lane = f & 63;
             const int i = lane & 31, d0 = 16 * (s2 >> 1) + 8 * (lane >> 5);
@@ -255,9 +257,13 @@ __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float
                 }
                 w[e] = (unsigned)p[0] | ((unsigned)p[1] << 16);
             }
-            outb[f] = make_uint4(w[0], w[1], w[2], w[3]);
+            if constexpr (BF == 3)
+                outb[(((lo_part ? (size_t)gridDim.x : 0) + blk) * (KT / 16) + (s2 >> 1)) * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
+            else
+                outb[f] = make_uint4(w[0], w[1], w[2], w[3]);
         }
     } else if constexpr (BF != 0) {
+        static_assert(BF == 1, "BF 2 / 3 are handled above");
         static_assert(BF == 0 || KT == 256 || KT == 128, "the bf16 operand image is 128 or 256 deep");
         // fragment f = NKS * tile + k-step; lane l: point 16 tile + (l & 15), dims 32 ks + 8 (l >> 4) .. + 7
         constexpr int NKS = KT / 32;
@@ -462,6 +468,16 @@ int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, c
                       unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form)
 {
     const int blocks = npts_pad / 32;
+    if (form == 3) {   // split-bf16 operands in the lazy layout (the depths of the lazy kernel)
+        if (kt != 128) {
+            set_error("prep: the lazy split layout is built at tile K 128 only (kt = %d)", kt);
+            return NNS_ERR_UNSUPPORTED;
+        }
+        hipLaunchKernelGGL((image_kernel<128, 3>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm, img,
+                           norms, max_norm_bits, maxabs_bits);
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
+    }
     if (form == 2) {   // split-bf16 operands at the fp32 depths
         switch (kt) {
         case 16:

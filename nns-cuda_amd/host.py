@@ -33,6 +33,7 @@ NNS_KEY_NONE = 0x7F80000000000000
 
 NNS_RECORDS_PER_REF = 512
 NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
+NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three products per tile) at every depth
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -47,7 +48,7 @@ ABI_SYMBOLS = (
     "nns_trim", "nns_warmup", "nns_shutdown", "nns_search_bf16_multi",
     "nns_index_near_ties", "nns_tau_consts", "nns_index_search_indices", "nns_selftest_lane_share", "nns_plan_filter", "nns_plan_exact",
     "nns_comm_unique_id", "nns_comm_create", "nns_comm_size", "nns_comm_allreduce_min", "nns_comm_destroy",
-    "nns_multi_last_exchange_ranks", "nns_index_filter_form",
+    "nns_multi_last_exchange_ranks", "nns_index_filter_form", "nns_selftest_mfma_lazy", "nns_split_lazy_bound",
     "nns_index_search_topk", "nns_keys_topk_merge", "nns_keys_topk_unpack", "nns_search_f32_topk",
     "nns_search_bf16_topk", "nns_plan_topk",
     "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
@@ -122,6 +123,8 @@ def _load() -> ctypes.CDLL:
     lib.nns_keys_unpack.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
     lib.nns_fill_uniform.argtypes = [c_vp, c_sz, c_u64, c_u64, c_vp]
     lib.nns_selftest_mfma.argtypes = [c_int, c_int, c_vp, c_vp, c_vp, c_vp]
+    lib.nns_selftest_mfma_lazy.argtypes = [c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.nns_split_lazy_bound.argtypes = [c_int, ctypes.c_float, ctypes.c_float, c_vp]
     lib.nns_index_search_topk.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp]
     lib.nns_keys_topk_merge.argtypes = [c_vp, c_vp, c_int, c_int, c_vp]
     lib.nns_keys_topk_unpack.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp]
@@ -174,13 +177,35 @@ def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: int = 0) -
     return out
 
 
-def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0) -> dict:
+def selftest_mfma_lazy(a: np.ndarray, b: np.ndarray, c0: np.ndarray):
+    """(out, out_hh) of nns_selftest_mfma_lazy: the split chain in the lazy filter's order and its hi.hi partial."""
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    c0 = np.ascontiguousarray(c0, np.float32)
+    assert a.shape == b.shape and a.shape[0] == 32 and c0.shape == (32,)
+    out = np.empty((32, 32), np.float32)
+    out_hh = np.empty((32, 32), np.float32)
+    _check(lib.nns_selftest_mfma_lazy(a.shape[1], a.ctypes.data, b.ctypes.data, c0.ctypes.data, out.ctypes.data,
+                                      out_hh.ctypes.data), "nns_selftest_mfma_lazy")
+    return out, out_hh
+
+
+def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
+    """B of the lazy split filter (nns_split_lazy_bound)."""
+    out = np.empty(1, np.float32)
+    _check(lib.nns_split_lazy_bound(kt, qnorm2, ymax2, out.ctypes.data), "nns_split_lazy_bound")
+    return float(out[0])
+
+
+def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0, schedule: bool = False) -> dict:
     """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  "split": 1 when fp32 points
-    take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0)."""
-    out = np.zeros(15, np.int32)
-    _check(lib.nns_plan_filter(k, m, n, int(bf16), flags, out.ctypes.data, 15), "nns_plan_filter")
+    take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0).  schedule=True asks for the
+    16th field too, "lazy": 1 when the split operands run the lazy schedule (0 with NNS_FILTER_SPLIT_EAGER)."""
+    nf = 16 if schedule else 15
+    out = np.zeros(nf, np.int32)
+    _check(lib.nns_plan_filter(k, m, n, int(bf16), flags, out.ctypes.data, nf), "nns_plan_filter")
     names = ("kt", "bf16", "mixed", "lpq", "m_pad", "n_pad", "total_slots", "splits", "slots_per_split", "qgroups",
-             "slot_pts", "queries_per_wg", "share_thr", "tile_rec", "split")
+             "slot_pts", "queries_per_wg", "share_thr", "tile_rec", "split", "lazy")[:nf]
     return dict(zip(names, (int(v) for v in out)))
 
 
@@ -436,9 +461,11 @@ class Index:
     """One prepared, device-resident shard of reference points (nns_index)."""
 
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
-                 soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False):
+                 soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False,
+                 filter_split_eager: bool = False):
         """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
-        filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones."""
+        filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
+        filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER)."""
         import torch
         if refs.dtype not in (torch.float32, torch.bfloat16) or refs.dim() != 2 or not refs.is_contiguous() \
                 or not refs.is_cuda:
@@ -448,7 +475,8 @@ class Index:
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
-            | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0)
+            | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
+            | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0)
         h = ctypes.c_void_p()
         create = lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),

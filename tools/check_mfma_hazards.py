@@ -153,7 +153,7 @@ def main() -> int:
         text = f.read().splitlines()
     kernels, cur, name = {}, None, None
     for i, l in enumerate(text, 1):
-        m = re.match(r"^(_Z\w*filter_(?:split_)?kernel\w*):", l)
+        m = re.match(r"^(_Z\w*filter_(?:split_|lazy_)?kernel\w*):", l)
         if m:
             name, cur = m.group(1), []
             kernels[name] = cur

@@ -4,6 +4,8 @@
 usage: probe_split.py ab [k ...]      per-depth A/B at 65536 x 1048576 (default k = 16 32 64 128 256): the two forms
                                       alternate, 3 runs of 5 timed searches each; filter_ms (HIP events, NNS_PROFILE) and
                                       wall ms per search, keys of the two forms compared bit for bit
+       probe_split.py ab lazy [k ...] the same A/B of the split operands' two schedules: lazy (the default where the library
+                                      enables it) against eager (NNS_FILTER_SPLIT_EAGER); default k = 128
        probe_split.py c3 split|f32 N  N C3 searches (65536 x 1048576 x 128) of one form (rocprofv3 / PMC runs)
        probe_split.py cluster         tight Gaussian clusters at 65536 x 1048576 x 128: exact-scan (ambiguous) and
                                       multi-candidate queries of each operand form
@@ -44,10 +46,12 @@ def timed(ix, q, keys, steps):
     return wall, st["filter_ms"], st
 
 
-def ab(ks):
+def ab(ks, lazy=False):
+    # (lazy: "split" = the default schedule, "f32" = the partner arm, here the eager split schedule)
     for k in ks:
         q, r = uniform(M, N, k)
-        ixs = {f: pkg.Index(r, path="mfma", profile=True, filter_f32=(f == "f32")) for f in ("split", "f32")}
+        partner = {"filter_split_eager": True} if lazy else {"filter_f32": True}
+        ixs = {f: pkg.Index(r, path="mfma", profile=True, **(partner if f == "f32" else {})) for f in ("split", "f32")}
         keys = {f: torch.empty(M, dtype=torch.int64, device="cuda") for f in ixs}
         for f, ix in ixs.items():
             ix.search_keys(q, keys[f])
@@ -61,7 +65,10 @@ def ab(ks):
                 res[f]["form"] = st["filter_form"]
         same = bool(torch.equal(keys["split"], keys["f32"]))
         fs, ff = np.median(res["split"]["filter_ms"]), np.median(res["f32"]["filter_ms"])
-        print(json.dumps({"probe": "ab", "m": M, "n": N, "k": k, "kt": ixs["split"].stats()["k_tile"], **res,
+        if lazy:
+            res = {"lazy": res["split"], "eager": res["f32"]}
+            res["lazy"]["lazy_planned"] = pkg.plan_filter(k, M, N, schedule=True)["lazy"]
+        print(json.dumps({"probe": "ab_lazy" if lazy else "ab", "m": M, "n": N, "k": k, "kt": ixs["split"].stats()["k_tile"], **res,
                           "filter_speedup_median": round(float(ff / fs), 3), "keys_equal": same}), flush=True)
         for ix in ixs.values():
             ix.close()
@@ -99,12 +106,15 @@ def cluster():
         q, r = clustered(M, N, 128, 1024, sigma)
         out = {}
         keys0 = None
-        for f, kw in (("split", {}), ("f32", {"filter_f32": True}), ("bf16", {"filter_bf16": True})):
-            ix = pkg.Index(r, path="mfma", **kw)
+        for f, kw in (("split", {}), ("split_eager", {"filter_split_eager": True}), ("f32", {"filter_f32": True}),
+                      ("bf16", {"filter_bf16": True})):
+            ix = pkg.Index(r, path="mfma", profile=True, **kw)
             keys = ix.search_keys(q)
             torch.cuda.synchronize()
+            fms = [timed(ix, q, keys, 3)[1] for _ in range(3)]
             st = ix.stats()
-            out[f] = {"ambiguous": st["ambiguous"], "multi_candidate": st["multi_candidate"]}
+            out[f] = {"ambiguous": st["ambiguous"], "multi_candidate": st["multi_candidate"],
+                      "filter_ms": [round(x, 3) for x in fms]}
             if keys0 is None:
                 keys0 = keys.clone()
             else:
@@ -139,7 +149,10 @@ def denorm():
 if __name__ == "__main__":
     what = sys.argv[1]
     if what == "ab":
-        ab([int(x) for x in sys.argv[2:]] or [16, 32, 64, 128, 256])
+        if sys.argv[2:3] == ["lazy"]:
+            ab([int(x) for x in sys.argv[3:]] or [128], lazy=True)
+        else:
+            ab([int(x) for x in sys.argv[2:]] or [16, 32, 64, 128, 256])
     elif what == "c3":
         c3(sys.argv[2], int(sys.argv[3]))
     elif what == "cluster":
