@@ -566,6 +566,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #ifndef NNS_F_LAZY_AHEAD
 #define NNS_F_LAZY_AHEAD 4
 #endif
+    // A query's two lanes adopt the smaller of their thresholds in the lazy kernel whatever the stream length (tighten);
+    // 0: only where the plan says so (A/B builds)
+#ifndef NNS_F_LAZY_SHARE
+#define NNS_F_LAZY_SHARE 1
+#endif
+    constexpr bool kLazyShare = NNS_F_LAZY_SHARE != 0;
     constexpr int AHEAD = LAZY ? NNS_F_LAZY_AHEAD : (OP::kLag || F_DMA_AHEAD_MAX < 3) ? 2 : 3;
     static_assert(AHEAD >= 2 && AHEAD <= F_D - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
 #ifndef NNS_F_NORM_ONE
@@ -701,7 +707,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     for (int st = 0; st < NS; ++st) {
         thr[st] = thrw[st] = __builtin_inff();
 #if defined(NNS_DIAG) && defined(NNS_F_THR_NEGINF)   // timing experiment: the fast path alone (results are wrong)
-        thr[st] = -__builtin_inff();
+        thr[st] = thrw[st] = -__builtin_inff();
 #endif
         cnt[st] = 0;
     }
@@ -807,7 +813,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         // every tile is slow), costs 0.2 % on C3 / C5: a launch-time choice by stream length
         // (launch_filter).  Row swaps (v_permlane32_swap / 16_swap, gfx950), not ds_bpermute: no LDS
         // round trip.  (Wave-uniform slow path: every lane is active here.)
-        if (a.share_thr) t = share_min<T16>(t);
+        // The LAZY kernel shares on long streams too (NNS_F_LAZY_SHARE, in the kernel: the plan's share_thr stays what
+        // it is).  There a flag costs a refinement — 8 global loads, a wait that also drains the wave's ring pieces, and
+        // 16 MFMAs: ~1900 cycles of the wave, ~185 of the workgroup — not the eager kernel's few dozen VALU
+        // instructions, and one record process over a query's n refs flags 43 % fewer tiles than two private ones over
+        // n / 2 each (C3: 3.40 % -> 1.93 % of the retirements, filter 13.70 -> 13.05 ms; DESIGN, "Where the lazy
+        // kernel's time goes").  Lists only get shorter; every entry K5 needs is still <= every threshold the lane holds.
+        if (a.share_thr || (LAZY && kLazyShare)) t = share_min<T16>(t);
         // (a finite threshold: "x <= thr" then also excludes the +INF scores of padding refs)
         thr[st] = fminf(t, 3.4028234663852886e38f);
         if constexpr (LAZY) thrw[st] = thr[st] + bnd[st];
@@ -864,13 +876,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // slow path of one state: every score of the block against the lane's threshold
 #ifdef NNS_DIAG
     unsigned diag_slow = 0, diag_tiles = 0;   // slow-path executions / retired (tile, state) pairs of this wave
-    unsigned long long diag_cyc = 0;   // s_memtime ticks spent inside record_all
+    unsigned long long diag_cyc = 0;   // s_memtime ticks spent inside record_all (lazy: from the flag to the end of record_all)
 #endif
     auto record_all = [&](const typename OP::Acc &acc, int blk_global, auto st_c) __attribute__((always_inline)) {
         constexpr int st = decltype(st_c)::value;
 #ifdef NNS_DIAG
         ++diag_slow;
-        const unsigned long long diag_t0 = __builtin_amdgcn_s_memtime();
+        const unsigned long long diag_t0 = LAZY ? 0ull : __builtin_amdgcn_s_memtime();   // (lazy: timed from the flag, epilogue)
 #endif
         // (the tile minimum is recomputed here, on the cold path, rather than kept live across the branch)
         const float tmv = tile_min(acc, st_c);
@@ -917,7 +929,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             if (__builtin_amdgcn_ballot_w64(t[15] <= thr[st]) != 0ull) record(st_c, t[15], jbase + 3 + 8 * 3, roomy);
         }
 #ifdef NNS_DIAG
-        diag_cyc += __builtin_amdgcn_s_memtime() - diag_t0;
+        if constexpr (!LAZY) diag_cyc += __builtin_amdgcn_s_memtime() - diag_t0;
 #endif
     };
     // ---- record form 2 (fp32 32 x 32 tiles on short ref streams): the lane's TWO BEST TILES, branch-free ---------
@@ -993,6 +1005,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     // same accumulator: rh x ql from the ring slot, rl x qh from the lo region of the image (plain
                     // loads: the wait behind them also waits for older ring DMA pieces, as the !roomy branch's does)
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(tm <= thrw[st]) != 0ull, 0)) {
+#ifdef NNS_DIAG
+                        const unsigned long long diag_f0 = __builtin_amdgcn_s_memtime();   // flag .. end of record_all
+#endif
                         const float4 *lo = reinterpret_cast<const float4 *>(a.rimg_lo) + (size_t)blk_global * (SPB * 64) + lane;
                         float4 rl[SPB];
 #pragma unroll
@@ -1009,6 +1024,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                             acc.template at<st>() = OP::mma(rl[b], bq[st][2 * b], acc.template at<st>());
                         });
                         record_all(acc, blk_global, st_c);
+#ifdef NNS_DIAG
+                        diag_cyc += __builtin_amdgcn_s_memtime() - diag_f0;
+#endif
                     }
                 } else
 #ifdef NNS_F_NOEXPECT

@@ -6,6 +6,11 @@ usage: probe_split.py ab [k ...]      per-depth A/B at 65536 x 1048576 (default 
                                       wall ms per search, keys of the two forms compared bit for bit
        probe_split.py ab lazy [k ...] the same A/B of the split operands' two schedules: lazy (the default where the library
                                       enables it) against eager (NNS_FILTER_SPLIT_EAGER); default k = 128
+       probe_split.py ab libs A.so B.so [k]
+                                      the same protocol between two BUILDS of the library (e.g. the parent commit's and
+                                      this tree's, or tools/build_variant.sh arms) at 65536 x 1048576 x k (default 128):
+                                      the builds alternate, 3 runs of 5 timed searches each, every run in a child process
+                                      of its own (NNS_LIB_PATH), keys compared through their SHA-256
        probe_split.py c3 split|f32 N  N C3 searches (65536 x 1048576 x 128) of one form (rocprofv3 / PMC runs)
        probe_split.py cluster         tight Gaussian clusters at 65536 x 1048576 x 128: exact-scan (ambiguous) and
                                       multi-candidate queries of each operand form
@@ -18,6 +23,36 @@ import time
 
 import numpy as np
 import torch
+
+
+def ab_libs(libs, k):
+    """(before the package is loaded: this process starts the children and never opens the device)"""
+    import subprocess
+    res = {lib: {"wall_ms": [], "filter_ms": []} for lib in libs}
+    sha = {}
+    for _ in range(3):
+        for lib in libs:
+            env = dict(os.environ, NNS_LIB_PATH=os.path.abspath(lib))
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "librun", str(k), "5"], env=env, check=True,
+                                 stdout=subprocess.PIPE, text=True, timeout=300).stdout
+            one = json.loads(out.strip().splitlines()[-1])
+            res[lib]["wall_ms"].append(one["wall_ms"])
+            res[lib]["filter_ms"].append(one["filter_ms"])
+            res[lib]["ambiguous"] = one["ambiguous"]
+            res[lib]["form"] = one["form"]
+            sha.setdefault(lib, set()).add(one["keys_sha256"])
+    a, b = libs
+    med = {lib: sorted(res[lib]["filter_ms"])[1] for lib in libs}
+    print(json.dumps({"probe": "ab_libs", "m": 65536, "n": 1048576, "k": k, "a": a, "b": b, "arm_a": res[a], "arm_b": res[b],
+                      "filter_ms_median": [med[a], med[b]], "filter_speedup_b_over_a": round(med[a] / med[b], 4),
+                      "keys_equal": len(sha[a] | sha[b]) == 1}), flush=True)
+
+
+if __name__ == "__main__" and sys.argv[1:3] == ["ab", "libs"]:
+    if len(sys.argv) not in (5, 6):
+        raise SystemExit("usage: probe_split.py ab libs A.so B.so [k]")
+    ab_libs(sys.argv[3:5], int(sys.argv[5]) if len(sys.argv) > 5 else 128)
+    sys.exit(0)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as graft  # noqa: E402
@@ -74,6 +109,20 @@ def ab(ks, lazy=False):
             ix.close()
         del q, r
         torch.cuda.empty_cache()
+
+
+def librun(k, steps):
+    """one run of `ab libs`: the library NNS_LIB_PATH names, default flags"""
+    import hashlib
+    q, r = uniform(M, N, k)
+    ix = pkg.Index(r, path="mfma", profile=True)
+    keys = torch.empty(M, dtype=torch.int64, device="cuda")
+    ix.search_keys(q, keys)
+    w, fm, st = timed(ix, q, keys, steps)
+    print(json.dumps({"probe": "librun", "k": k, "wall_ms": round(w, 3), "filter_ms": round(fm, 3), "ambiguous": st["ambiguous"],
+                      "form": st["filter_form"], "keys_sha256": hashlib.sha256(keys.cpu().numpy().tobytes()).hexdigest()}),
+          flush=True)
+    ix.close()
 
 
 def c3(form, steps):
@@ -153,6 +202,8 @@ if __name__ == "__main__":
             ab([int(x) for x in sys.argv[3:]] or [128], lazy=True)
         else:
             ab([int(x) for x in sys.argv[2:]] or [16, 32, 64, 128, 256])
+    elif what == "librun":
+        librun(int(sys.argv[2]), int(sys.argv[3]))
     elif what == "c3":
         c3(sys.argv[2], int(sys.argv[3]))
     elif what == "cluster":
