@@ -25,7 +25,7 @@
 // those few candidates with V0's own arithmetic: indices come out bit-identical to V0
 // although the filter itself is approximate.
 //
-// Geometry (fp32; what the bf16 instantiation does differently is described at OpBF16):
+// Geometry (fp32; what the bf16 instantiation does differently is described at OpBF16T):
 //   * MFMA A = refs (rows of the 32x32 tile), B = queries (columns): the C layout puts
 //     a query on a lane (col = lane & 31) and 16 refs in the lane's 16 accumulator
 //     registers, so the running state is per lane and needs no cross-lane traffic.
@@ -90,7 +90,7 @@ struct AccSet {
     }
 };
 
-// The same 32 registers as eight 16x16 tiles [ref tile rt][query tile qt] (OpBF16)
+// The same 32 registers as eight 16x16 tiles [ref tile rt][query tile qt] (OpBF16T)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct AccSet16 {
     f32x4 t00, t01, t02, t03, t10, t11, t12, t13;
@@ -117,40 +117,6 @@ struct AccSet16 {
     }
 };
 
-// sixteen 16x16 tiles [ref tile rt][query tile qt]: 128 queries per wave (the one-wave-per-SIMD form of OpBF16)
-struct AccSet16W {
-    f32x4 a0, a1, a2, a3, a4, a5, a6, a7, b0, b1, b2, b3, b4, b5, b6, b7;
-    template <int RT, int QT>
-    __device__ __forceinline__ f32x4 &at()
-    {
-        static_assert(RT >= 0 && RT < 2 && QT >= 0 && QT < 8, "2 ref tiles x 8 query tiles");
-        if constexpr (RT == 0) {
-            if constexpr (QT == 0) return a0;
-            else if constexpr (QT == 1) return a1;
-            else if constexpr (QT == 2) return a2;
-            else if constexpr (QT == 3) return a3;
-            else if constexpr (QT == 4) return a4;
-            else if constexpr (QT == 5) return a5;
-            else if constexpr (QT == 6) return a6;
-            else return a7;
-        } else {
-            if constexpr (QT == 0) return b0;
-            else if constexpr (QT == 1) return b1;
-            else if constexpr (QT == 2) return b2;
-            else if constexpr (QT == 3) return b3;
-            else if constexpr (QT == 4) return b4;
-            else if constexpr (QT == 5) return b5;
-            else if constexpr (QT == 6) return b6;
-            else return b7;
-        }
-    }
-    template <int RT, int QT>
-    __device__ __forceinline__ const f32x4 &at() const
-    {
-        return const_cast<AccSet16W *>(this)->template at<RT, QT>();
-    }
-};
-
 // Timing diagnostics only (results are wrong): build with -DNNS_DIAG -DNNS_FILTER_ABLATE=<bits>
 //   1 no ring sync (wait + barrier), 2 no epilogue, 16 no DMA issue.  The product build (no NNS_DIAG)
 // has none of the diagnostic switches: no ablation, no NNS_FILTER_CLOCK / NNS_DIAG_FILTER_ONLY
@@ -165,52 +131,49 @@ struct AccSet16W {
 #endif
 constexpr int kAblate = NNS_FILTER_ABLATE;
 
-constexpr int F_D = 4;                   // ring depth
-#ifndef NNS_F_DMA_AHEAD
-#define NNS_F_DMA_AHEAD 3
-#endif
-constexpr int F_DMA_AHEAD_MAX = NNS_F_DMA_AHEAD;   // (A/B builds: 2 = round 2's schedule for every operator)
-constexpr int F_SLOT_COORD = 32768;      // image bytes of one ring slot (32 fragment steps x 1 KiB)
-constexpr int F_SLOT_NORM = 2048;        // room for the slot's norms (up to 512 floats: the 16-deep tile)
-constexpr int F_SLOT_BYTES = F_SLOT_COORD + F_SLOT_NORM;
-constexpr int F_LDS_BYTES = F_D * F_SLOT_BYTES;
-
 // ---- operand traits ---------------------------------------------------------------
-// query blocks (of 32) per wave: their B operands stay resident in VGPRs (64 each).  More
+// What every operator has unless it says otherwise.
+struct OpBase {
+    static constexpr bool kSplit = false;     // split-bf16 operands of fp32 points streamed hi, lo per k-step (OpSplitT)
+    static constexpr bool kLazy = false;      // the lazy schedule of the split operands (OpLazySplitT)
+    static constexpr int kSlotSteps = 32;     // fragment steps (1 KiB each) of a ring slot
+    static constexpr int kRingDepth = 4;      // ring slots
+    static constexpr bool kDmaBurst = false;  // a slot's ring DMA pieces one per step (true: back to back, see the interval)
+    static constexpr bool kTile16 = false;    // 32x32 MFMA tiles: a lane owns one query per query block
+    // the lanes' tau constants (c0, x2 per state) stay in registers: an LDS round trip on the slow path
+    // queues behind the whole workgroup's fragment reads (measured: ~900 cycles each under this load)
+    static constexpr bool kTauInRegs = true;
+    using Acc = AccSet;
+    // waves per workgroup: 8 = two per SIMD (<= 256 VGPRs each), 4 = one per SIMD (<= 512)
+    static constexpr int kNW = 8;
+    static constexpr int kPrefetch = 2;       // fragments in flight ahead of the MFMAs
+};
+// kQB = query blocks (of 32) per wave: their B operands stay resident in VGPRs (64 each at KT = 128).  More
 // blocks = more MFMAs per LDS byte and per barrier interval, fewer waves' worth of registers.
-#ifndef NNS_F_QB_F32
-#define NNS_F_QB_F32 2
-#endif
-#ifndef NNS_F_QB_BF16
-#define NNS_F_QB_BF16 2
-#endif
-// waves per workgroup: 8 = two per SIMD (<= 256 VGPRs each), 4 = one per SIMD (<= 512)
-#ifndef NNS_F_NW_F32
-#define NNS_F_NW_F32 8
-#endif
-#ifndef NNS_F_NW_BF16
-#define NNS_F_NW_BF16 8
-#endif
+
+// The ring of an operator: kRingDepth slots of kSlotSteps 1 KiB fragments + room for the slot's norms (up to 512 floats:
+// the 16-deep tile; the lazy ring's slots never hold more than 256 refs)
+template <class OP>
+constexpr int F_D = OP::kRingDepth;
+template <class OP>
+constexpr int F_SLOT_COORD = OP::kSlotSteps * 1024;
+template <class OP>
+constexpr int F_SLOT_NORM = OP::kLazy ? 1024 : 2048;
+template <class OP>
+constexpr int F_SLOT_BYTES = F_SLOT_COORD<OP> + F_SLOT_NORM<OP>;
+template <class OP>
+constexpr int F_LDS_BYTES = F_D<OP> * F_SLOT_BYTES<OP>;
 
 template <int SPB, int QB_>
-struct OpF32T {  // fp32 operands: float4 #b = operands of MFMA k-steps 4b .. 4b+3 (8 dims per fragment)
+struct OpF32T : OpBase {  // fp32 operands: float4 #b = operands of MFMA k-steps 4b .. 4b+3 (8 dims per fragment)
     static constexpr int kSPB = SPB;          // fragment steps per 32-point image block: KT = 8 * SPB
-    static constexpr bool kTile16 = false;    // 32x32 MFMA tiles: a lane owns one query per query block
     // a slot's ring DMA pieces back to back (see the interval) — where it measured faster: KT = 128 (+0.65 % on long streams:
     // C3) and KT = 32 (+0.8 %); KT = 16 / 64 / 256 within -0.4 .. +0.1 %: one piece per step as before
     static constexpr bool kDmaBurst = SPB == 16 || SPB == 4;
     // SIMD partners half a block out of phase (+1.3 % on C3); a 2-step block (KT = 16) has no half to lag by
     static constexpr bool kLag = SPB >= 4;
-    // the lanes' tau constants (c0, x2 per state) stay in registers: an LDS round trip on the slow path
-    // queues behind the whole workgroup's fragment reads (measured: ~900 cycles each under this load)
-    static constexpr bool kTauInRegs = true;
-    using Acc = AccSet;
     static constexpr int kQB = QB_;           // 4 * SPB resident operand registers per query block
-    static constexpr int kNW = NNS_F_NW_F32;
-#ifndef NNS_F_PF
-#define NNS_F_PF 2
-#endif
-    static constexpr int kPrefetch = NNS_F_PF;   // fragments in flight ahead of the MFMAs (4 x 64 cycles each)
+    // (kPrefetch: 4 x 64 cycles per fragment)
     __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
     {
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
@@ -220,15 +183,27 @@ struct OpF32T {  // fp32 operands: float4 #b = operands of MFMA k-steps 4b .. 4b
         return acc;
     }
 };
-using OpF32 = OpF32T<16, NNS_F_QB_F32>;      // KT = 128
-using OpF32K32 = OpF32T<4, NNS_F_QB_F32>;    // KT = 32: the mid-range dimensionalities (k = 17 .. 32)
+using OpF32 = OpF32T<16, 2>;      // KT = 128
+using OpF32K32 = OpF32T<4, 2>;    // KT = 32: the mid-range dimensionalities (k = 17 .. 32)
 // KT = 16: the reference driver's own 16-D samples (main.cu:38-51) without zero padding to 32: 2 fragment
 // steps per 32-ref block, 16 blocks = 512 refs per ring slot (norms: two dwordx4 DMA pieces)
-using OpF32K16 = OpF32T<2, NNS_F_QB_F32>;
-using OpF32K64 = OpF32T<8, NNS_F_QB_F32>;    // KT = 64: 32 < k <= 64 without padding to 128
+using OpF32K16 = OpF32T<2, 2>;
+using OpF32K64 = OpF32T<8, 2>;    // KT = 64: 32 < k <= 64 without padding to 128
 // KT = 256 (128 < k <= 256): the resident operands of ONE query block already take 128 registers,
 // a ring slot holds one 32-ref block (32 KiB), and the ring turns twice as often per MFMA
 using OpF32K256 = OpF32T<32, 1>;
+
+// v_mfma_f32_32x32x16_bf16 on 16-byte fragments (8 bf16 = one operand): lane = query, 16 refs per lane — the C layout of
+// the 32x32x2 f32 form.  The compiler builtin, not OpBF16T's in-place asm: with the 32x32 tile's two 16-register
+// accumulators hipcc keeps every accumulator in one tuple (no extra copies against OpF32T, no scratch:
+// tests/test_split_filter_cpu.py), and its hazard recognizer places the wait states in front of the epilogue's reads,
+// which asm MFMAs would leave to hand-placed fences.
+struct OpMma32x16 : OpBase {
+    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    }
+};
 
 // Split-bf16 operands for fp32 points (the default for them; NNS_FILTER_F32 keeps OpF32T): every centred value v is
 // h = rn_bf16(v) plus l = rn_bf16(v - h) (v - h is exact in fp32), and x'.y' is taken as the three products
@@ -240,35 +215,21 @@ using OpF32K256 = OpF32T<32, 1>;
 // b / 2; the MFMAs of ref fragment b: hi (b even) x qh, ql; lo (b odd) x qh — 3 MFMAs x 32 cycles per k-step and
 // query block against 8 x 64 of OpF32T.
 template <int SPB, int QB_>
-struct OpSplitT {
+struct OpSplitT : OpMma32x16 {
     static constexpr int kSPB = SPB;
-    static constexpr bool kTile16 = false;
     static constexpr bool kSplit = true;
-    static constexpr bool kDmaBurst = false;  // (the bf16 operators' schedule: intervals ~5x shorter than OpF32T's)
+    // (kDmaBurst: the bf16 operators' schedule — intervals ~5x shorter than OpF32T's)
     static constexpr bool kLag = SPB >= 4;    // (the lag of half a block keeps hi / lo pairs together: SPB / 2 is even)
-    static constexpr bool kTauInRegs = true;
-    using Acc = AccSet;
     static constexpr int kQB = QB_;
-    static constexpr int kNW = NNS_F_NW_F32;
-    static constexpr int kPrefetch = NNS_F_PF;   // fragments in flight ahead of the MFMAs (2 x 32 or 4 x 32 cycles each)
-    // The compiler builtin, as OpF32T / OpBF16T32T use, not OpBF16T's in-place asm: with the 32x32 tile's two
-    // 16-register accumulators hipcc keeps every accumulator in one tuple (no extra copies against OpF32T, no
-    // scratch: tests/test_split_filter_cpu.py), and its hazard recognizer places the wait states in front of the
-    // epilogue's reads, which asm MFMAs would leave to hand-placed fences.
-    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
+    // (kPrefetch: 2 x 32 or 4 x 32 cycles per fragment)
 };
-using OpSplitK16 = OpSplitT<2, NNS_F_QB_F32>;
-using OpSplitK32 = OpSplitT<4, NNS_F_QB_F32>;
-using OpSplitK64 = OpSplitT<8, NNS_F_QB_F32>;
-using OpSplit = OpSplitT<16, NNS_F_QB_F32>;   // KT = 128: C3
+using OpSplitK16 = OpSplitT<2, 2>;
+using OpSplitK32 = OpSplitT<4, 2>;
+using OpSplitK64 = OpSplitT<8, 2>;
+using OpSplit = OpSplitT<16, 2>;   // KT = 128: C3
 using OpSplitK256 = OpSplitT<32, 1>;
 
-// bf16, KT = 256, 16 fragment steps per 32-ref block either way; two MFMA shapes:
-//
-// OpBF16 (the product): v_mfma_f32_16x16x32_bf16.  Same flops per cycle as the 32x32x16 form,
+// bf16 points at KT = 128 / 256 / 512: v_mfma_f32_16x16x32_bf16.  Same flops per cycle as the 32x32x16 form,
 // but the chip holds a ~14 % higher clock on it under this loop's load (measured here on C5:
 // in-kernel clock 2.05 vs 1.80 GHz, filter 70 vs 80 ms in the bare loop; MI355X guide, 'DVFS
 // give-back' item 7).  A step = one 1 KiB fragment (16 refs x 32 dims) x the wave's FOUR
@@ -283,39 +244,26 @@ using OpSplitK256 = OpSplitT<32, 1>;
 // not hide it, measured), which cost 7-9 % of this kernel.  Two v_min per MFMA gap fit the 8
 // issue cycles a 16x16x32 leaves free, so the reduction of tile rt's finished scores is spread
 // over k-step 1 of tile 1 - rt, and the threshold test + (rare) slow path follow at k-step 2.
-template <int SPB_, int NW_ = NNS_F_NW_BF16, bool ASM_ = true, int QB_ = 2>
-struct OpBF16T {
+template <int SPB_, int NW_ = 8, int QB_ = 2>
+struct OpBF16T : OpBase {
     static constexpr int kSPB = SPB_;         // 16: KT = 256 (8 k-steps per 16-ref tile); 8: KT = 128 (4 k-steps); 32: KT = 512
-    static constexpr bool kAsmMfma = ASM_;    // false: compiler builtins (the 512-deep form: operands beyond the 256 ArchVGPRs an asm "v" can name)
     static constexpr bool kTile16 = true;
-    static constexpr bool kDmaBurst = false;
     static constexpr bool kLag = false;       // lock-step SIMD partners (lagging them: +1..4 % time on C5)
     static constexpr bool kTauInRegs = false; // 222-234 VGPRs: the four states' constants live in LDS (read on the slow path)
-    using Acc = std::conditional_t<QB_ == 4, AccSet16W, AccSet16>;
-    static constexpr int kQB = QB_;           // 2: 64 queries per wave = 4 query tiles; 4: 128 queries = 8 tiles (one wave per SIMD)
+    using Acc = AccSet16;
+    static constexpr int kQB = QB_;           // 2: 64 queries per wave = 4 query tiles; 1: 32 queries = 2 tiles
     static constexpr int kNW = NW_;
-#ifndef NNS_F_PF_BF16
-#define NNS_F_PF_BF16 2
-#endif
-    static constexpr int kPrefetch = NNS_F_PF_BF16;
     // Inline asm, accumulating IN PLACE: through the builtin hipcc picks the three-address form
     // and rotates the eight 4-register accumulators through extra tuples (52-72 registers live
     // instead of 32), which spills the resident query operands.  The compiler does not see MFMA
     // hazards of an asm statement; the kernel keeps them by construction: an accumulator is
-    // re-used as srcC only 8 MFMAs later, and VALU reads of it (the epilogue) wait behind an
-    // the epilogue's fences (mma16_fence_lo / _hi).
+    // re-used as srcC only 8 MFMAs later, and VALU reads of it (the epilogue) wait behind
+    // the epilogue's fences (mma16_tail_fence, the sched_barriers of t16_step).
     __device__ static __forceinline__ void mma16(const float4 &a, const float4 &b, f32x4 &acc)
     {
-        if constexpr (ASM_ && QB_ == 4)   // the wave's 256 query-operand registers are the AGPR half of its file
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
-                         : "+v"(acc)
-                         : "v"(__builtin_bit_cast(f32x4, a)), "a"(__builtin_bit_cast(f32x4, b)));
-        else if constexpr (ASM_)
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
-                         : "+v"(acc)
-                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)));
-        else
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
+                     : "+v"(acc)
+                     : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)));
     }
     // First MFMA of a tile: srcC = the refs' norms (three-address form).  The accumulator is an
     // in/out operand although its old value is not read: that pins every tile to ONE register
@@ -324,16 +272,9 @@ struct OpBF16T {
     // interval's last MFMAs — a read hazard (caught by tools/check_mfma_hazards.py).
     __device__ static __forceinline__ void mma16_seed(const float4 &a, const float4 &b, f32x4 &acc, const f32x4 &c)
     {
-        if constexpr (ASM_ && QB_ == 4)
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
-                         : "+v"(acc)
-                         : "v"(__builtin_bit_cast(f32x4, a)), "a"(__builtin_bit_cast(f32x4, b)), "v"(c));
-        else if constexpr (ASM_)
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
-                         : "+v"(acc)
-                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)), "v"(c));
-        else
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
+                     : "+v"(acc)
+                     : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)), "v"(c));
     }
     // VALU may read an accumulator 8 wait states after the MFMA that wrote it issued (what hipcc
     // inserts behind the builtin: s_nop 7).  To the compiler an asm MFMA's result is ready at
@@ -341,91 +282,46 @@ struct OpBF16T {
     // __builtin_amdgcn_sched_barrier keeps them there; the kernel's tail reads right behind the
     // last MFMAs and needs the explicit wait, with the accumulators as in/out operands so that
     // the reads are ordered behind it.
-    template <class A>
-    __device__ static __forceinline__ void mma16_tail_fence(A &c)
+    __device__ static __forceinline__ void mma16_tail_fence(AccSet16 &c)
     {
-        if constexpr (ASM_ && QB_ == 4) {
-            // (volatile statements keep their order: the pins, and every read of the tiles behind them, follow the wait)
-            asm volatile("s_nop 7");
-            asm volatile("" : "+v"(c.template at<1, 0>()), "+v"(c.template at<1, 1>()), "+v"(c.template at<1, 2>()), "+v"(c.template at<1, 3>()));
-            asm volatile("" : "+v"(c.template at<1, 4>()), "+v"(c.template at<1, 5>()), "+v"(c.template at<1, 6>()), "+v"(c.template at<1, 7>()));
-        } else if constexpr (ASM_ && QB_ == 1) asm volatile("s_nop 7" : "+v"(c.t10), "+v"(c.t11));   // (two query tiles per wave)
-        else if constexpr (ASM_) asm volatile("s_nop 7" : "+v"(c.t10), "+v"(c.t11), "+v"(c.t12), "+v"(c.t13));
-        // (builtin MFMAs: hipcc's hazard recognizer places the wait states)
+        if constexpr (QB_ == 1) asm volatile("s_nop 7" : "+v"(c.t10), "+v"(c.t11));   // (two query tiles per wave)
+        else asm volatile("s_nop 7" : "+v"(c.t10), "+v"(c.t11), "+v"(c.t12), "+v"(c.t13));
     }
 };
 using OpBF16 = OpBF16T<16>;       // KT = 256
 using OpBF16K128 = OpBF16T<8>;    // KT = 128: k <= 128 without padding to 256 (half the MFMAs)
-// KT = 512 in the 16x16x32 form (round 2): the resident operands of the wave's four query tiles are 256
-// registers, so four waves per workgroup (one per SIMD) = 256 queries; a 1 KiB LDS fragment still feeds FOUR
-// MFMAs (the 32x32x16 form of OpBF16K512: one — LDS-bandwidth bound at 55 % of peak).  Compiler builtins
-// instead of inline asm: an asm "v" operand must sit in the 256 architectural VGPRs.
-#ifndef NNS_K512_NW4
-// Round 3: EIGHT waves x 32 queries (two query tiles per wave, 128 operand registers): the same 256 queries per
-// workgroup, but two waves per SIMD — a partner issues MFMAs while a wave sits in an LDS-DMA issue — and in-place asm
-// MFMAs (the four-wave form's operands spill into AGPRs and hipcc copies one back per MFMA: 70 v_accvgpr_read per 64
-// MFMAs).  A 1 KiB fragment feeds two MFMAs per wave: LDS fragment reads 32 of every 64 cycles.
-using OpBF16K512T = OpBF16T<32, 8, true, 1>;
-#else
-using OpBF16K512T = OpBF16T<32, 4, false>;
-#endif
-// KT = 256 with 128 queries per wave on four waves (experiment, -DNNS_BF16_WIDE): half the LDS fragment reads per MFMA
-using OpBF16Wide = OpBF16T<16, 4, true, 4>;
+// KT = 512: EIGHT waves x 32 queries (two query tiles per wave, 128 operand registers) = 256 queries per workgroup, two
+// waves per SIMD — a partner issues MFMAs while a wave sits in an LDS-DMA issue.  A 1 KiB fragment feeds two MFMAs per
+// wave: LDS fragment reads 32 of every 64 cycles.
+using OpBF16K512T = OpBF16T<32, 8, 1>;
 
-
-// OpBF16T32: v_mfma_f32_32x32x16_bf16 (the first version; kept for A/B builds with
-// -DNNS_BF16_TILE32): 16 bytes = 8 bf16 = one operand, lane = query, 16 refs per lane.
-template <int SPB_, int QB_, int NW_ = NNS_F_NW_BF16, bool LAG_ = (NW_ == 8)>
-struct OpBF16T32T {
+// The deep bf16 tiles whose blocks do not divide a ring slot (KT 384, 640, 768, 1024) run v_mfma_f32_32x32x16_bf16 with
+// ONE query block per wave.
+template <int SPB_, int QB_, int NW_ = 8, bool LAG_ = (NW_ == 8)>
+struct OpBF16T32T : OpMma32x16 {
     static constexpr int kSPB = SPB_;         // fragment steps (16 dims each) per 32-ref block
-    static constexpr bool kTile16 = false;
-    static constexpr bool kDmaBurst = false;
     static constexpr bool kLag = LAG_;        // (one wave per SIMD has no partner to stagger against)
-    static constexpr bool kTauInRegs = true;
-    using Acc = AccSet;
     static constexpr int kQB = QB_;
     static constexpr int kNW = NW_;
-    static constexpr int kPrefetch = NNS_F_PF_BF16;   // one MFMA (32 cycles) per fragment and query block
-    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                       __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
+    // (kPrefetch: one MFMA (32 cycles) per fragment and query block)
 };
-using OpBF16T32 = OpBF16T32T<16, NNS_F_QB_BF16>;   // KT = 256
-// KT = 512 (256 < k <= 512): the 32x32x16 form with ONE query block per wave (its resident operands are
-// 128 registers) and one 32-ref block per ring slot — the bf16 twin of OpF32K256
-using OpBF16K512 = OpBF16T32T<32, 1>;
 // KT = 1024 (512 < k <= 1024): K-split accumulation.  The resident operands of one query block are 256
 // registers, so a workgroup is FOUR waves (one per SIMD, up to 512 registers each) = 128 queries; a 32-ref
 // block is 64 fragment steps = TWO ring slots, and its accumulators carry across the slot barrier: seeded at
-// step 0 of the even slot, retired at step 31 of the odd one.  One MFMA per 1 KiB LDS fragment, like the
-// 512-deep tile: LDS-bandwidth bound (~50 % of the bf16 MFMA peak), still ~50x the exact VALU scan.
+// step 0 of the even slot, retired at step 31 of the odd one.  One MFMA per 1 KiB LDS fragment:
+// LDS-bandwidth bound (~50 % of the bf16 MFMA peak), still ~50x the exact VALU scan.
 using OpBF16K1024 = OpBF16T32T<64, 1, 4>;
-// KT = 768 (512 < k <= 768; round 3): 48 fragment steps per block — two blocks over three ring slots.  The resident
+// KT = 768 (512 < k <= 768): 48 fragment steps per block — two blocks over three ring slots.  The resident
 // operands of one query block are 192 registers, so — unlike at 1024 — TWO waves per SIMD fit (<= 256 registers
 // each): eight waves = 256 queries per workgroup, and a SIMD partner covers a wave's LDS-DMA issue stalls (the
 // one-wave-per-SIMD tiles lose about half their MFMA slots to them: profiles/r03_deep_ablate.txt).  Lock-step
 // partners (a half-block lag would straddle slots).
-#ifndef NNS_F_NW_K768
-#define NNS_F_NW_K768 8
-#endif
-using OpBF16K768 = OpBF16T32T<48, 1, NNS_F_NW_K768, false>;
+using OpBF16K768 = OpBF16T32T<48, 1, 8, false>;
 // KT = 640 (512 < k <= 640): 40 fragment steps per block — FOUR blocks over FIVE ring slots; 160 operand registers, eight waves
 using OpBF16K640 = OpBF16T32T<40, 1, 8, false>;
-// KT = 384 (256 < k <= 384, round 3): the same form below 512 — 24 steps per block, four blocks over three slots, 96 operand
+// KT = 384 (256 < k <= 384): the same form below 512 — 24 steps per block, four blocks over three slots, 96 operand
 // registers; k = 300 ran on the 512-deep tile at 36 % of peak
 using OpBF16K384 = OpBF16T32T<24, 1, 8, false>;
-#if defined(NNS_BF16_WIDE)
-using OpBF16Active = OpBF16Wide;
-using OpBF16K512Active = OpBF16K512T;
-#elif NNS_BF16_TILE16
-using OpBF16Active = OpBF16;
-using OpBF16K512Active = OpBF16K512T;
-#else
-using OpBF16Active = OpBF16T32;
-using OpBF16K512Active = OpBF16K512;
-#endif
 
 // Lazy split ("lazy split"): the split operands in a schedule that runs the two cross products only where the result
 // needs them.  The kernel uses a score to ask "is the minimum of this 32 x 32 tile within the lane's threshold?"; the
@@ -438,44 +334,15 @@ using OpBF16K512Active = OpBF16K512;
 // the ring eight slots deep (an interval is a third of the eager one, the DMA latency is not).
 // kSPB = HI fragments per block (KT / 16); the resident query operands are the eager ones (qh, ql per k-step).
 template <int SPB, int QB_>
-struct OpLazySplitT {
+struct OpLazySplitT : OpMma32x16 {
     static constexpr int kSPB = SPB;
     static constexpr int kSlotSteps = 16;
     static constexpr int kRingDepth = 8;
-    static constexpr bool kLazy = true;
-    static constexpr bool kTile16 = false;
-    static constexpr bool kDmaBurst = false;
+    static constexpr bool kLazy = true;       // (kSplit stays false: that is the eager stream of hi AND lo fragments)
     static constexpr bool kLag = SPB >= 4;
-    static constexpr bool kTauInRegs = true;
-    using Acc = AccSet;
     static constexpr int kQB = QB_;
-    static constexpr int kNW = NNS_F_NW_F32;
-    static constexpr int kPrefetch = NNS_F_PF;
-    __device__ static __forceinline__ f32x16 mma(const float4 &a, const float4 &b, f32x16 acc)
-    {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
 };
-using OpLazySplit = OpLazySplitT<8, NNS_F_QB_F32>;   // KT = 128: C3
-
-template <class OP, class = void>
-struct is_lazy_op : std::false_type {};
-template <class OP>
-struct is_lazy_op<OP, std::void_t<decltype(OP::kLazy)>> : std::bool_constant<OP::kLazy> {};
-// fragment steps of a ring slot, ring depth: 32 and F_D unless the operator says otherwise
-template <class OP, class = void>
-struct slot_steps : std::integral_constant<int, 32> {};
-template <class OP>
-struct slot_steps<OP, std::void_t<decltype(OP::kSlotSteps)>> : std::integral_constant<int, OP::kSlotSteps> {};
-template <class OP, class = void>
-struct ring_depth : std::integral_constant<int, 4> {};
-template <class OP>
-struct ring_depth<OP, std::void_t<decltype(OP::kRingDepth)>> : std::integral_constant<int, OP::kRingDepth> {};
-
-template <class OP, class = void>
-struct is_split_op : std::false_type {};
-template <class OP>
-struct is_split_op<OP, std::void_t<decltype(OP::kSplit)>> : std::bool_constant<OP::kSplit> {};
+using OpLazySplit = OpLazySplitT<8, 2>;   // KT = 128: C3
 
 // min over the lanes that carry the same query: l ^ 32 (32x32 tiles), and l ^ 16 too (16x16 tiles).  Row
 // swaps (v_permlane32_swap / v_permlane16_swap, gfx950), not ds_bpermute: no LDS round trip on the slow
@@ -531,14 +398,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // (24 steps, 384-deep: 3 slots = 4 blocks.)  "Deep" = the block does not divide the slot.
     // The lazy split operator streams hi fragments only: its slots are SPS = 16 steps in a ring of 8 (see OpLazySplitT);
     // everywhere else SPS = 32, F_D = 4.
-    constexpr bool LAZY = is_lazy_op<OP>::value;
-    constexpr int SPS = slot_steps<OP>::value;
-    constexpr int F_D = ring_depth<OP>::value;
-    constexpr int F_SLOT_COORD = SPS * 1024;           // image bytes of one ring slot
-    constexpr int F_SLOT_NORM = LAZY ? 1024 : nns::F_SLOT_NORM;
-    constexpr int F_SLOT_BYTES = F_SLOT_COORD + F_SLOT_NORM;
-    constexpr int F_LDS_BYTES = F_D * F_SLOT_BYTES;
-    static_assert(F_LDS_BYTES == nns::F_LDS_BYTES, "every operator's ring takes the same LDS (launch_filter_t)");
+    constexpr bool LAZY = OP::kLazy;
+    constexpr int SPS = OP::kSlotSteps;
+    static_assert(F_LDS_BYTES<OP> == 4 * (32768 + 2048), "every operator's ring takes the same LDS: one workgroup per CU");
     constexpr bool DEEP = SPS % SPB != 0;
     static_assert(SPS == 32 || !DEEP, "blocks straddling slots: 32-step slots only");
     constexpr int SUP_SLOTS = DEEP ? SPB / SUP_GCD : 1;
@@ -547,14 +409,14 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     constexpr int BPS = DEEP ? 1 : SPS / SPB;          // image blocks per ring slot (shallow tiles)
     constexpr int BLK_BYTES = SPB * 1024;
     constexpr int SLOT_REFS = 32 * SUP_BLKS;           // norms DMAed with a slot
-    constexpr int F_PPW = F_SLOT_COORD / 1024 / F_NW;   // 1 KiB DMA pieces per wave per slot
+    constexpr int F_PPW = F_SLOT_COORD<OP> / 1024 / F_NW;   // 1 KiB DMA pieces per wave per slot
     static_assert((SPS % SPB == 0 && SPB >= 2) || SPB == 64 || SPB == 48 || SPB == 40 || SPB == 24, "a slot is SPS fragment steps");
     static_assert(SUP_SLOTS * SPS == SUP_BLKS * SPB, "a super-period is whole slots and whole blocks");
     static_assert(SPBLK == 1 || (!OP::kLag && !OP::kTile16), "blocks straddling slots: lock-step 32x32 tiles only");
     static_assert(SLOT_REFS == 32 || SLOT_REFS == 64 || SLOT_REFS == 128 || SLOT_REFS == 256 || SLOT_REFS == 512,
                   "norm pieces: one dword per lane, or dwordx4 pieces of 256 norms");
     constexpr int F_NP = SLOT_REFS <= 256 ? 1 : SLOT_REFS / 256;   // norm DMA pieces per slot
-    static_assert(SLOT_REFS * 4 <= F_SLOT_NORM, "norm room of a ring slot");
+    static_assert(SLOT_REFS * 4 <= F_SLOT_NORM<OP>, "norm room of a ring slot");
     // How far ahead of its interval a slot's DMA is issued.  Lagging SIMD partners still read slot s - 1 during
     // the first half of interval s, so with four ring slots they can fill slot s + 2 at most: ONE interval between
     // issue and deadline — plenty when an interval is 16 000 cycles (fp32 tiles), not when it is 1 000 - 4 000
@@ -572,22 +434,19 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #define NNS_F_LAZY_SHARE 1
 #endif
     constexpr bool kLazyShare = NNS_F_LAZY_SHARE != 0;
-    constexpr int AHEAD = LAZY ? NNS_F_LAZY_AHEAD : (OP::kLag || F_DMA_AHEAD_MAX < 3) ? 2 : 3;
-    static_assert(AHEAD >= 2 && AHEAD <= F_D - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
-#ifndef NNS_F_NORM_ONE
-#define NNS_F_NORM_ONE 1
-#endif
+    constexpr int AHEAD = LAZY ? NNS_F_LAZY_AHEAD : OP::kLag ? 2 : 3;
+    static_assert(AHEAD >= 2 && AHEAD <= F_D<OP> - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
     // DMA pieces per wave and slot that the counted vmcnt waits may leave in flight: with the norms issued by one wave
     // per slot, a wave's youngest slot has F_PPW or F_PPW + F_NP pieces — counting F_PPW is safe for both
     // (not the 768-deep tile: 252 of its 256 registers are taken, the turn-taking test spills)
-    constexpr bool NORM_ONE = NNS_F_NORM_ONE && SPB != 48;
+    constexpr bool NORM_ONE = SPB != 48;
     constexpr int F_PPS = NORM_ONE ? F_PPW : F_PPW + F_NP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5;
     constexpr int QB = OP::kQB;
-    static_assert(QB <= 2 || OP::kTile16, "the 32x32 accumulator sets hold two query blocks");
+    static_assert(QB <= 2, "the accumulator sets hold two query blocks");
     const int qblk0 = (blockIdx.x * F_NW + wave) * QB;
     // Lane STATES: the running minimum / threshold / candidate list a lane keeps per query it
     // carries.  32x32 tiles: one query per query block (state = block, 16 scores per ref block);
@@ -627,17 +486,14 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     for (int st = 0; st < NS; ++st) {
 #pragma unroll
         for (int b = 0; b < NBQ; ++b)
-            if constexpr (T16 && QB > 2)   // (AGPR-resident operands: see OpBF16T::mma16)
-                asm volatile("" : "+a"(bq[st][b].x), "+a"(bq[st][b].y), "+a"(bq[st][b].z), "+a"(bq[st][b].w));
-            else
-                asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
+            asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
         asm volatile("" : "+v"(tc[st].c0), "+v"(tc[st].c1), "+v"(tc[st].x2));
         if constexpr (LAZY) asm volatile("" : "+v"(bnd[st]));
     }
     // The tau constants of the lane's states live in LDS behind the ring (2 KiB per wave, read only on
     // the slow path) instead of 3 registers per state; c1 depends on the tile depth alone and is
     // wave-uniform
-    float *tcl = reinterpret_cast<float *>(smem + F_LDS_BYTES) + wave * (NS > 4 ? 1024 : 512) + lane;
+    float *tcl = reinterpret_cast<float *>(smem + F_LDS_BYTES<OP>) + wave * 512 + lane;
     if constexpr (!OP::kTauInRegs) {
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
@@ -663,10 +519,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // (relative to slot0) into ring position s % F_D
     auto issue_piece = [&](int s, int p) __attribute__((always_inline)) {
         const size_t gslot = (size_t)(slot0 + s);
-        const unsigned dst = lds_base + (s & (F_D - 1)) * F_SLOT_BYTES;
+        const unsigned dst = lds_base + (s & (F_D<OP> - 1)) * F_SLOT_BYTES<OP>;
         if (p < F_PPW) {
             const int piece = wave * F_PPW + p;
-            if constexpr (is_split_op<OP>::value) {
+            if constexpr (OP::kSplit) {
                 if (a.rimg_lo) {
                     // an eager kernel on the lazy image (the short-stream record forms of an index whose long streams run
                     // the lazy kernel): LDS fragment `piece` = block piece / SPB, k-step (piece % SPB) / 2, hi (even) or lo
@@ -676,7 +532,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     return;
                 }
             }
-            dma16(a.rimg + gslot * F_SLOT_COORD + piece * 1024 + lane * 16, dst + piece * 1024);
+            dma16(a.rimg + gslot * F_SLOT_COORD<OP> + piece * 1024 + lane * 16, dst + piece * 1024);
         } else if (NORM_ONE && ((int)gslot & (F_NW - 1)) != wave) {
             // the slot's norms are ONE wave's business, the waves taking turns slot by slot (round 1 - 3: every wave copied
             // the same bytes to the same words, to keep the DMA counts per slot identical — eight pieces where one does,
@@ -684,10 +540,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             // below therefore count IMAGE pieces only (a wave whose youngest slot carries norm pieces waits for them too)
         } else if constexpr (SLOT_REFS <= 64) {   // (128- and 256-ref slots: one dwordx4 piece of 256 norms)
             // (a 32-ref slot also copies the next slot's 32)
-            dma4(a.rnorm + (gslot / SPBLK) * SLOT_REFS + lane, dst + F_SLOT_COORD);   // (a deep block: both its slots)
+            dma4(a.rnorm + (gslot / SPBLK) * SLOT_REFS + lane, dst + F_SLOT_COORD<OP>);   // (a deep block: both its slots)
         } else {
             const int np = p - F_PPW;             // 256 norms per piece (a deep block: its super-period's, + over-read)
-            dma16(a.rnorm + (gslot / SPBLK) * SLOT_REFS + np * 256 + lane * 4, dst + F_SLOT_COORD + np * 1024);
+            dma16(a.rnorm + (gslot / SPBLK) * SLOT_REFS + np * 256 + lane * 4, dst + F_SLOT_COORD<OP> + np * 1024);
         }
     };
     auto issue = [&](int s) __attribute__((always_inline)) {
@@ -729,7 +585,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         if constexpr (T16) {
             return;   // (16x16 tiles: seed16 below)
         } else {
-        const float *nrm = reinterpret_cast<const float *>(slot + F_SLOT_COORD) + blk * 32 + 4 * h;
+        const float *nrm = reinterpret_cast<const float *>(slot + F_SLOT_COORD<OP>) + blk * 32 + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 nv = *reinterpret_cast<const float4 *>(nrm + 8 * g);
@@ -747,16 +603,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // Shallow lock-step tiles (KT = 16: a tile is two steps, and both SIMD partners reach their tile boundaries
     // together): the NEXT tile's norms are read a whole tile ahead into 16 registers, so the tile's first MFMA does not
     // wait for an LDS round trip every 8 MFMAs (at the deeper tiles the lagging partner's MFMA chain covers it).
-#ifndef NNS_F_SEED_AHEAD
-#define NNS_F_SEED_AHEAD 1
-#endif
-    constexpr bool kSeedAhead = NNS_F_SEED_AHEAD && !T16 && !OP::kLag && SPB <= 4;
+    constexpr bool kSeedAhead = !T16 && !OP::kLag && SPB <= 4;
     float4 nsd[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) nsd[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     auto seed_fetch = [&](const char *slot, int blk) __attribute__((always_inline)) {
         if constexpr (kSeedAhead) {
-            const float *nrm = reinterpret_cast<const float *>(slot + F_SLOT_COORD) + blk * 32 + 4 * h;
+            const float *nrm = reinterpret_cast<const float *>(slot + F_SLOT_COORD<OP>) + blk * 32 + 4 * h;
 #pragma unroll
             for (int g = 0; g < 4; ++g) nsd[g] = *reinterpret_cast<const float4 *>(nrm + 8 * g);
         }
@@ -779,7 +632,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // two steps ahead of the tile's first MFMAs, which take them as srcC (no register copies)
     auto seed16 = [&](const char *slot, int blk, auto rt_c) __attribute__((always_inline)) {
         constexpr int rt = decltype(rt_c)::value;
-        const float4 nv = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(slot + F_SLOT_COORD) +
+        const float4 nv = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(slot + F_SLOT_COORD<OP>) +
                                                             blk * 32 + 16 * rt + 4 * (lane >> 4));
         if constexpr (rt == 0) nseed0 = f32x4{nv.x, nv.y, nv.z, nv.w};
         else nseed1 = f32x4{nv.x, nv.y, nv.z, nv.w};
@@ -1029,11 +882,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #endif
                     }
                 } else
-#ifdef NNS_F_NOEXPECT
-                if (__builtin_amdgcn_ballot_w64(tm <= thr[st]) != 0ull)   // rare: ~ln(n) tiles per lane
-#else
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(tm <= thr[st]) != 0ull, 0))   // rare: ~ln(n) tiles per lane
-#endif
                     record_all(acc, blk_global, st_c);
             });
         }
@@ -1049,7 +898,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     constexpr int qb = decltype(qc)::value;
                     acc.template at<qb>() = OP::mma(frag, bq[qb][2 * b], acc.template at<qb>());
                 });
-            } else if constexpr (is_split_op<OP>::value) {
+            } else if constexpr (OP::kSplit) {
                 // ref hi fragment x (qh, ql) of the k-step; ref lo fragment x qh
                 static_for<QB>([&](auto qc) __attribute__((always_inline)) {
                     constexpr int qb = decltype(qc)::value;
@@ -1134,7 +983,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     // separate registers (8 v_mov at the latch, 8 more to put them back in front of the tile's
                     // seed MFMA, whose in/out constraint "reads" them): 16 of the 74 VALU instructions of an
                     // interval, in a loop where every VALU issue cycle is an MFMA issue cycle lost.
-                    if constexpr (OP::kAsmMfma) asm volatile("" : "+v"(acc.template at<ot, qt>()));
+                    asm volatile("" : "+v"(acc.template at<ot, qt>()));
                     const f32x4 o = acc.template at<ot, qt>();
                     if constexpr ((kAblate & 2) != 0) asm volatile("" ::"v"(o));
                     else tmh[qt] = fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]);
@@ -1205,30 +1054,17 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             // for the two SIMD partners (an LDS-DMA issue stalls the issuing wave ~100 cycles;
             // past the end of the shard it reads the image's padding)
             if constexpr ((kAblate & 16) == 0) {
-#ifdef NNS_F_DMA_SAMEPHASE
-                constexpr int d0 = 2;
-#else
                 constexpr int d0 = DPH == 0 ? 2 : SPS / 2;
-#endif
-#ifdef NNS_F_DMA_SP
-                constexpr int sp = NNS_F_DMA_SP;
-#else
                 // steps between pieces: two where they fit — except K4's 256-deep 16x16x32 form, whose pieces go out on consecutive
                 // steps (same-device A/B on C5: 78.2 -> 77.5 ms, +0.9 %; the 512- / 384-deep tiles lose 1 % that way, three steps
                 // apart loses everywhere: profiles/r03_ab_dma_burst.txt)
-                constexpr int sp = (T16 && SPB == 16 && QB == 2) ? 1 : ((F_PPW + F_NP) * 2 <= 14 ? 2 : 1);
-#endif
+                constexpr int sp = (T16 && SPB == 16) ? 1 : ((F_PPW + F_NP) * 2 <= 14 ? 2 : 1);
                 static_assert(d0 + sp * (F_PPW + F_NP) <= SPS, "DMA pieces must fit the interval");
                 // fp32 operators issue a slot's pieces BACK TO BACK at one step (round 3, second session): a lone LDS-DMA piece
                 // costs its SIMD ~130 cycles of MFMA issue, a burst of them far less per piece (tools/ubench/chain_loop.hip:
                 // 36.8 -> 25.2 ms); C3 118.3 -> 117.6 ms (OP::kDmaBurst: by tile depth).  The bf16 operators keep one piece per step: bursts cost THEM 1 - 6 %
                 // (profiles/r03_ab_dma_burst.txt) — their intervals are 8 - 16x shorter and a burst stalls the lock-step partner too.
-#ifdef NNS_F_DMA_BURST
-                constexpr bool BURST = NNS_F_DMA_BURST != 0;
-#else
-                constexpr bool BURST = OP::kDmaBurst;
-#endif
-                if constexpr (BURST) {
+                if constexpr (OP::kDmaBurst) {
                     if constexpr (t == d0) issue(s + AHEAD);
                 } else if constexpr (t >= d0 && t < d0 + sp * (F_PPW + F_NP) && (t - d0) % sp == 0) {
                     issue_piece(s + AHEAD, (t - d0) / sp);
@@ -1267,9 +1103,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     }
                 }
             }
-#ifndef NNS_F_NOSCHED
             __builtin_amdgcn_sched_barrier(0);
-#endif
         });
     };
 
@@ -1281,8 +1115,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #else
     const bool lag = OP::kLag && half;
 #endif
-    auto ring = [&](int s) __attribute__((always_inline)) { return smem + ((s + F_D) & (F_D - 1)) * F_SLOT_BYTES; };
-    static_assert((F_D & (F_D - 1)) == 0, "ring depth must be a power of two");
+    auto ring = [&](int s) __attribute__((always_inline)) { return smem + ((s + F_D<OP>) & (F_D<OP> - 1)) * F_SLOT_BYTES<OP>; };
+    static_assert((F_D<OP> & (F_D<OP> - 1)) == 0, "ring depth must be a power of two");
 
     // prologue: slots 0 .. AHEAD - 1 in flight; confirm slot 0; start interval 0's first fragments
     static_for<AHEAD>([&](auto s_c) __attribute__((always_inline)) { issue(decltype(s_c)::value); });
@@ -1520,7 +1354,7 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
         }
     } else {
         // bf16 == 2: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
-        // the operand / result lane mapping the filter's OpBF16 and K2's order 1 image assume
+        // the operand / result lane mapping the filter's OpBF16T and K2's order 1 image assume
         const int c = lane & 15, g = lane >> 4;
         for (int rt = 0; rt < 2; ++rt)
             for (int qt = 0; qt < 2; ++qt) {
@@ -1590,6 +1424,44 @@ constexpr bool lazy_depth(int kt)
     return kt == 128;
 }
 
+// The one depth-to-operator table: f(OP{}) for the operator that runs geometry g — (bf16, split, lazy, kt).  The kt
+// ladder of filter_plan produces exactly the depths listed here.
+template <class F>
+static int with_filter_op(const FilterGeom &g, F &&f)
+{
+    if (g.bf16) {
+        switch (g.kt) {
+        case 128: return f(OpBF16K128{});
+        case 256: return f(OpBF16{});
+        case 384: return f(OpBF16K384{});
+        case 512: return f(OpBF16K512T{});
+        case 640: return f(OpBF16K640{});
+        case 768: return f(OpBF16K768{});
+        case 1024: return f(OpBF16K1024{});
+        }
+    } else if (g.lazy) {
+        if (g.kt == 128) return f(OpLazySplit{});
+    } else if (g.split) {
+        switch (g.kt) {
+        case 16: return f(OpSplitK16{});
+        case 32: return f(OpSplitK32{});
+        case 64: return f(OpSplitK64{});
+        case 128: return f(OpSplit{});
+        case 256: return f(OpSplitK256{});
+        }
+    } else {
+        switch (g.kt) {
+        case 16: return f(OpF32K16{});
+        case 32: return f(OpF32K32{});
+        case 64: return f(OpF32K64{});
+        case 128: return f(OpF32{});
+        case 256: return f(OpF32K256{});
+        }
+    }
+    set_error("MFMA filter: no operator for kt = %d (bf16 %d, split %d, lazy %d)", g.kt, g.bf16, g.split, g.lazy);
+    return NNS_ERR_UNSUPPORTED;
+}
+
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
@@ -1598,7 +1470,7 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
         if (k <= 128) kt = 128;        // OpBF16K128: 4 k-steps per 16-ref tile, 4 blocks per slot
         else if (k <= 256) kt = 256;
         else if (k <= 384) kt = 384;   // OpBF16K384: four 24-step blocks over three ring slots
-        else if (k <= 512) kt = 512;   // OpBF16K512
+        else if (k <= 512) kt = 512;   // OpBF16K512T
         else if (k <= 640) kt = 640;   // OpBF16K640: four 40-step blocks over five ring slots
         else if (k <= 768) kt = 768;   // OpBF16K768: two 48-step blocks over three ring slots
         else if (k <= 1024) kt = 1024; // OpBF16K1024: K-split accumulation over two ring slots per block
@@ -1618,15 +1490,13 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
     g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;
     g->kt = kt;
-    g->lpq = (bf16 && kt <= 512 && kt != 384 && OpBF16Active::kTile16) ? 4 : 2;
+    // (the schedule is chosen at the end, from the stream length that the query groups fix: the lazy operator has its
+    //  eager twin's tiles and workgroup)
+    static_assert(OpLazySplit::kQB * OpLazySplit::kNW == OpSplit::kQB * OpSplit::kNW, "lazy and eager split: same query groups");
+    g->lazy = g->lazy_img = 0;
+    g->lpq = with_filter_op(*g, [](auto op) { return decltype(op)::kTile16 ? 4 : 2; });
     // queries per workgroup
-    const int qw = 32 * (bf16 ? (kt == 1024  ? OpBF16K1024::kQB * OpBF16K1024::kNW
-                              : kt == 768 ? OpBF16K768::kQB * OpBF16K768::kNW
-                              : kt == 640 ? OpBF16K640::kQB * OpBF16K640::kNW
-                              : kt == 384 ? OpBF16K384::kQB * OpBF16K384::kNW
-                              : kt == 512 ? OpBF16K512Active::kQB * OpBF16K512Active::kNW
-                                          : OpBF16Active::kQB * OpBF16Active::kNW)
-                              : (kt == 256 ? OpF32K256::kQB * OpF32K256::kNW : OpF32::kQB * OpF32::kNW));
+    const int qw = with_filter_op(*g, [](auto op) { return 32 * decltype(op)::kQB * decltype(op)::kNW; });
     g->m_pad = divup(m, qw) * qw;
     // refs per ring slot (32 fragment steps of 8 fp32 / 16 bf16 dims)
     const int steps_per_block = bf16 ? kt / 16 : kt / 8;
@@ -1687,15 +1557,6 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     // eager kernel — reading the same image — on the short-stream record forms, where nearly every tile refines anyway.
     g->lazy_img = (g->split && lazy_depth(kt) && !split_eager) ? 1 : 0;
     g->lazy = (g->lazy_img && g->tile_rec == 0) ? 1 : 0;
-#ifdef NNS_F_NOTOP2
-    if (g->tile_rec == 2) g->tile_rec = 1;
-#endif
-#ifdef NNS_F_NOSHARE   // (A/B builds)
-    g->share_thr = 0;
-#endif
-#ifdef NNS_F_NOTILEREC
-    g->tile_rec = 0;
-#endif
     return NNS_OK;
 }
 
@@ -1703,12 +1564,12 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (is_lazy_op<OP>::value) return filter_lazy_kernel<OP>;
-        else if constexpr (is_split_op<OP>::value) return filter_split_kernel<OP>;
+        if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
+        else if constexpr (OP::kSplit) return filter_split_kernel<OP>;
         else return filter_kernel<OP>;
     }();
     // + 2 KiB per wave for the lanes' tau constants
-    constexpr int lds_bytes = F_LDS_BYTES + OP::kNW * ((OP::kTile16 && OP::kQB > 2) ? 4096 : 2048);
+    constexpr int lds_bytes = F_LDS_BYTES<OP> + OP::kNW * 2048;
     // > 64 KiB of dynamic LDS needs the opt-in, once per device
     static std::atomic<bool> attr_set[64];   // (two threads racing here both set it: harmless)
     int dev = 0;
@@ -1751,24 +1612,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
         NNS_HIP(hipMemsetAsync(a.stamps, 0, (nwg * 4 + 8) * sizeof(unsigned long long), st));
     }
 #endif
-    const int rc = g.bf16 ? (g.kt == 128    ? launch_filter_t<OpBF16K128>(g, a, st)
-                             : g.kt == 512  ? launch_filter_t<OpBF16K512Active>(g, a, st)
-                             : g.kt == 1024 ? launch_filter_t<OpBF16K1024>(g, a, st)
-                             : g.kt == 768  ? launch_filter_t<OpBF16K768>(g, a, st)
-                             : g.kt == 640  ? launch_filter_t<OpBF16K640>(g, a, st)
-                             : g.kt == 384  ? launch_filter_t<OpBF16K384>(g, a, st)
-                                           : launch_filter_t<OpBF16Active>(g, a, st))
-                          : g.lazy ? launch_filter_t<OpLazySplit>(g, a, st)
-                          : g.split ? (g.kt == 16    ? launch_filter_t<OpSplitK16>(g, a, st)
-                                       : g.kt == 32  ? launch_filter_t<OpSplitK32>(g, a, st)
-                                       : g.kt == 64  ? launch_filter_t<OpSplitK64>(g, a, st)
-                                       : g.kt == 256 ? launch_filter_t<OpSplitK256>(g, a, st)
-                                                     : launch_filter_t<OpSplit>(g, a, st))
-                          : (g.kt == 16    ? launch_filter_t<OpF32K16>(g, a, st)
-                             : g.kt == 32  ? launch_filter_t<OpF32K32>(g, a, st)
-                             : g.kt == 64  ? launch_filter_t<OpF32K64>(g, a, st)
-                             : g.kt == 256 ? launch_filter_t<OpF32K256>(g, a, st)
-                                           : launch_filter_t<OpF32>(g, a, st));
+    const int rc = with_filter_op(g, [&](auto op) { return launch_filter_t<decltype(op)>(g, a, st); });
 #ifdef NNS_DIAG
     if (a.stamps) {   // diagnostic: synchronous read-out, median clock over workgroups
         std::vector<unsigned long long> h(nwg * 4 + 8);

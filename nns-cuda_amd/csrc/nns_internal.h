@@ -261,12 +261,10 @@ __device__ __forceinline__ void dma4(const void *g, unsigned lds_byte)
 // (v_mfma_f32_32x32x2_f32: lane supplies A[i = lane&31][k = lane>>5]).
 constexpr int kBlockPts = 32;
 
-// bf16 filter MFMA shape: 1 = v_mfma_f32_16x16x32_bf16 (the product: the chip clocks ~14 % higher
-// on it under load), 0 = v_mfma_f32_32x32x16_bf16 (A/B builds).  Fixes the bf16 tile-image order
-// (prep_kernels.hip) and the lanes a query's candidate lists live on (finalize.hip).
-#ifndef NNS_BF16_TILE16
-#define NNS_BF16_TILE16 1
-#endif
+// The bf16 filter at KT 128 / 256 / 512 runs v_mfma_f32_16x16x32_bf16 on 16x16 tiles (the chip clocks ~14 % higher on
+// it under load than on the 32x32x16 form).  That fixes the bf16 tile-image order, 1 (prep_kernels.hip), and the four
+// lanes a query's candidate lists live on (FilterGeom.lpq, finalize.hip).
+constexpr int kBf16ImageOrder = 1;
 
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)

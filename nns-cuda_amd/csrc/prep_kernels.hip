@@ -525,7 +525,7 @@ int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, c
             hipLaunchKernelGGL((image_deep_kernel<1024, float>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale,
                                pad_norm, (uint16_t *)img, norms, max_norm_bits, maxabs_bits);
         else if (kt == 512)
-            hipLaunchKernelGGL(image_mixed512_kernel, dim3(blocks), dim3(256), 0, st, NNS_BF16_TILE16 ? 1 : 0, k, npts, pts, mean,
+            hipLaunchKernelGGL(image_mixed512_kernel, dim3(blocks), dim3(256), 0, st, kBf16ImageOrder, k, npts, pts, mean,
                                scale, pad_norm, (uint16_t *)img, norms, max_norm_bits, maxabs_bits);
         else if (kt == 256)
             hipLaunchKernelGGL((image_kernel<256, 1>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale,
