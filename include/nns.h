@@ -116,6 +116,13 @@ enum {
                           * tiles whose hi-hi minimum is within B of the lane's threshold).  Same candidate lists' meaning,
                           * same indices and distances; for A/B runs, tests, and data so tightly clustered that most tiles
                           * refine.  NNS_ERR_INVALID with bf16 points, NNS_FILTER_BF16 or NNS_FILTER_F32 */
+    NNS_RANGE_MFMA = 4096, /* range search through the MFMA flag pass (K7m): nns_index_create builds the split-bf16 ref image
+                          * and norms whatever the path bits say (the 1-NN path stays what they say), and
+                          * nns_index_range_count / _fill flag, per query, the 32-ref blocks whose split-bf16 score lies
+                          * within a per-query threshold, then evaluate V0's distance only there.  Same lims, indices and
+                          * distance bits as without the flag.  fp32 points whose filter form is the split one, 8 <= k <=
+                          * 256; with bf16 points, NNS_FILTER_F32, NNS_FILTER_BF16 or another k: NNS_ERR_UNSUPPORTED.  Also
+                          * accepted by nns_search_f32_range */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -324,7 +331,8 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 /* Whole calls: count, read lims[m], allocate, fill.  lims_out: the caller's host int64[m + 1].  *idx_out (and
  * *dist_out when dist_out != NULL) are malloc()'d by the library with lims[m] entries, never NULL on success; the
  * caller free()s them.  On error both are set to NULL and nothing leaks; output beyond device or host memory gives
- * NNS_ERR_NOMEM.  flags: NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE; any other: NNS_ERR_UNSUPPORTED.
+ * NNS_ERR_NOMEM.  flags: NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and for fp32 points NNS_RANGE_MFMA
+ * (below); any other: NNS_ERR_UNSUPPORTED.
  * Library stream, no device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is
  * allocated. */
 int nns_search_f32_range(int k, int m, int n, const float *s_points, const float *r_points, float radius2,
@@ -335,6 +343,40 @@ int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const u
  * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
  * workgroup, workspace bytes}. */
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
+
+/* ---- range search on the matrix cores (NNS_RANGE_MFMA, K7m) ------------------------
+ * On an index created with NNS_RANGE_MFMA the two range passes keep every contract above (lims form, ascending global
+ * indices, bit-equal V0 distances, inclusive compare, NaN / +INF never a hit, fill matches the last count, searches in
+ * between allowed, no atomically ordered positions, null idx_dev / dist_dev) and run in two steps: a flag pass on
+ * v_mfma_f32_32x32x16_bf16 sets, per query, the bit of every 32-ref block that holds a split-bf16 score within the
+ * query's threshold (nns_range_threshold); the evaluation pass computes V0's distance for the refs of flagged blocks
+ * only, on the original points, and alone decides the hits.  The flag bitmap (m_pad x n_pad / 32 bits, at most
+ * 256 MiB; beyond that the queries run in batches, the output order unchanged) belongs to the index, grows on demand
+ * and is freed behind an event.  The passes fall back to K7, decided on the host, when m is below the filter's query
+ * floor (64), the refs hold NaN / INF / |v| >= 1e17, or radius2 is not finite.  A QUERY with such values is known only
+ * on the device: its flag row is filled, so the evaluation is the exact scan for it.  The whole call
+ * nns_search_f32_range accepts the flag too (with NNS_PATH_AUTO / NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE).
+ * nns_index_stats reports NNS_PATH_MFMA after a filtered pass; with NNS_PROFILE prep_queries_ms is K2 on the queries,
+ * filter_ms the flag pass, finalize_ms the evaluation (with several batches: filter_ms covers all but the last
+ * batch's evaluation). */
+
+/* Diagnostic: what the last nns_index_range_count on this index did.  out[0..3] = {path taken (NNS_PATH_EXACT: K7,
+ * NNS_PATH_MFMA: K7m), flagged (query, 32-ref block) pairs, pairs examined (m x blocks per query), total hits
+ * lims[m]}; the middle two are 0 on the exact path, all four before any count.  out_len >= 4.  Waits for the stream
+ * the index last worked on (not the device), like nns_index_near_ties. */
+int nns_index_range_info(nns_index *ix, int64_t *out, int out_len);
+/* Diagnostic (host only, no device needed): the launch geometry of K7m for a k-D search of m queries over n refs with
+ * index flags `flags` (NNS_FILTER_SPLIT_EAGER selects the eager image layout).  out[0..9] = {tile depth kt, refs per
+ * flagged block (32), blocks per query (n padded to K2's ring slot), queries per batch, batches, flag-workspace bytes,
+ * grid.x of a full batch's flag pass, grid.y (ref-range splits), LDS bytes per workgroup, ref image layout (0 eager: hi,
+ * lo fragments interleaved; 1 lazy: hi region, lo region)}.  out_len >= 10.  NNS_ERR_UNSUPPORTED outside the supported
+ * forms (k outside 8 .. 256, NNS_FILTER_F32, NNS_FILTER_BF16, an n whose flag rows pass the workspace cap). */
+int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_len);
+/* Diagnostic (host only): the score threshold K7m's flag pass gives a query of centred squared norm qnorm2 against
+ * refs of maximum centred squared norm ymax2 at tile depth kt and squared radius radius2: with a = fl(radius2 - qnorm2),
+ * fl(a + 1.002 tau(a)) (tau: nns_tau_consts mode 3) plus 2^-22 (radius2 + qnorm2).  Every ref with a V0 distance
+ * <= radius2 has a score <= *thr_out.  Monotone in radius2. */
+int nns_range_threshold(int kt, float qnorm2, float ymax2, float radius2, float *thr_out);
 
 /* Deterministic synthetic clouds: dev[i] = u24(splitmix64(seed, offset+i)) * 2^-24
  * in [0,1) — bit-identical to oracle/v0_oracle.c:nns_rng_fill on the CPU. */

@@ -121,6 +121,16 @@ struct nns_index {
     const void *range_q = nullptr;
     float range_r2 = 0.0f;
 
+    // NNS_RANGE_MFMA (K7m): the flag bitmap of one query batch, {flagged blocks, lims[m]} of the last count, and the
+    // path that count took (the fill follows it)
+    bool range_mfma = false;
+    bool refs_unknown = false;     // refreshed since refs_bad was latched: the next filtered count reads K2's word first
+    char *range_flags = nullptr;
+    size_t range_flags_bytes = 0;
+    unsigned long long *range_stat = nullptr;
+    int range_path = 0;            // 0: no count yet
+    int64_t range_examined = 0;
+
     // NNS_PROFILE: a ring of event sets, one per search (refresh + search = one step), so that a
     // caller can time many steps back to back and read the averages once, without a device
     // synchronisation inside every step
@@ -266,7 +276,7 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     // index's own, still running) are not waited for.  (Round 2: hipDeviceSynchronize() here.)
     void *const blocks[] = {ix->r_own, ix->rimg, ix->rnorm, ix->mean, ix->mean_ws, ix->scal, ix->qimg, ix->qnorm,
                             ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws, ix->topk_ws,
-                            ix->range_ws};
+                            ix->range_ws, ix->range_flags, ix->range_stat};
     if (stream_idle)
         for (void *b : blocks) pool_free(b);
     else
@@ -294,6 +304,14 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         return NNS_ERR_INVALID;
     }
     *out = nullptr;
+    if (flags & NNS_RANGE_MFMA) {
+        // (the first version: fp32 points whose filter form is the split one, at the split tiles' depths)
+        if (bf16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) || k < 8 || k > 256) {
+            set_error("nns_index_create: the range-MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256 (k=%d, flags 0x%x)",
+                      k, flags);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    }
     NNS_TRY(ensure_device_ok(device));
     hipStream_t st = (hipStream_t)stream;
 
@@ -307,6 +325,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     ix->r_dev = r_dev;
     ix->bf16 = bf16;
     ix->profile = (flags & NNS_PROFILE) != 0;
+    ix->range_mfma = (flags & NNS_RANGE_MFMA) != 0;
     ix->last_stream = st;
     {
         const int frc = operand_form(k, bf16 != 0, flags, &ix->mixed, &ix->split);
@@ -357,7 +376,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             }
             ix->ev_valid = true;
         }
-        if (path == NNS_PATH_MFMA) {
+        if (path == NNS_PATH_MFMA || ix->range_mfma) {   // (the range flag builds the image whatever the 1-NN path)
             if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
                                   (flags & NNS_FILTER_SPLIT_EAGER) != 0)) !=
                 NNS_OK)
@@ -423,9 +442,10 @@ int nns_index_refresh(nns_index *ix, void *stream)
     ix->last_stream = st;
     if (ix->r_soa)   // the caller's dimension-major array may have changed
         NNS_TRY(launch_soa_to_aos(ix->k, ix->n, ix->r_soa, ix->r_own, ix->bf16 ? 2 : 4, st));
-    if (ix->path != NNS_PATH_MFMA) return NNS_OK;
+    if (ix->path != NNS_PATH_MFMA && !ix->range_mfma) return NNS_OK;
     if (ix->profile) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_R0], st);
     NNS_TRY(prep_refs(ix, st));
+    ix->refs_unknown = ix->range_mfma;
     // The new values may or may not void the error bound (NaN / INF / huge); refresh stays asynchronous,
     // so the next search runs the filter and K5 decides on the device (finalize.hip re-checks K2's max-|v|
     // word and sends every query to the exact scan if it must).  nns_index_stats() re-latches the flag.
@@ -440,7 +460,7 @@ int nns_index_refresh(nns_index *ix, void *stream)
 // (a block that is replaced goes back to the pool behind an event on `st`, the stream of the search that is about
 //  to be enqueued: the index's earlier searches were ordered before it by the caller — searches of one index do
 //  not overlap — so once that event has fired nothing reads the old block any more.  No host wait.)
-static int ensure_query_ws(nns_index *ix, int m, hipStream_t st)
+static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists = true)
 {
     FilterGeom g = ix->geom;
     FilterGeom gq{};
@@ -465,6 +485,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st)
         }
         ix->m_cap = gq.m_pad;
     }
+    if (!with_lists) return NNS_OK;   // (K7m: query image and norms only)
     const size_t need = (size_t)gq.splits * gq.m_pad * gq.lpq;   // lane-lists
     if (need > ix->lists_cap) {
         void *const old[] = {ix->lists, ix->counts};
@@ -745,6 +766,74 @@ static int range_check_split(const char *where, nns_index *ix, int m, const void
     return NNS_OK;
 }
 
+// ---- K7m: the filtered passes of an NNS_RANGE_MFMA index ---------------------------------------------------------
+// K2 on the queries, as the 1-NN filter's (the workspaces are shared with it: a fill never relies on them surviving a
+// search in between — one batch keeps its bitmap, several batches prepare the queries again)
+static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipStream_t st)
+{
+    NNS_TRY(ensure_query_ws(ix, m, st, false));
+    const FilterGeom &g = ix->geom;
+    NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
+    return launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f, (float *)ix->qimg,
+                             ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st, 2);
+}
+
+// the filtered path runs when its result can be trusted and pays: enough queries for the tiles, finite refs below
+// 1e17, a finite radius, a shape the flag pass plans
+static int range_mfma_choose(nns_index *ix, int m, float radius2, hipStream_t st, RangeMfmaPlan *mp, bool *use)
+{
+    *use = false;
+    if (!ix->range_mfma || m < kTinyM || !(radius2 < INFINITY)) return NNS_OK;
+    if (ix->refs_unknown) {   // refreshed since the flag was latched: read K2's max-|v| word (one wait on this stream)
+        DevScalars h{};
+        NNS_HIP(hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, st));
+        NNS_HIP(hipStreamSynchronize(st));
+        ix->refs_bad = h.r_maxabs_bits >= 0x5BB1A2BCu;
+        ix->refs_unknown = false;
+    }
+    if (ix->refs_bad) return NNS_OK;
+    *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp) == NNS_OK;
+    return NNS_OK;
+}
+
+// fill = false: the count pass (lims, the per-chunk offsets in range_ws, range_stat); true: the fill
+static int range_mfma_pass(nns_index *ix, const RangeMfmaPlan &mp, bool fill, int m, const void *q_dev, float radius2,
+                           int64_t *lims_dev, int *idx_dev, float *dist_dev, hipStream_t st)
+{
+    const bool prof = ix->profile;
+    hipEvent_t *ev = ix->evr[ix->ev_slot];
+    if (prof) (void)hipEventRecord(ev[EV_BEGIN], st);
+    const bool prep = !fill || mp.batches > 1;
+    if (prep) NNS_TRY(range_mfma_prep_queries(ix, m, q_dev, st));
+    if (prof) (void)hipEventRecord(ev[EV_QPREP], st);
+    if (!fill) NNS_HIP(hipMemsetAsync(ix->range_stat, 0, 2 * sizeof(unsigned long long), st));
+    for (int b = 0; b < mp.batches; ++b) {
+        const int i0 = b * mp.batch;
+        const int rows = m - i0 < mp.batch ? m - i0 : mp.batch;
+        if (prep)
+            NNS_TRY(launch_range_flags(mp, ix->k, i0, rows, q_dev, ix->qimg, ix->qnorm, ix->rimg, ix->rnorm, ix->scal,
+                                       radius2, ix->range_flags, st));
+        if (prof && b == mp.batches - 1) (void)hipEventRecord(ev[EV_FILTER], st);
+        NNS_TRY(launch_range_eval(mp, fill, ix->k, i0, rows, ix->n, q_dev, ix->r_dev, ix->range_flags, radius2, ix->base,
+                                  lims_dev, ix->range_ws, idx_dev, dist_dev, ix->range_stat, st));
+    }
+    if (!fill) {
+        int64_t *sums = mp.tiles > 1 ? (int64_t *)(ix->range_ws + mp.offs_bytes) : nullptr;
+        NNS_TRY(launch_range_lims(m, mp.echunks, mp.tiles, mp.echunks > 1 ? (int *)ix->range_ws : nullptr, sums, lims_dev, st));
+        NNS_HIP(hipMemcpyAsync(ix->range_stat + 1, lims_dev + m, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (prof) {
+        (void)hipEventRecord(ev[EV_FINAL], st);
+        (void)hipEventRecord(ev[EV_RERANK], st);
+        (void)hipEventRecord(ev[EV_END], st);
+    }
+    ix->last_m = m;
+    ix->last_path = NNS_PATH_MFMA;
+    ix->searched = true;
+    profile_advance(ix, NNS_PATH_MFMA);
+    return NNS_OK;
+}
+
 static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float radius2, int64_t *lims_dev,
                                   hipStream_t st)
 {
@@ -754,6 +843,28 @@ static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float
     NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
+    if (ix->range_mfma && !ix->range_stat && pool_alloc(&ix->range_stat, 2 * sizeof(unsigned long long)) != hipSuccess) {
+        set_error("nns_index_range_count: workspace allocation failed");
+        return NNS_ERR_NOMEM;
+    }
+    RangeMfmaPlan mp{};
+    bool filtered = false;
+    NNS_TRY(range_mfma_choose(ix, m, radius2, st, &mp, &filtered));
+    if (filtered) {
+        if (!grow_index_ws(&ix->range_ws, &ix->range_ws_bytes, mp.ws_bytes, st) ||
+            !grow_index_ws(&ix->range_flags, &ix->range_flags_bytes, mp.flag_bytes, st)) {
+            set_error("nns_index_range_count: workspace allocation failed (%zu + %zu bytes)", mp.ws_bytes, mp.flag_bytes);
+            return NNS_ERR_NOMEM;
+        }
+        NNS_TRY(range_mfma_pass(ix, mp, false, m, q_dev, radius2, lims_dev, nullptr, nullptr, st));
+        ix->range_counted = true;
+        ix->range_m = m;
+        ix->range_q = q_dev;
+        ix->range_r2 = radius2;
+        ix->range_path = NNS_PATH_MFMA;
+        ix->range_examined = (int64_t)m * mp.blocks;
+        return NNS_OK;
+    }
     if (!grow_index_ws(&ix->range_ws, &ix->range_ws_bytes, p.ws_bytes, st)) {
         set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
         return NNS_ERR_NOMEM;
@@ -761,10 +872,16 @@ static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float
     NNS_TRY(index_exact_pass(ix, m, st, [&] {
         return launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st);
     }));
+    if (ix->range_mfma) {   // (nns_index_range_info: the exact pass's total; no flags were examined)
+        NNS_HIP(hipMemsetAsync(ix->range_stat, 0, sizeof(unsigned long long), st));
+        NNS_HIP(hipMemcpyAsync(ix->range_stat + 1, lims_dev + m, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    }
     ix->range_counted = true;
     ix->range_m = m;
     ix->range_q = q_dev;
     ix->range_r2 = radius2;
+    ix->range_path = NNS_PATH_EXACT;
+    ix->range_examined = 0;
     return NNS_OK;
 }
 
@@ -781,6 +898,12 @@ static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float 
     NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
+    if (ix->range_path == NNS_PATH_MFMA) {   // (the count's path; its plan depends on k, m, n and the index alone)
+        RangeMfmaPlan mp{};
+        NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp));
+        if (!idx_dev && !dist_dev) return NNS_OK;
+        return range_mfma_pass(ix, mp, true, m, q_dev, radius2, const_cast<int64_t *>(lims_dev), idx_dev, dist_dev, st);
+    }
     return index_exact_pass(ix, m, st, [&] {
         if (!idx_dev && !dist_dev) return (int)NNS_OK;
         return launch_range_fill(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, ix->base, lims_dev,
@@ -814,6 +937,50 @@ int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
     return NNS_OK;
 }
 
+int nns_index_range_info(nns_index *ix, int64_t *out, int out_len)
+{
+    if (!ix || !out || out_len < 4) {
+        set_error("nns_index_range_info: bad arguments");
+        return NNS_ERR_INVALID;
+    }
+    out[0] = ix->range_path;
+    out[1] = out[2] = out[3] = 0;
+    if (!ix->range_path) return NNS_OK;
+    out[2] = ix->range_examined;
+    out[3] = -1;   // (an index without NNS_RANGE_MFMA keeps no total)
+    if (!ix->range_stat) return NNS_OK;
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(ix->device));
+    unsigned long long h[2] = {0, 0};
+    NNS_HIP(hipMemcpyAsync(h, ix->range_stat, sizeof(h), hipMemcpyDeviceToHost, ix->last_stream));
+    NNS_HIP(hipStreamSynchronize(ix->last_stream));
+    out[1] = (int64_t)h[0];
+    out[3] = (int64_t)h[1];
+    return NNS_OK;
+}
+
+int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_len)
+{
+    if (!out || out_len < 10 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
+    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) {
+        set_error("nns_plan_range_mfma: the range-MFMA flag runs on split-bf16 operands only (flags 0x%x)", flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    RangeMfmaPlan p{};
+    NNS_TRY(range_mfma_plan(k, m, n, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &p));
+    const int v[10] = {p.kt, 32, p.blocks, p.batch, p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, p.lazy_img};
+    memcpy(out, v, sizeof(v));
+    return NNS_OK;
+}
+
+int nns_range_threshold(int kt, float qnorm2, float ymax2, float radius2, float *thr_out)
+{
+    if (kt <= 0 || !thr_out) return NNS_ERR_INVALID;
+    *thr_out = range_threshold(kt, qnorm2, ymax2, radius2);
+    return NNS_OK;
+}
+
 int nns_index_stats(nns_index *ix, nns_stats *out)
 {
     if (!ix || !out) return NNS_ERR_INVALID;
@@ -822,9 +989,11 @@ int nns_index_stats(nns_index *ix, nns_stats *out)
     memset(out, 0, sizeof(*out));
     out->path = ix->searched ? ix->last_path : ix->path;
     out->nonfinite = ix->refs_bad ? 1 : 0;
-    if (ix->path == NNS_PATH_MFMA) {
-        out->k_tile = ix->geom.kt;
-        out->splits = ix->geom.splits;
+    if (ix->scal) {   // (an index with a ref image: the MFMA path, or NNS_RANGE_MFMA)
+        if (ix->path == NNS_PATH_MFMA || out->path == NNS_PATH_MFMA) {
+            out->k_tile = ix->geom.kt;
+            out->splits = ix->geom.splits;
+        }
         // (the index's own stream, not the device: the read-out waits for this index's work only)
         DevScalars h{};
         NNS_HIP(hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, ix->last_stream));
@@ -832,6 +1001,7 @@ int nns_index_stats(nns_index *ix, nns_stats *out)
         out->ambiguous = ix->searched && ix->last_path == NNS_PATH_MFMA ? h.amb_count : 0;
         out->multi_candidate = ix->searched && ix->last_path == NNS_PATH_MFMA ? h.multi_count : 0;
         ix->refs_bad = h.r_maxabs_bits >= 0x5BB1A2BCu;   // (re-)latch: refs that void the bound go straight to K1
+        ix->refs_unknown = false;
         if (ix->refs_bad || h.q_maxabs_bits >= 0x5BB1A2BCu) out->nonfinite = 1;
     }
     if (ix->profile && ix->ev_valid) {
@@ -1476,7 +1646,11 @@ static int search_whole_range(const char *where, int k, int m, int n, const void
     NNS_TRY(whole_call_upload(call, where, k, m, n, s_points, r_points, esz, flags, &q_d, &r_d,
                               [&] { return call.alloc(&lims_d, lb); }));
     // (the exact path's index: no MFMA ref pre-pass, it reads the point-major refs only)
-    NNS_TRY(index_create_impl(&call.ix, device, k, n, r_d, bf16, 0, NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync,
+    // (NNS_RANGE_MFMA: the same index plus the split-bf16 ref image; its build waits once to learn whether the refs
+    //  void the error model)
+    NNS_TRY(index_create_impl(&call.ix, device, k, n, r_d, bf16, 0,
+                              NNS_PATH_EXACT | (flags & NNS_PROFILE) |
+                                  ((flags & NNS_RANGE_MFMA) ? (unsigned)NNS_RANGE_MFMA : kCreateNoSync),
                               st));
     NNS_TRY(index_range_count_impl(call.ix, m, q_d, radius2, lims_d, st));
     if (call.copy(lims_out, lims_d, lb, hipMemcpyDeviceToHost) != hipSuccess || call.finish() != hipSuccess) {
@@ -1522,7 +1696,11 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     // (lims_out stands for the output buffer of the shared check)
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
     NNS_TRY(range_check_radius(where, radius2));
-    NNS_TRY(check_exact_only_flags(where, "range search", flags));
+    NNS_TRY(check_exact_only_flags(where, "range search", flags & ~(unsigned)NNS_RANGE_MFMA));
+    if ((flags & NNS_RANGE_MFMA) && (bf16 || k < 8 || k > 256)) {
+        set_error("%s: the range-MFMA flag takes fp32 points, 8 <= k <= 256 (k=%d)", where, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
     RangePlan p{};
     NNS_TRY(range_plan(k, m, n, &p));   // (k beyond the exact path: before any device work)
     DeviceScope keep_device;

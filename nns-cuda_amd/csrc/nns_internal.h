@@ -413,6 +413,20 @@ __host__ __device__ inline float record_threshold(const TauConsts &t, float a)
     return a + (t.c0 + t.c1 * (d > 0.0f ? d : 0.0f)) * 1.002f;
 }
 
+// K7m's flag threshold of a query (range_mfma.hip): a ref whose V0 distance is <= radius2 has a split-bf16 score
+// (tau mode 3) <= this value.  With a = fl(radius2 - |x'|^2): fl(a + 1.002 tau(a)), the filter's record threshold at a,
+// plus 2^-22 (radius2 + |x'|^2) for the roundings of the subtraction and of the two sums, which are relative to
+// max(radius2, |x'|^2) — a magnitude tau's own rounding term (sized for scores, <= (X + Y)^2) does not cover once the
+// radius is far larger than the cloud.  Monotone in radius2.  Derivation: DESIGN section 4, "K7m".
+__host__ __device__ inline float range_threshold(int kt, float qnorm2, float ymax2, float radius2)
+{
+#pragma clang fp contract(off)
+    const TauConsts t = tau_consts(kt, qnorm2, ymax2, 3);
+    const float a = radius2 - qnorm2;
+    const float thr = record_threshold(t, a);
+    return thr + 0x1p-22f * (radius2 + qnorm2);
+}
+
 // tau(a) of K1f, the vector-ALU filter of k <= 3 (exact_kernels.hip, lowdim_filter_kernel), in fp32, rounded up everywhere.
 // Its score is an FMA chain of 2K steps (K for the norm of y' = fl(r - c), K for -2 x'.y' on top of it), so the relative
 // part is tau_consts' model at kt = 2K <= 8 with (X + Y)^2 <= 2 (X^2 + Y^2): c0 <= 62.2 u (X^2 + Y^2), c1 <= 20.1 u.
@@ -559,5 +573,31 @@ int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, c
 // fill pass: idx[lims[m]] (global indices), dist (optional) from the lims and ws of the count pass
 int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
                       int64_t base, const int64_t *lims, const void *ws, int *idx, float *dist, hipStream_t st);
+
+// the lims scans of the count pass alone (offs: [m][chunks] counts -> offsets and lims[i + 1]; one chunk: lims[1 .. m]
+// already hold the counts), shared with K7m; tiles = range_scan_tiles(m), sums: tiles int64 (several tiles)
+int range_scan_tiles(int m);
+int launch_range_lims(int m, int chunks, int tiles, int *offs, int64_t *sums, int64_t *lims, hipStream_t st);
+
+// range_mfma.hip (K7m: the MFMA flag pass + V0 evaluation of the flagged 32-ref blocks)
+struct RangeMfmaPlan {
+    int kt, spb, qb;      // tile depth; 1 KiB fragment steps per 32-ref block; 32-query blocks per wave
+    int qw;               // queries per workgroup of the flag pass
+    int n_pad, total_slots, blocks, wpq;   // K2's padding; ring slots; 32-ref blocks and flag words per query
+    int lazy_img;         // the ref image is in the lazy layout
+    int batch, batches;   // queries per flag-bitmap batch (whole workgroups), batches
+    size_t flag_bytes;    // the bitmap of one batch
+    int gx, gy, slots_per_split, lds;      // flag pass: grid of a full batch, slots per ref-range split, LDS bytes
+    int echunks, eper;    // evaluation: chunks per query, flag words per chunk
+    int tiles;            // tiles of the lims scan
+    size_t offs_bytes, ws_bytes;   // K7's workspace layout: [m][echunks] counts (several chunks), then the tile sums
+};
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p);
+int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
+                       const void *rimg, const float *rnorm, const DevScalars *scal, float radius2, void *flags,
+                       hipStream_t st);
+int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows, int n, const void *q, const void *r,
+                      const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
+                      unsigned long long *stat, hipStream_t st);
 
 }  // namespace nns

@@ -259,6 +259,26 @@ int range_plan(int k, int m, int n, RangePlan *p)
     return NNS_OK;
 }
 
+int range_scan_tiles(int m) { return divup(m, kScanTile); }
+
+int launch_range_lims(int m, int chunks, int tiles, int *offs, int64_t *sums, int64_t *lims, hipStream_t st)
+{
+    if (chunks > 1) {
+        hipLaunchKernelGGL(range_chunk_offsets_kernel, dim3(divup(m, kRangeWaves)), dim3(kRangeThreads), 0, st, offs, m,
+                           chunks, lims);
+        NNS_HIP(hipGetLastError());
+    }
+    if (tiles > 1) {
+        hipLaunchKernelGGL(range_tile_sums_kernel, dim3(tiles), dim3(kRangeThreads), 0, st, lims, m, sums);
+        NNS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(range_sums_scan_kernel, dim3(1), dim3(kRangeThreads), 0, st, sums, tiles);
+        NNS_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(range_tile_scan_kernel, dim3(tiles), dim3(kRangeThreads), 0, st, lims, m, (const int64_t *)sums);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
 template <bool FILL, typename T>
 static int launch_range_scan(const RangePlan &p, int k, int m, int n, const void *q, const void *r, float radius2,
                              int64_t base, int64_t *lims, int *offs, int *idx, float *dist, hipStream_t st)
@@ -284,20 +304,7 @@ int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, c
         NNS_TRY((launch_range_scan<false, uint16_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
     else
         NNS_TRY((launch_range_scan<false, float>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    if (p.chunks > 1) {
-        hipLaunchKernelGGL(range_chunk_offsets_kernel, dim3(divup(m, kRangeWaves)), dim3(kRangeThreads), 0, st, offs, m,
-                           p.chunks, lims);
-        NNS_HIP(hipGetLastError());
-    }
-    if (p.tiles > 1) {
-        hipLaunchKernelGGL(range_tile_sums_kernel, dim3(p.tiles), dim3(kRangeThreads), 0, st, lims, m, sums);
-        NNS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(range_sums_scan_kernel, dim3(1), dim3(kRangeThreads), 0, st, sums, p.tiles);
-        NNS_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(range_tile_scan_kernel, dim3(p.tiles), dim3(kRangeThreads), 0, st, lims, m, (const int64_t *)sums);
-    NNS_HIP(hipGetLastError());
-    return NNS_OK;
+    return launch_range_lims(m, p.chunks, p.tiles, offs, sums, lims, st);
 }
 
 int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,

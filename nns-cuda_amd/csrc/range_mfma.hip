@@ -1,0 +1,452 @@
+// range_mfma.hip — K7m: the MFMA-filtered fixed-radius search (NNS_RANGE_MFMA; fp32 points, split-bf16 operands).
+//
+// K7 evaluates V0's distance for every (query, ref) pair on the vector ALUs.  K7m asks the matrix cores first which
+// 32-ref blocks can hold a hit at all, and evaluates V0 only there:
+//   flag pass:  the eager split filter's tile (filter_mfma.hip, OpSplitT): refs are A and queries B of
+//               v_mfma_f32_32x32x16_bf16, the accumulator seeded with |y'|^2, hi.hi + hi.lo + lo.hi per 16-dim step, a
+//               wave's query operands resident, refs streamed through a 4-slot LDS ring by global_load_lds_dwordx4
+//               with counted vmcnt waits and one barrier per slot.  K2's ref image is read in both layouts (eager:
+//               hi, lo interleaved; lazy: hi region, lo region).  The threshold is FIXED per query before the loop
+//               (range_threshold, nns_internal.h): no running minimum, no lists.  A finished 32 x 32 tile is tested
+//               score by score with !(s > thr) — a NaN score passes — and a lane that passes sets the bit of
+//               (its query, the 32-ref block) in the flag bitmap with a vector atomicOr (order-free: the bitmap is
+//               deterministic; both lanes of a query set the same bit).
+//   void rows:  a query with a non-finite coordinate or |v| >= 1e17 (the bound of K5's error model) gets its whole
+//               flag row filled: the evaluation below is then the exact scan for it.
+//   evaluation: one wave per (query, chunk of flag words) walks the words in ascending order; per set bit, lane = ref
+//               of the block evaluates V0's chain (v0_lane_chains, the scan core of K7) on the ORIGINAL points and
+//               applies K7's hit predicate.  Count writes per-(query, chunk) counts in K7's layout (K7's own kernels
+//               turn them into lims); fill recomputes and writes each hit at chunk start + hits so far + ballot
+//               prefix.  Blocks, lanes and chunks ascend: index order, no atomics, identical buffers every run.
+// The evaluation alone decides hits; a false flag costs time, never an answer.  Why no hit is missed: DESIGN §4 "K7m".
+//
+// The operator geometry (fragment steps per block, query blocks per wave) repeats OpSplitT's few lines instead of
+// sharing a header with filter_mfma.hip: that file's kernels stay byte for byte what they were.
+#include "nns_internal.h"
+
+namespace nns {
+
+typedef float rm_f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 rm_bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kRmWaves = 8;                            // waves per workgroup: two per SIMD
+constexpr int kRmSlotSteps = 32;                       // 1 KiB fragments per ring slot
+constexpr int kRmRing = 4;                             // ring slots
+constexpr int kRmSlotCoord = kRmSlotSteps * 1024;
+constexpr int kRmSlotBytes = kRmSlotCoord + 2048;      // + the slot's norms (up to 512 refs)
+constexpr int kRmLds = kRmRing * kRmSlotBytes;
+constexpr int kRmAhead = 3;                            // slots in flight ahead of the one being consumed
+constexpr int kRmPpw = kRmSlotSteps / kRmWaves;        // image DMA pieces per wave and slot
+constexpr size_t kRmFlagBudget = (size_t)256 << 20;    // flag bitmap cap (include/nns.h)
+constexpr int kRmEvalThreads = 256;
+constexpr int kRmEvalWaves = kRmEvalThreads / 64;
+constexpr int kRmChunkWords = 64;                      // a chunk of the evaluation is whole 64-word steps
+
+// as range_kernels.hip
+__device__ __forceinline__ bool rm_hit(float d, float radius2) { return d <= radius2 && d < __builtin_inff(); }
+__device__ __forceinline__ int rm_lanes_below(uint64_t mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+__device__ __forceinline__ rm_f32x16 rm_mma(const float4 &a, const float4 &b, rm_f32x16 acc)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(rm_bf16x8, a), __builtin_bit_cast(rm_bf16x8, b), acc, 0, 0,
+                                                   0);
+}
+
+struct RangeFlagArgs {
+    const float4 *qimg;     // the batch's query image (K2 form 2: qh, ql fragment per k-step), [rows / 32][SPB][64]
+    const char *rimg;       // K2's ref image
+    const char *rimg_lo;    // lazy layout: the lo region; nullptr: the eager layout
+    const float *rnorm;     // [n_pad]
+    const float *qnorm;     // the batch's centred squared norms
+    const DevScalars *scal;
+    unsigned *flags;        // [rows][wpq] words, bit b of a row = block b
+    int rows_live;          // queries of the batch (rows beyond are padding: never flagged)
+    int wpq;                // flag words per query
+    int total_slots, slots_per_split, n_pad, kt;
+    float radius2;
+};
+
+// SPB: 1 KiB fragment steps per 32-ref block (kt / 8: hi, lo per 16-dim step); QB: 32-query blocks per wave
+template <int SPB, int QB>
+__global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFlagArgs a)
+{
+    constexpr int BPS = kRmSlotSteps / SPB;            // blocks per ring slot
+    constexpr int SLOT_REFS = 32 * BPS;
+    constexpr int NP = SLOT_REFS > 256 ? SLOT_REFS / 256 : 1;   // norm DMA pieces per slot
+    static_assert(kRmSlotSteps % SPB == 0 && SPB >= 2 && SPB % 2 == 0, "whole blocks per slot, hi / lo pairs");
+    static_assert(SLOT_REFS * 4 <= kRmSlotBytes - kRmSlotCoord, "norm room of a ring slot");
+    extern __shared__ __attribute__((aligned(16))) char rm_smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5;
+    const int qblk0 = (blockIdx.x * kRmWaves + wave) * QB;
+
+    // ---- resident B operands and the lanes' fixed thresholds -------------------------------------------------
+    float4 bq[QB][SPB];
+    float thr[QB];
+    unsigned *row[QB];   // the flag row of the lane's query
+    {
+        const float4 *src = a.qimg + (size_t)qblk0 * (SPB * 64) + lane;
+        const float ymax2 = __uint_as_float(a.scal->ymax2_bits);
+#pragma unroll
+        for (int st = 0; st < QB; ++st) {
+#pragma unroll
+            for (int b = 0; b < SPB; ++b) bq[st][b] = src[(st * SPB + b) * 64];
+            const int qi = (qblk0 + st) * 32 + (lane & 31);
+            const float qn = a.qnorm[qi];
+            // (padding rows: nothing passes !(s > -INF) but a NaN or -INF score, and their rows are never read.  A norm
+            //  that is not finite comes from a coordinate beyond 1e17: that query's row is filled behind this pass)
+            thr[st] = qi < a.rows_live && qn < __builtin_inff() ? range_threshold(a.kt, qn, ymax2, a.radius2) : -__builtin_inff();
+            row[st] = a.flags + (size_t)qi * a.wpq;
+        }
+    }
+    // the loads are waited for here, before the ring starts (the compiler does not see the asm DMAs)
+#pragma unroll
+    for (int st = 0; st < QB; ++st) {
+#pragma unroll
+        for (int b = 0; b < SPB; ++b)
+            asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
+        asm volatile("" : "+v"(thr[st]));
+    }
+
+    const int slot0 = blockIdx.y * a.slots_per_split;
+    int ns = a.total_slots - slot0;
+    if (ns > a.slots_per_split) ns = a.slots_per_split;
+    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)rm_smem);
+
+    // slot s (relative to slot0, s < ns: nothing is read past the image) into ring position s % kRmRing: the norms by
+    // one wave, first, then every wave's kRmPpw image pieces — a counted wait that leaves the youngest slot's kRmPpw
+    // pieces in flight has therefore seen every older piece land, norms included
+    auto issue = [&](int s) __attribute__((always_inline)) {
+        const size_t gslot = (size_t)(slot0 + s);
+        const unsigned dst = lds_base + (s & (kRmRing - 1)) * kRmSlotBytes;
+        if (((int)gslot & (kRmWaves - 1)) == wave) {
+            if constexpr (SLOT_REFS >= 128) {
+                // 256 norms per piece (a 128-ref slot: the upper lanes read the next slot's, or the array's last four)
+#pragma unroll
+                for (int np = 0; np < NP; ++np) {
+                    size_t e = gslot * SLOT_REFS + np * 256 + lane * 4;
+                    if (e > (size_t)a.n_pad - 4) e = (size_t)a.n_pad - 4;
+                    dma16(a.rnorm + e, dst + kRmSlotCoord + np * 1024);
+                }
+            } else {
+                size_t e = gslot * SLOT_REFS + lane;
+                if (e > (size_t)a.n_pad - 1) e = (size_t)a.n_pad - 1;
+                dma4(a.rnorm + e, dst + kRmSlotCoord);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < kRmPpw; ++p) {
+            const int piece = wave * kRmPpw + p;
+            if (a.rimg_lo) {
+                // lazy layout: LDS fragment `piece` = block piece / SPB, k-step (piece % SPB) / 2, hi (even) or lo
+                const int pb = piece / SPB, pf = piece % SPB;
+                const char *reg = (pf & 1) ? a.rimg_lo : a.rimg;
+                dma16(reg + ((gslot * BPS + pb) * (SPB / 2) + (pf >> 1)) * 1024 + lane * 16, dst + piece * 1024);
+            } else {
+                dma16(a.rimg + gslot * kRmSlotCoord + piece * 1024 + lane * 16, dst + piece * 1024);
+            }
+        }
+    };
+
+#pragma unroll
+    for (int s = 0; s < kRmAhead; ++s)
+        if (s < ns) issue(s);
+
+    for (int s = 0; s < ns; ++s) {
+        // slot s has landed: at most the pieces of the (up to two) younger slots stay in flight.  (vmcnt counts in issue
+        // order; a flag atomic issued in between only makes the wait longer.)
+        const int younger = ns - 1 - s;
+        if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kRmPpw) : "memory");
+        else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kRmPpw) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // everyone's share of slot s has landed; everyone is done with slot s - 1, whose ring position slot s + 3 takes
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + kRmAhead < ns) issue(s + kRmAhead);
+        const char *slot = rm_smem + (s & (kRmRing - 1)) * kRmSlotBytes;
+#pragma unroll 1
+        for (int blk = 0; blk < BPS; ++blk) {
+            rm_f32x16 acc0, acc1;
+            // accumulators start at |y'_j|^2 of their rows: (r & 3) + 8 (r >> 2) + 4 h
+            const float *nrm = reinterpret_cast<const float *>(slot + kRmSlotCoord) + blk * 32 + 4 * h;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 nv = *reinterpret_cast<const float4 *>(nrm + 8 * g);
+                acc0[4 * g + 0] = nv.x;
+                acc0[4 * g + 1] = nv.y;
+                acc0[4 * g + 2] = nv.z;
+                acc0[4 * g + 3] = nv.w;
+            }
+            acc1 = acc0;
+            const float4 *fp = reinterpret_cast<const float4 *>(slot + blk * (SPB * 1024)) + lane;
+#pragma unroll
+            for (int b = 0; b < SPB; b += 2) {
+                const float4 rh = fp[b * 64], rl = fp[(b + 1) * 64];
+                // ref hi x (qh, ql) of the k-step, ref lo x qh
+                acc0 = rm_mma(rh, bq[0][b], acc0);
+                if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b], acc1);
+                acc0 = rm_mma(rh, bq[0][b + 1], acc0);
+                if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b + 1], acc1);
+                acc0 = rm_mma(rl, bq[0][b], acc0);
+                if constexpr (QB == 2) acc1 = rm_mma(rl, bq[1][b], acc1);
+            }
+            const int bg = (slot0 + s) * BPS + blk;   // the block's number = its bit in a flag row
+#pragma unroll
+            for (int st = 0; st < QB; ++st) {
+                const rm_f32x16 t = st == 0 ? acc0 : acc1;
+                bool pass = false;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) pass = pass || !(t[r] > thr[st]);   // (a NaN score passes)
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(pass) != 0ull, 0)) {   // rare, wave-uniform
+                    if (pass) atomicOr(row[st] + (bg >> 5), 1u << (bg & 31));
+                }
+            }
+        }
+    }
+}
+
+// one wave per query of the batch: a non-finite coordinate or |v| >= 1e17 fills the query's flag row
+__global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, int rows, const float *__restrict__ q,
+                                                                         unsigned *__restrict__ flags, int wpq)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * kRmEvalWaves + (threadIdx.x >> 6);
+    if (i >= rows) return;   // (whole waves)
+    bool bad = false;
+    for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(q[(size_t)i * k + t]) < 1e17f);
+    if (__ballot(bad) == 0ull) return;
+    for (int w = lane; w < wpq; w += 64) flags[(size_t)i * wpq + w] = 0xFFFFFFFFu;
+}
+
+// grid = (queries of the batch / waves per workgroup) x chunks.  One wave: query i0 + (its row), flag words
+// [c * per, min((c + 1) * per, wpq)).  offs: [m][chunks] (several chunks): count writes the chunk's hits, fill reads the
+// chunk's start within the query's segment.  lims: count writes lims[i + 1] (one chunk), fill reads lims[i], lims[i + 1].
+// stat[0] (count): += the wave's flagged blocks that hold a ref below n.
+template <int VEC, bool FILL>
+__global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int rows, int i0, int n, int per, int chunks,
+                                                                    int wpq, float radius2, const float *__restrict__ q,
+                                                                    const float *__restrict__ r,
+                                                                    const unsigned *__restrict__ flags, int64_t index_base,
+                                                                    int64_t *__restrict__ lims, int *__restrict__ offs,
+                                                                    int *__restrict__ idx, float *__restrict__ dist,
+                                                                    unsigned long long *__restrict__ stat)
+{
+    extern __shared__ __attribute__((aligned(16))) float rm_sq[];   // [waves][k]: each wave's query
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * kRmEvalWaves + wave;
+    if (row >= rows) return;   // (whole waves; no workgroup barrier below)
+    const int64_t i = i0 + row;
+    const int c = blockIdx.y;
+    float *sq = rm_sq + (size_t)wave * k;
+    for (int t = lane; t < k; t += 64) sq[t] = q[(size_t)i * k + t];
+    // (the wave reads only what it wrote itself: LDS operations of one wave complete in order)
+    const unsigned *frow = flags + (size_t)row * wpq;
+    const int w0 = c * per, w1 = w0 + per < wpq ? w0 + per : wpq;
+    const int nblk = (n + 31) >> 5;   // blocks that hold a ref
+    int64_t slot0 = 0, stop = 0;
+    if (FILL) {
+        slot0 = lims[i] + (chunks > 1 ? offs[(size_t)i * chunks + c] : 0);
+        stop = lims[i + 1];
+    }
+    int run = 0;
+    unsigned flagged = 0;
+    for (int wb = w0; wb < w1; wb += 64) {
+        const int w = wb + lane;
+        unsigned word = w < w1 ? frow[w] : 0u;
+        // (bits of blocks past the refs — a void row, padding blocks under an infinite threshold — are dropped)
+        const int first = w << 5;
+        if (first + 32 > nblk) word = first >= nblk ? 0u : word & (0xFFFFFFFFu >> (first + 32 - nblk));
+        flagged += __popc(word);
+        uint64_t live = __ballot(word != 0u);
+        while (live) {   // wave-uniform: the non-empty words of this step, ascending
+            const int src = __builtin_ctzll(live);
+            live &= live - 1;
+            unsigned bits = (unsigned)__shfl((int)word, src);
+            const int blk0 = (wb + src) << 5;
+            while (bits) {   // two set bits per round: the lower block on lanes 0 - 31, the next on lanes 32 - 63
+                const int b0 = __builtin_ctz(bits);
+                bits &= bits - 1;
+                int b1 = -1;
+                if (bits) {
+                    b1 = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                }
+                const int b = lane < 32 ? b0 : b1;
+                const int64_t j = ((int64_t)(blk0 + b) << 5) + (lane & 31);
+                float sum[1] = {__builtin_nanf("")};   // a lane without a ref hits nothing
+                if (b >= 0 && j < n) v0_lane_chains<1, VEC, 8>(k, sq, r + (size_t)j * k, sum);
+                const bool hit = rm_hit(sum[0], radius2);
+                const uint64_t mask = __ballot(hit);
+                if (FILL) {
+                    const int64_t slot = slot0 + run + rm_lanes_below(mask);
+                    // (slot < stop holds whenever the points are those the count saw; the bound keeps a fill after
+                    //  the caller changed them inside the buffers)
+                    if (hit && slot < stop) {
+                        if (idx) idx[slot] = (int)(index_base + j);
+                        if (dist) dist[slot] = sum[0];
+                    }
+                }
+                run += __popcll(mask);
+            }
+        }
+    }
+    if (FILL) return;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) flagged += __shfl_xor((int)flagged, d);
+    if (lane == 0) {
+        if (chunks > 1) offs[(size_t)i * chunks + c] = run;
+        else lims[i + 1] = run;
+        if (flagged) atomicAdd(stat, (unsigned long long)flagged);
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+// the split operators' geometry by tile depth (OpSplitT, filter_mfma.hip): fragment steps per block, query blocks per wave
+static bool rm_geometry(int kt, int *spb, int *qb)
+{
+    switch (kt) {
+    case 16: case 32: case 64: case 128: *spb = kt / 8; *qb = 2; return true;
+    case 256: *spb = 32; *qb = 1; return true;
+    }
+    return false;
+}
+
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p)
+{
+    if (k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    if (k < 8 || k > 256) {
+        set_error("the range-MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    FilterGeom g{};
+    NNS_TRY(filter_plan(k, m, n, false, &g, false, false, true, split_eager));
+    int spb = 0, qb = 0;
+    if (!g.split || !rm_geometry(g.kt, &spb, &qb)) {
+        set_error("the range-MFMA flag: no split-bf16 tile for k = %d", k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    p->kt = g.kt;
+    p->spb = spb;
+    p->qb = qb;
+    p->qw = 32 * qb * kRmWaves;
+    p->n_pad = g.n_pad;
+    p->total_slots = g.total_slots;
+    p->blocks = g.n_pad / 32;
+    p->wpq = divup(p->blocks, 32);
+    p->lazy_img = g.lazy_img;
+    p->lds = kRmLds;
+    if (g.m_pad % p->qw != 0 || g.total_slots != g.n_pad / (32 * (kRmSlotSteps / spb))) {
+        set_error("the range-MFMA flag: the filter's plan does not have the flag pass's geometry (kt = %d)", g.kt);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    // query batches: whole workgroups' worth of rows within the bitmap's cap
+    const size_t row_bytes = (size_t)p->wpq * sizeof(unsigned);
+    const int64_t cap_rows = (int64_t)(kRmFlagBudget / row_bytes) / p->qw * p->qw;
+    if (cap_rows < p->qw) {
+        set_error("the range-MFMA flag: n = %d: one workgroup's flag rows exceed the 256 MiB workspace", n);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    const int64_t m_pad = (int64_t)divup(m, p->qw) * p->qw;
+    p->batch = (int)(m_pad < cap_rows ? m_pad : cap_rows);
+    p->batches = divup(m, p->batch);
+    p->flag_bytes = (size_t)p->batch * row_bytes;
+    p->gx = p->batch / p->qw;
+    // ref-range splits: as filter_plan — one workgroup per CU, so minimise rounds x work per workgroup
+    int splits = 1;
+    double best = 1e30;
+    for (int sp = 1; sp <= 64 && sp <= p->total_slots; ++sp) {
+        const double cost = (double)divup(p->gx * sp, 256) / sp * (1.0 + 0.004 * sp);
+        if (cost < best - 1e-12) {
+            best = cost;
+            splits = sp;
+        }
+    }
+    if (p->gx * splits < 256) splits = divup(256, p->gx);
+    if (splits > p->total_slots) splits = p->total_slots;
+    if (splits > 65535) splits = 65535;
+    p->slots_per_split = divup(p->total_slots, splits);
+    p->gy = divup(p->total_slots, p->slots_per_split);
+    // evaluation: chunks of whole 64-word steps, about 4096 waves
+    int64_t chunks = divup(4096, m);
+    const int steps = divup(p->wpq, kRmChunkWords);
+    if (chunks > steps) chunks = steps;
+    // (K7's workspace rule: [m][chunks] counts within the range workspace's cap)
+    const int64_t by_ws = (int64_t)(((size_t)256 << 20) / ((size_t)m * sizeof(int)));
+    if (chunks > by_ws) chunks = by_ws;
+    if (chunks > 65535) chunks = 65535;
+    if (chunks < 1) chunks = 1;
+    p->eper = divup(steps, (int)chunks) * kRmChunkWords;
+    p->echunks = divup(p->wpq, p->eper);
+    p->tiles = range_scan_tiles(m);
+    p->offs_bytes = p->echunks > 1 ? ((size_t)m * p->echunks * sizeof(int) + 7) & ~(size_t)7 : 0;
+    p->ws_bytes = p->offs_bytes + (p->tiles > 1 ? (size_t)p->tiles * sizeof(int64_t) : 0);
+    return NNS_OK;
+}
+
+template <int SPB, int QB>
+static int launch_flag_t(const RangeMfmaPlan &p, const RangeFlagArgs &a, int gx, hipStream_t st)
+{
+    return launch_lds(range_flag_kernel<SPB, QB>, dim3(gx, p.gy), dim3(kRmWaves * 64), (size_t)kRmLds, st, a);
+}
+
+// the flag pass of one query batch: rows [i0, i0 + rows) of the prepared query image / norms; the bitmap is zeroed on
+// the stream first, void queries' rows are filled behind the pass
+int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
+                       const void *rimg, const float *rnorm, const DevScalars *scal, float radius2, void *flags,
+                       hipStream_t st)
+{
+    const int rows_pad = divup(rows, p.qw) * p.qw;
+    if (i0 % p.qw != 0 || rows_pad > p.batch) return NNS_ERR_INVALID;
+    NNS_HIP(hipMemsetAsync(flags, 0, (size_t)rows_pad * p.wpq * sizeof(unsigned), st));
+    RangeFlagArgs a;
+    a.qimg = reinterpret_cast<const float4 *>(qimg) + (size_t)(i0 / 32) * (p.spb * 64);
+    a.rimg = reinterpret_cast<const char *>(rimg);
+    a.rimg_lo = p.lazy_img ? a.rimg + (size_t)p.n_pad * p.kt * 2 : nullptr;
+    a.rnorm = rnorm;
+    a.qnorm = qnorm + i0;
+    a.scal = scal;
+    a.flags = reinterpret_cast<unsigned *>(flags);
+    a.rows_live = rows;
+    a.wpq = p.wpq;
+    a.total_slots = p.total_slots;
+    a.slots_per_split = p.slots_per_split;
+    a.n_pad = p.n_pad;
+    a.kt = p.kt;
+    a.radius2 = radius2;
+    const int gx = rows_pad / p.qw;
+    switch (p.spb) {
+    case 2: NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st))); break;
+    case 4: NNS_TRY((launch_flag_t<4, 2>(p, a, gx, st))); break;
+    case 8: NNS_TRY((launch_flag_t<8, 2>(p, a, gx, st))); break;
+    case 16: NNS_TRY((launch_flag_t<16, 2>(p, a, gx, st))); break;
+    case 32: NNS_TRY((launch_flag_t<32, 1>(p, a, gx, st))); break;
+    default: return NNS_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(range_void_rows_kernel, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k, rows,
+                       (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+// the evaluation of one query batch (fill: idx / dist; count: the per-(query, chunk) counts and stat[0])
+int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows, int n, const void *q, const void *r,
+                      const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
+                      unsigned long long *stat, hipStream_t st)
+{
+    int *offs = p.echunks > 1 ? (int *)ws : nullptr;
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & 15) == 0);
+    const dim3 grid(divup(rows, kRmEvalWaves), p.echunks);
+    const size_t lds = (size_t)kRmEvalWaves * k * sizeof(float);
+    auto go = [&](auto kern) {
+        return launch_lds(kern, grid, dim3(kRmEvalThreads), lds, st, k, rows, i0, n, p.eper, p.echunks, p.wpq, radius2,
+                          (const float *)q, (const float *)r, (const unsigned *)flags, base, lims, offs, idx, dist, stat);
+    };
+    if (fill) return vec ? go(range_eval_kernel<4, true>) : go(range_eval_kernel<1, true>);
+    return vec ? go(range_eval_kernel<4, false>) : go(range_eval_kernel<1, false>);
+}
+
+}  // namespace nns

@@ -34,6 +34,7 @@ NNS_KEY_NONE = 0x7F80000000000000
 NNS_RECORDS_PER_REF = 512
 NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
 NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three products per tile) at every depth
+NNS_RANGE_MFMA = 4096   # range search through the MFMA flag pass (K7m): fp32 points, split-bf16 operands, 8 <= k <= 256
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -52,6 +53,7 @@ ABI_SYMBOLS = (
     "nns_index_search_topk", "nns_keys_topk_merge", "nns_keys_topk_unpack", "nns_search_f32_topk",
     "nns_search_bf16_topk", "nns_plan_topk",
     "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
+    "nns_index_range_info", "nns_plan_range_mfma", "nns_range_threshold",
 )
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
@@ -138,6 +140,9 @@ def _load() -> ctypes.CDLL:
                                          ctypes.POINTER(ctypes.POINTER(ctypes.c_float)), c_u, c_int]
     lib.nns_search_bf16_range.argtypes = lib.nns_search_f32_range.argtypes
     lib.nns_plan_range.argtypes = [c_int, c_int, c_int, c_int, c_vp, c_int]
+    lib.nns_index_range_info.argtypes = [c_vp, c_vp, c_int]
+    lib.nns_plan_range_mfma.argtypes = [c_int, c_int, c_int, c_u, c_vp, c_int]
+    lib.nns_range_threshold.argtypes = [c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp]
     lib.nns_device_count.argtypes = []
     lib.nns_strerror.argtypes = [c_int]
     lib.nns_strerror.restype = ctypes.c_char_p
@@ -233,6 +238,23 @@ def plan_range(k: int, m: int, n: int, bf16: bool = False) -> dict:
     _check(lib.nns_plan_range(k, m, n, int(bf16), out.ctypes.data, 6), "nns_plan_range")
     names = ("queries_per_wg", "chunks", "per", "workgroups", "lds_bytes", "ws_bytes")
     return dict(zip(names, (int(v) for v in out)))
+
+
+def plan_range_mfma(k: int, m: int, n: int, flags: int = 0) -> dict:
+    """nns_plan_range_mfma: the launch geometry of the MFMA-filtered range search (K7m) for a shape (host only);
+    flags: the index's (NNS_FILTER_SPLIT_EAGER selects the eager ref image layout)."""
+    out = np.zeros(10, np.int32)
+    _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
+    names = ("kt", "block_refs", "blocks_per_query", "batch", "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes",
+             "layout")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def range_threshold(kt: int, qnorm2: float, ymax2: float, radius2: float) -> float:
+    """nns_range_threshold: the score threshold K7m's flag pass gives a query (host only)."""
+    out = np.zeros(1, np.float32)
+    _check(lib.nns_range_threshold(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold")
+    return float(out[0])
 
 
 def selftest_lane_share(values, tile16: bool) -> np.ndarray:
@@ -396,7 +418,7 @@ def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: b
     return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa)
 
 
-def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa):
+def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
     m, k = q.shape
@@ -406,7 +428,8 @@ def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa)
     pdist = ctypes.POINTER(ctypes.c_float)()
     fn = lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
-              ctypes.byref(pdist) if return_distances else None, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0),
+              ctypes.byref(pdist) if return_distances else None,
+              _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_RANGE_MFMA if range_mfma else 0),
               device), "nns_search_range")
     total = int(lims[-1])
     try:
@@ -422,13 +445,14 @@ def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa)
 
 
 def search_range(query_points, reference_points, radius2: float, *, return_distances: bool = False,
-                 path: str = "auto", device: int = 0, refs_soa: bool = False):
+                 path: str = "auto", device: int = 0, refs_soa: bool = False, range_mfma: bool = False):
     """Every reference within squared radius ``radius2`` of each query (nns_search_f32_range), in CSR form:
     (lims int64[m + 1], idx int32[lims[m]][, dist fp32[lims[m]]]); query i's hits are idx[lims[i]:lims[i + 1]] in
-    ascending index order, with their V0 distances (d <= radius2, NaN / +INF never)."""
+    ascending index order, with their V0 distances (d <= radius2, NaN / +INF never).  range_mfma: through the MFMA
+    flag pass (NNS_RANGE_MFMA; 8 <= k <= 256), same results."""
     q = _as_f32(query_points, "query_points")
     r = _as_f32(reference_points, "reference_points")
-    return _search_range(q, r, radius2, False, return_distances, path, device, refs_soa)
+    return _search_range(q, r, radius2, False, return_distances, path, device, refs_soa, range_mfma)
 
 
 def search_range_bf16(query_bits, reference_bits, radius2: float, *, return_distances: bool = False,
@@ -462,10 +486,11 @@ class Index:
 
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
                  soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False,
-                 filter_split_eager: bool = False):
+                 filter_split_eager: bool = False, range_mfma: bool = False):
         """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
         filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
-        filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER)."""
+        filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER).
+        range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA)."""
         import torch
         if refs.dtype not in (torch.float32, torch.bfloat16) or refs.dim() != 2 or not refs.is_contiguous() \
                 or not refs.is_cuda:
@@ -476,7 +501,8 @@ class Index:
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
             | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
-            | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0)
+            | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0) | (NNS_RANGE_MFMA if range_mfma else 0)
+        self.flags = flags
         h = ctypes.c_void_p()
         create = lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
@@ -587,6 +613,13 @@ class Index:
         total = int(lims[-1].item())
         out = self.range_fill(queries, radius2, lims, total=total, return_distances=return_distances, stream=stream)
         return (lims,) + out if return_distances else (lims, out)
+
+    def range_info(self) -> dict:
+        """nns_index_range_info: what the last range_count did — path (1 exact K7, 2 MFMA-filtered), flagged and
+        examined (query, 32-ref block) pairs, total hits.  Waits for the index's stream."""
+        out = np.zeros(4, np.int64)
+        _check(lib.nns_index_range_info(self._h, out.ctypes.data, 4), "nns_index_range_info")
+        return dict(zip(("path", "flagged", "examined", "hits"), (int(v) for v in out)))
 
     def stats(self) -> dict:
         st = nns_stats()
