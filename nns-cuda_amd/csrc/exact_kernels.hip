@@ -780,7 +780,7 @@ __global__ __launch_bounds__(512) void lowdim_filter_kernel(
 #pragma unroll
                 for (int t = 0; t < K; ++t) {
                     const float v = sv[i][t];
-                    bad = bad || !(fabsf(v) < 1e17f);          // NaN, INF, or a square that could overflow
+                    bad = bad || !(fabsf(v) < kHuge);          // NaN, INF, or a square that could overflow
                     yc[t] = __fsub_rn(v, cen[t]);
                     nrm = __builtin_fmaf(yc[t], yc[t], nrm);
                 }

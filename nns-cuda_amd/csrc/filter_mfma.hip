@@ -1494,12 +1494,23 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     //  eager twin's tiles and workgroup)
     static_assert(OpLazySplit::kQB * OpLazySplit::kNW == OpSplit::kQB * OpSplit::kNW, "lazy and eager split: same query groups");
     g->lazy = g->lazy_img = 0;
-    g->lpq = with_filter_op(*g, [](auto op) { return decltype(op)::kTile16 ? 4 : 2; });
-    // queries per workgroup
-    const int qw = with_filter_op(*g, [](auto op) { return 32 * decltype(op)::kQB * decltype(op)::kNW; });
+    // the operator's tile and workgroup (read with lazy = 0: the eager operator, whose blocks the image is made of)
+    NNS_TRY(with_filter_op(*g, [g](auto op) {
+        using OP = decltype(op);
+        // (K7m's flag kernel, range_mfma.hip, takes its workgroup and ring slot from these two constants)
+        if constexpr (OP::kSplit && !OP::kLazy)
+            static_assert(OP::kNW == kSplitWaves && OP::kSlotSteps == kSplitSlotSteps, "the eager split operators' workgroup and slot");
+        g->lpq = OP::kTile16 ? 4 : 2;
+        g->spb = OP::kSPB;
+        g->qb = OP::kQB;
+        g->waves = OP::kNW;
+        g->qw = 32 * OP::kQB * OP::kNW;
+        return (int)NNS_OK;
+    }));
+    const int qw = g->qw;
     g->m_pad = divup(m, qw) * qw;
     // refs per ring slot (32 fragment steps of 8 fp32 / 16 bf16 dims)
-    const int steps_per_block = bf16 ? kt / 16 : kt / 8;
+    const int steps_per_block = g->spb;
     // deep blocks straddle slots: super-periods of `slots_per_block` slots = `pad_pts` refs (1024-deep: 2 slots = one
     // block of 32; 768-deep: 3 slots = two blocks = 64 refs, i.e. 21.33 refs per slot — slot_pts, which only sizes
     // paddings from here on, is rounded up)
@@ -1512,30 +1523,9 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     g->n_pad = divup(n, pad_pts) * pad_pts;
     g->total_slots = g->n_pad / pad_pts * slots_per_block;
     g->qgroups = g->m_pad / qw;
-    // One 8-wave workgroup is resident per CU (132 KiB of LDS), so the grid runs in rounds of
-    // 256 workgroups and a round that is mostly empty costs as much as a full one.  Choose the
-    // number of ref-range splits that minimises rounds x (work per workgroup), i.e.
-    // ceil(qgroups * s / 256) / s, with a small per-split charge (prologue, lists, merge) and a
-    // cap on the candidate-list memory (512 B per lane-list: 1 or 2 KiB per query per split).
-    int splits = 1;
-    {
-        const int64_t list_cap = (int64_t)2 << 30;
-        double best_cost = 1e30;
-        for (int sp = 1; sp <= 64; ++sp) {
-            if (sp > g->total_slots) break;
-            if (sp > 1 && (int64_t)sp * g->m_pad * g->lpq * 512 > list_cap) break;
-            const int rounds = divup(g->qgroups * sp, 256);
-            const double cost = (double)rounds / sp * (1.0 + 0.004 * sp);
-            if (cost < best_cost - 1e-12) {
-                best_cost = cost;
-                splits = sp;
-            }
-        }
-        // very few queries: more splits than the scan above tries, to cover all CUs
-        if (g->qgroups * splits < 256) splits = divup(256, g->qgroups);
-    }
-    if (splits > g->total_slots) splits = g->total_slots;
-    if (splits > 65535) splits = 65535;
+    // ref-range splits: within 2 GiB of candidate lists (512 B per lane-list: 1 or 2 KiB per query per split)
+    const int64_t list_cap = (int64_t)2 << 30;
+    const int splits = ring_pass_splits(g->qgroups, g->total_slots, list_cap / ((int64_t)g->m_pad * g->lpq * 512));
     g->slots_per_split = divup(divup(g->total_slots, splits), slots_per_block) * slots_per_block;   // whole blocks
     g->splits = divup(g->total_slots, g->slots_per_split);
     g->slot_pts = slot_pts;

@@ -66,9 +66,6 @@
 
 namespace nns {
 
-// |value| above this (or NaN/INF) voids the error analysis (squares overflow)
-constexpr unsigned kHugeBits = 0x5BB1A2BCu;   // 1e17f
-
 __device__ __forceinline__ float load_f(const float *p, size_t i) { return p[i]; }
 __device__ __forceinline__ float load_f(const uint16_t *p, size_t i)
 {

@@ -234,6 +234,17 @@ static int prep_refs(nns_index *ix, hipStream_t st)
     return NNS_OK;
 }
 
+// K2's scalars read back on `st` (one host wait), and the latch they decide: refs that void the error bound (NaN /
+// INF / |v| >= 1e17) go straight to the exact kernels
+static int read_scalars(nns_index *ix, hipStream_t st, DevScalars *h)
+{
+    NNS_HIP(hipMemcpyAsync(h, ix->scal, sizeof(*h), hipMemcpyDeviceToHost, st));
+    NNS_HIP(hipStreamSynchronize(st));
+    ix->refs_bad = h->r_maxabs_bits >= kHugeBits;
+    ix->refs_unknown = false;
+    return NNS_OK;
+}
+
 extern "C" {
 
 int nns_version(void) { return NNS_VERSION_MAJOR * 1000 + NNS_VERSION_MINOR; }
@@ -402,13 +413,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             if (flags & kCreateNoSync) break;   // (pipelined whole call: stay asynchronous, K5 checks on the device)
             // index build is synchronous: learn whether the refs void the error bound
             DevScalars h{};
-            if (hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                set_error("nns_index_create: readback failed: %s", hipGetErrorString(hipGetLastError()));
-                rc = NNS_ERR_HIP;
-                break;
-            }
-            ix->refs_bad = h.r_maxabs_bits >= 0x5BB1A2BCu;   // NaN / INF / |v| >= 1e17
+            rc = read_scalars(ix, st, &h);
         }
     } while (0);
     if (rc != NNS_OK) {
@@ -503,10 +508,16 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
     return NNS_OK;
 }
 
-// a search has recorded its events into the current set: close it and move on to the next one
-static void profile_advance(nns_index *ix, int path)
+// The end of every pass of an index (1-NN search, top-K, range count / fill): the profile events from `first` through
+// EV_END (a stage the pass does not have is an empty interval), what the index remembers of its last pass, and the
+// event set closed — the next refresh / search records into the next one
+static void end_pass(nns_index *ix, int m, int path, int first, hipStream_t st)
 {
+    ix->last_m = m;
+    ix->last_path = path;
+    ix->searched = true;
     if (!ix->profile) return;
+    for (int e = first; e <= EV_END; ++e) (void)hipEventRecord(ix->evr[ix->ev_slot][e], st);
     ix->ev_path[ix->ev_slot] = path;
     ix->ev_slot = (ix->ev_slot + 1) % kEvRing;
     ix->ev_refreshed[ix->ev_slot] = false;
@@ -532,14 +543,9 @@ static bool grow_index_ws(T **ws, size_t *have, size_t need, hipStream_t st)
 template <class F>
 static int index_exact_pass(nns_index *ix, int m, hipStream_t st, F &&run)
 {
-    const bool prof = ix->profile;
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
+    if (ix->profile) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
     NNS_TRY(run());
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-    ix->last_m = m;
-    ix->last_path = NNS_PATH_EXACT;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_EXACT);
+    end_pass(ix, m, NNS_PATH_EXACT, EV_END, st);
     return NNS_OK;
 }
 }  // extern "C++"
@@ -612,14 +618,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
     static const bool filter_only = getenv("NNS_DIAG_FILTER_ONLY") != nullptr;
     if (filter_only) {
         NNS_TRY(launch_keys_fill(keys_dev, m, NNS_KEY_NONE, st));
-        if (prof) {
-            (void)hipEventRecord(ix->evr[ix->ev_slot][EV_FINAL], st);
-            (void)hipEventRecord(ix->evr[ix->ev_slot][EV_RERANK], st);
-            (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-        }
-        ix->last_path = NNS_PATH_MFMA;
-        ix->searched = true;
-        profile_advance(ix, NNS_PATH_MFMA);
+        end_pass(ix, m, NNS_PATH_MFMA, EV_FINAL, st);
         return NNS_OK;
     }
 #endif
@@ -630,10 +629,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
                                 keys_dev, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_RERANK], st);
     if (idx_dev) NNS_TRY(launch_keys_unpack(keys_dev, m, idx_dev, dist_dev, st));
-    if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_END], st);
-    ix->last_path = NNS_PATH_MFMA;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_MFMA);
+    end_pass(ix, m, NNS_PATH_MFMA, EV_END, st);
     return NNS_OK;
 }
 
@@ -786,10 +782,7 @@ static int range_mfma_choose(nns_index *ix, int m, float radius2, hipStream_t st
     if (!ix->range_mfma || m < kTinyM || !(radius2 < INFINITY)) return NNS_OK;
     if (ix->refs_unknown) {   // refreshed since the flag was latched: read K2's max-|v| word (one wait on this stream)
         DevScalars h{};
-        NNS_HIP(hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, st));
-        NNS_HIP(hipStreamSynchronize(st));
-        ix->refs_bad = h.r_maxabs_bits >= 0x5BB1A2BCu;
-        ix->refs_unknown = false;
+        NNS_TRY(read_scalars(ix, st, &h));
     }
     if (ix->refs_bad) return NNS_OK;
     *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp) == NNS_OK;
@@ -822,15 +815,7 @@ static int range_mfma_pass(nns_index *ix, const RangeMfmaPlan &mp, bool fill, in
         NNS_TRY(launch_range_lims(m, mp.echunks, mp.tiles, mp.echunks > 1 ? (int *)ix->range_ws : nullptr, sums, lims_dev, st));
         NNS_HIP(hipMemcpyAsync(ix->range_stat + 1, lims_dev + m, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     }
-    if (prof) {
-        (void)hipEventRecord(ev[EV_FINAL], st);
-        (void)hipEventRecord(ev[EV_RERANK], st);
-        (void)hipEventRecord(ev[EV_END], st);
-    }
-    ix->last_m = m;
-    ix->last_path = NNS_PATH_MFMA;
-    ix->searched = true;
-    profile_advance(ix, NNS_PATH_MFMA);
+    end_pass(ix, m, NNS_PATH_MFMA, EV_FINAL, st);
     return NNS_OK;
 }
 
@@ -857,31 +842,26 @@ static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float
             return NNS_ERR_NOMEM;
         }
         NNS_TRY(range_mfma_pass(ix, mp, false, m, q_dev, radius2, lims_dev, nullptr, nullptr, st));
-        ix->range_counted = true;
-        ix->range_m = m;
-        ix->range_q = q_dev;
-        ix->range_r2 = radius2;
-        ix->range_path = NNS_PATH_MFMA;
-        ix->range_examined = (int64_t)m * mp.blocks;
-        return NNS_OK;
+    } else {
+        if (!grow_index_ws(&ix->range_ws, &ix->range_ws_bytes, p.ws_bytes, st)) {
+            set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
+            return NNS_ERR_NOMEM;
+        }
+        NNS_TRY(index_exact_pass(ix, m, st, [&] {
+            return launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st);
+        }));
+        if (ix->range_mfma) {   // (nns_index_range_info: the exact pass's total; no flags were examined)
+            NNS_HIP(hipMemsetAsync(ix->range_stat, 0, sizeof(unsigned long long), st));
+            NNS_HIP(hipMemcpyAsync(ix->range_stat + 1, lims_dev + m, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        }
     }
-    if (!grow_index_ws(&ix->range_ws, &ix->range_ws_bytes, p.ws_bytes, st)) {
-        set_error("nns_index_range_count: workspace allocation failed (%zu bytes)", p.ws_bytes);
-        return NNS_ERR_NOMEM;
-    }
-    NNS_TRY(index_exact_pass(ix, m, st, [&] {
-        return launch_range_count(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, lims_dev, ix->range_ws, st);
-    }));
-    if (ix->range_mfma) {   // (nns_index_range_info: the exact pass's total; no flags were examined)
-        NNS_HIP(hipMemsetAsync(ix->range_stat, 0, sizeof(unsigned long long), st));
-        NNS_HIP(hipMemcpyAsync(ix->range_stat + 1, lims_dev + m, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    }
+    // what the fill may rely on: the count it must match and the path it follows
     ix->range_counted = true;
     ix->range_m = m;
     ix->range_q = q_dev;
     ix->range_r2 = radius2;
-    ix->range_path = NNS_PATH_EXACT;
-    ix->range_examined = 0;
+    ix->range_path = filtered ? NNS_PATH_MFMA : NNS_PATH_EXACT;
+    ix->range_examined = filtered ? (int64_t)m * mp.blocks : 0;
     return NNS_OK;
 }
 
@@ -894,16 +874,17 @@ static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float 
         set_error("nns_index_range_fill: m, q_dev and radius2 must be those of the last nns_index_range_count on this index");
         return NNS_ERR_INVALID;
     }
-    RangePlan p{};
-    NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
-    if (ix->range_path == NNS_PATH_MFMA) {   // (the count's path; its plan depends on k, m, n and the index alone)
+    // (the count's path; either plan depends on k, m, n and the index alone, and the count has made it once already)
+    if (ix->range_path == NNS_PATH_MFMA) {
         RangeMfmaPlan mp{};
         NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp));
         if (!idx_dev && !dist_dev) return NNS_OK;
         return range_mfma_pass(ix, mp, true, m, q_dev, radius2, const_cast<int64_t *>(lims_dev), idx_dev, dist_dev, st);
     }
+    RangePlan p{};
+    NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     return index_exact_pass(ix, m, st, [&] {
         if (!idx_dev && !dist_dev) return (int)NNS_OK;
         return launch_range_fill(p, ix->k, m, ix->n, q_dev, ix->r_dev, ix->bf16, radius2, ix->base, lims_dev,
@@ -996,13 +977,10 @@ int nns_index_stats(nns_index *ix, nns_stats *out)
         }
         // (the index's own stream, not the device: the read-out waits for this index's work only)
         DevScalars h{};
-        NNS_HIP(hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, ix->last_stream));
-        NNS_HIP(hipStreamSynchronize(ix->last_stream));
+        NNS_TRY(read_scalars(ix, ix->last_stream, &h));   // (re-)latch: refs that void the bound go straight to K1
         out->ambiguous = ix->searched && ix->last_path == NNS_PATH_MFMA ? h.amb_count : 0;
         out->multi_candidate = ix->searched && ix->last_path == NNS_PATH_MFMA ? h.multi_count : 0;
-        ix->refs_bad = h.r_maxabs_bits >= 0x5BB1A2BCu;   // (re-)latch: refs that void the bound go straight to K1
-        ix->refs_unknown = false;
-        if (ix->refs_bad || h.q_maxabs_bits >= 0x5BB1A2BCu) out->nonfinite = 1;
+        if (ix->refs_bad || h.q_maxabs_bits >= kHugeBits) out->nonfinite = 1;
     }
     if (ix->profile && ix->ev_valid) {
         NNS_HIP(hipStreamSynchronize(ix->last_stream));

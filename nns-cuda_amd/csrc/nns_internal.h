@@ -138,6 +138,33 @@ static inline LaneScanGrid lane_scan_grid(int k, int m, int n, int qt0, size_t l
     return {qt, qgroups, (int)splits, (int)(per < n ? per : n)};
 }
 
+// The cap of every index-owned search workspace (include/nns.h): top-K's split lists, K7's per-(query, chunk) counts,
+// K7m's flag bitmap of one query batch and its counts
+constexpr size_t kWsBudget = (size_t)256 << 20;
+
+// Ref-range splits of a ring-fed MFMA pass (the filter, K7m's flag pass).  One 8-wave workgroup is resident per CU, so
+// the grid runs in rounds of 256 workgroups and a round that is mostly empty costs as much as a full one: choose the
+// split count (up to 64, and up to max_by_mem beyond the first) that minimises rounds x (work per workgroup), i.e.
+// ceil(qgroups * s / 256) / s, with a charge of 0.4 % per split (prologue, per-split outputs, merge); very few query
+// groups take more splits than that scan tries, to cover all CUs.  At most one split per ring slot and 65535 (grid.y).
+static inline int ring_pass_splits(int qgroups, int total_slots, int64_t max_by_mem = INT64_MAX)
+{
+    int splits = 1;
+    double best_cost = 1e30;
+    for (int sp = 1; sp <= 64 && sp <= total_slots; ++sp) {
+        if (sp > 1 && sp > max_by_mem) break;
+        const double cost = (double)divup(qgroups * sp, 256) / sp * (1.0 + 0.004 * sp);
+        if (cost < best_cost - 1e-12) {
+            best_cost = cost;
+            splits = sp;
+        }
+    }
+    if (qgroups * splits < 256) splits = divup(256, qgroups);
+    if (splits > total_slots) splits = total_slots;
+    if (splits > 65535) splits = 65535;
+    return splits;
+}
+
 // ---- packed keys --------------------------------------------------------------
 // (fp32 bits << 32) | index; distances are >= +0 so integer order == (distance,
 // index) lexicographic order == V0's rule (reference core.cu:44).
@@ -150,6 +177,16 @@ __device__ __forceinline__ nns_key pack_key(float d, uint32_t idx)
 __device__ __forceinline__ nns_key make_key(float best, int64_t idx)
 {
     return (best < __builtin_inff()) ? pack_key(best, (uint32_t)idx) : (nns_key)NNS_KEY_NONE;
+}
+
+// The hit predicate of the range searches (K7, K7m: count and fill must agree on it).  NaN compares false; +INF is
+// excluded explicitly (radius2 may be +INF)
+__device__ __forceinline__ bool range_hit(float d, float radius2) { return d <= radius2 && d < __builtin_inff(); }
+
+// number of set bits of `mask` below the calling lane (the slot of a lane's hit within its wave's ballot)
+__device__ __forceinline__ int lanes_below(uint64_t mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 // ---- V0 arithmetic, spelled so that nothing can contract it -------------------
@@ -266,6 +303,10 @@ constexpr int kBlockPts = 32;
 // lanes a query's candidate lists live on (FilterGeom.lpq, finalize.hip).
 constexpr int kBf16ImageOrder = 1;
 
+// the eager split operators' workgroup and ring slot (OpSplitT; filter_plan asserts them), shared by K7m's flag kernel
+constexpr int kSplitWaves = 8;        // waves per workgroup: two per SIMD
+constexpr int kSplitSlotSteps = 32;   // 1 KiB fragment steps per ring slot
+
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
@@ -274,6 +315,11 @@ struct FilterGeom {
     int lazy;             // split = 1: the lazy schedule (OpLazySplitT: cross products only on tiles near the threshold)
     int lazy_img;         // split = 1: the ref image is in the lazy layout (hi fragments | lo fragments; K2 form 3)
     int kt;               // K of the tile (k padded up with zeros)
+    int spb;              // 1 KiB fragment steps per 32-ref block of the tile image (the operator's kSPB; a lazy search:
+                          // its eager twin's — hi and lo fragments — which is how the image is sized either way)
+    int qb;               // 32-query blocks per wave (kQB)
+    int waves;            // waves per workgroup (kNW)
+    int qw;               // queries per workgroup: 32 * qb * waves
     int m_pad;            // queries padded to the workgroup's query count
     int n_pad;            // refs padded to a whole ring slot
     int total_slots;      // n_pad / (32 * kSlotBlocks)
@@ -456,6 +502,12 @@ __host__ __device__ inline float k1f_threshold(float a, float xn, float y2)
 #pragma clang fp contract(off)
     return a + k1f_tau(a, xn * 1.00001f, y2 * 1.00001f);
 }
+
+// |value| at or above this (or NaN / INF) voids the filters' error analysis (squares overflow): the bound of K5's error
+// model.  K2 keeps the largest |value| as fp32 bits (DevScalars), so the same number in both forms.
+constexpr float kHuge = 1e17f;
+constexpr unsigned kHugeBits = 0x5BB1A2BCu;
+static_assert(__builtin_bit_cast(unsigned, kHuge) == kHugeBits, "kHugeBits is kHuge's bit pattern");
 
 // device-side scalars shared between kernels of one index
 struct DevScalars {

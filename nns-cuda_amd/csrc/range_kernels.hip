@@ -18,20 +18,10 @@ namespace nns {
 
 constexpr int kRangeThreads = 256;
 constexpr int kRangeWaves = kRangeThreads / 64;
-constexpr size_t kRangeWsBudget = (size_t)256 << 20;   // workspace cap (include/nns.h)
 constexpr int kRangeMinPerChunk = 1024;                // refs a chunk sees at least (its query tile load amortises)
 constexpr int kRangeMaxGridX = 1 << 20;                // query groups per grid row (2^28 lanes; the limit is 2^32)
 constexpr int kScanItems = 16;
 constexpr int kScanTile = kRangeThreads * kScanItems;  // query counts per tile of the lims scan
-
-// NaN compares false; +INF is excluded explicitly (radius2 may be +INF)
-__device__ __forceinline__ bool range_hit(float d, float radius2) { return d <= radius2 && d < __builtin_inff(); }
-
-// number of set bits of `mask` below the calling lane
-__device__ __forceinline__ int lanes_below(uint64_t mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // grid = query groups (x, continued in z: one grid dimension holds at most 2^32 lanes) x ref chunks (y).  offs:
 // [m][chunks] (several chunks only): count writes the chunk's hit count, fill reads the chunk's start offset within
@@ -247,7 +237,7 @@ int range_plan(int k, int m, int n, RangePlan *p)
     const int tiles = divup(m, kScanTile);
     const size_t sums_bytes = tiles > 1 ? (size_t)tiles * sizeof(int64_t) : 0;
     const LaneScanGrid g = lane_scan_grid(k, m, n, 16, 0, 0, kRangeMinPerChunk, (size_t)m * sizeof(int),
-                                          kRangeWsBudget - sums_bytes);
+                                          kWsBudget - sums_bytes);
     p->qt = g.qt;
     p->qgroups = g.qgroups;
     p->chunks = g.splits;

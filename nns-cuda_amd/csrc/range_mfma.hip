@@ -20,8 +20,12 @@
 //               prefix.  Blocks, lanes and chunks ascend: index order, no atomics, identical buffers every run.
 // The evaluation alone decides hits; a false flag costs time, never an answer.  Why no hit is missed: DESIGN §4 "K7m".
 //
-// The operator geometry (fragment steps per block, query blocks per wave) repeats OpSplitT's few lines instead of
-// sharing a header with filter_mfma.hip: that file's kernels stay byte for byte what they were.
+// Shared with the rest: the plan's geometry is filter_plan's (FilterGeom: fragment steps per block, query blocks per wave,
+// waves and queries per workgroup, padding and ring slots — the one depth-to-operator table, filter_mfma.hip) and its
+// ref-range splits are ring_pass_splits'; the workgroup and the ring slot are kSplitWaves / kSplitSlotSteps, which
+// filter_mfma.hip asserts of the eager split operators; the hit predicate, the ballot prefix, kHuge and kWsBudget are
+// nns_internal.h's.  The kernel's own: the ring loop below (same schedule as filter_main's, not the same code), the
+// fixed-threshold tile test, the bitmap and the evaluation.
 #include "nns_internal.h"
 
 namespace nns {
@@ -29,25 +33,17 @@ namespace nns {
 typedef float rm_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 rm_bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kRmWaves = 8;                            // waves per workgroup: two per SIMD
-constexpr int kRmSlotSteps = 32;                       // 1 KiB fragments per ring slot
+constexpr int kRmWaves = kSplitWaves;                  // waves per workgroup: two per SIMD
+constexpr int kRmSlotSteps = kSplitSlotSteps;          // 1 KiB fragments per ring slot
 constexpr int kRmRing = 4;                             // ring slots
 constexpr int kRmSlotCoord = kRmSlotSteps * 1024;
 constexpr int kRmSlotBytes = kRmSlotCoord + 2048;      // + the slot's norms (up to 512 refs)
 constexpr int kRmLds = kRmRing * kRmSlotBytes;
 constexpr int kRmAhead = 3;                            // slots in flight ahead of the one being consumed
 constexpr int kRmPpw = kRmSlotSteps / kRmWaves;        // image DMA pieces per wave and slot
-constexpr size_t kRmFlagBudget = (size_t)256 << 20;    // flag bitmap cap (include/nns.h)
 constexpr int kRmEvalThreads = 256;
 constexpr int kRmEvalWaves = kRmEvalThreads / 64;
 constexpr int kRmChunkWords = 64;                      // a chunk of the evaluation is whole 64-word steps
-
-// as range_kernels.hip
-__device__ __forceinline__ bool rm_hit(float d, float radius2) { return d <= radius2 && d < __builtin_inff(); }
-__device__ __forceinline__ int rm_lanes_below(uint64_t mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 __device__ __forceinline__ rm_f32x16 rm_mma(const float4 &a, const float4 &b, rm_f32x16 acc)
 {
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, 
     const int64_t i = (int64_t)blockIdx.x * kRmEvalWaves + (threadIdx.x >> 6);
     if (i >= rows) return;   // (whole waves)
     bool bad = false;
-    for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(q[(size_t)i * k + t]) < 1e17f);
+    for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(q[(size_t)i * k + t]) < kHuge);
     if (__ballot(bad) == 0ull) return;
     for (int w = lane; w < wpq; w += 64) flags[(size_t)i * wpq + w] = 0xFFFFFFFFu;
 }
@@ -279,10 +275,10 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int r
                 const int64_t j = ((int64_t)(blk0 + b) << 5) + (lane & 31);
                 float sum[1] = {__builtin_nanf("")};   // a lane without a ref hits nothing
                 if (b >= 0 && j < n) v0_lane_chains<1, VEC, 8>(k, sq, r + (size_t)j * k, sum);
-                const bool hit = rm_hit(sum[0], radius2);
+                const bool hit = range_hit(sum[0], radius2);
                 const uint64_t mask = __ballot(hit);
                 if (FILL) {
-                    const int64_t slot = slot0 + run + rm_lanes_below(mask);
+                    const int64_t slot = slot0 + run + lanes_below(mask);
                     // (slot < stop holds whenever the points are those the count saw; the bound keeps a fill after
                     //  the caller changed them inside the buffers)
                     if (hit && slot < stop) {
@@ -305,16 +301,6 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int r
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// the split operators' geometry by tile depth (OpSplitT, filter_mfma.hip): fragment steps per block, query blocks per wave
-static bool rm_geometry(int kt, int *spb, int *qb)
-{
-    switch (kt) {
-    case 16: case 32: case 64: case 128: *spb = kt / 8; *qb = 2; return true;
-    case 256: *spb = 32; *qb = 1; return true;
-    }
-    return false;
-}
-
 int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p)
 {
     if (k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
@@ -324,28 +310,23 @@ int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p)
     }
     FilterGeom g{};
     NNS_TRY(filter_plan(k, m, n, false, &g, false, false, true, split_eager));
-    int spb = 0, qb = 0;
-    if (!g.split || !rm_geometry(g.kt, &spb, &qb)) {
+    if (!g.split) {
         set_error("the range-MFMA flag: no split-bf16 tile for k = %d", k);
         return NNS_ERR_UNSUPPORTED;
     }
     p->kt = g.kt;
-    p->spb = spb;
-    p->qb = qb;
-    p->qw = 32 * qb * kRmWaves;
+    p->spb = g.spb;
+    p->qb = g.qb;
+    p->qw = g.qw;
     p->n_pad = g.n_pad;
     p->total_slots = g.total_slots;
     p->blocks = g.n_pad / 32;
     p->wpq = divup(p->blocks, 32);
     p->lazy_img = g.lazy_img;
     p->lds = kRmLds;
-    if (g.m_pad % p->qw != 0 || g.total_slots != g.n_pad / (32 * (kRmSlotSteps / spb))) {
-        set_error("the range-MFMA flag: the filter's plan does not have the flag pass's geometry (kt = %d)", g.kt);
-        return NNS_ERR_UNSUPPORTED;
-    }
     // query batches: whole workgroups' worth of rows within the bitmap's cap
     const size_t row_bytes = (size_t)p->wpq * sizeof(unsigned);
-    const int64_t cap_rows = (int64_t)(kRmFlagBudget / row_bytes) / p->qw * p->qw;
+    const int64_t cap_rows = (int64_t)(kWsBudget / row_bytes) / p->qw * p->qw;
     if (cap_rows < p->qw) {
         set_error("the range-MFMA flag: n = %d: one workgroup's flag rows exceed the 256 MiB workspace", n);
         return NNS_ERR_UNSUPPORTED;
@@ -355,27 +336,14 @@ int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p)
     p->batches = divup(m, p->batch);
     p->flag_bytes = (size_t)p->batch * row_bytes;
     p->gx = p->batch / p->qw;
-    // ref-range splits: as filter_plan — one workgroup per CU, so minimise rounds x work per workgroup
-    int splits = 1;
-    double best = 1e30;
-    for (int sp = 1; sp <= 64 && sp <= p->total_slots; ++sp) {
-        const double cost = (double)divup(p->gx * sp, 256) / sp * (1.0 + 0.004 * sp);
-        if (cost < best - 1e-12) {
-            best = cost;
-            splits = sp;
-        }
-    }
-    if (p->gx * splits < 256) splits = divup(256, p->gx);
-    if (splits > p->total_slots) splits = p->total_slots;
-    if (splits > 65535) splits = 65535;
-    p->slots_per_split = divup(p->total_slots, splits);
+    p->slots_per_split = divup(p->total_slots, ring_pass_splits(p->gx, p->total_slots));
     p->gy = divup(p->total_slots, p->slots_per_split);
     // evaluation: chunks of whole 64-word steps, about 4096 waves
     int64_t chunks = divup(4096, m);
     const int steps = divup(p->wpq, kRmChunkWords);
     if (chunks > steps) chunks = steps;
     // (K7's workspace rule: [m][chunks] counts within the range workspace's cap)
-    const int64_t by_ws = (int64_t)(((size_t)256 << 20) / ((size_t)m * sizeof(int)));
+    const int64_t by_ws = (int64_t)(kWsBudget / ((size_t)m * sizeof(int)));
     if (chunks > by_ws) chunks = by_ws;
     if (chunks > 65535) chunks = 65535;
     if (chunks < 1) chunks = 1;
@@ -418,13 +386,16 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
     a.kt = p.kt;
     a.radius2 = radius2;
     const int gx = rows_pad / p.qw;
-    switch (p.spb) {
-    case 2: NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st))); break;
-    case 4: NNS_TRY((launch_flag_t<4, 2>(p, a, gx, st))); break;
-    case 8: NNS_TRY((launch_flag_t<8, 2>(p, a, gx, st))); break;
-    case 16: NNS_TRY((launch_flag_t<16, 2>(p, a, gx, st))); break;
-    case 32: NNS_TRY((launch_flag_t<32, 1>(p, a, gx, st))); break;
-    default: return NNS_ERR_UNSUPPORTED;
+    // (spb, qb) of the five eager split operators
+    const auto is = [&p](int spb, int qb) { return p.spb == spb && p.qb == qb; };
+    if (is(2, 2)) NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st)));
+    else if (is(4, 2)) NNS_TRY((launch_flag_t<4, 2>(p, a, gx, st)));
+    else if (is(8, 2)) NNS_TRY((launch_flag_t<8, 2>(p, a, gx, st)));
+    else if (is(16, 2)) NNS_TRY((launch_flag_t<16, 2>(p, a, gx, st)));
+    else if (is(32, 1)) NNS_TRY((launch_flag_t<32, 1>(p, a, gx, st)));
+    else {
+        set_error("the range-MFMA flag: no flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
+        return NNS_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(range_void_rows_kernel, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k, rows,
                        (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq);

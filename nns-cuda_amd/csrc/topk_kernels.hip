@@ -23,7 +23,6 @@ constexpr int kTopkThreads = 256;
 constexpr int kTopkQueue = 512;                    // queue capacity per query (keys)
 constexpr int kTopkFlushAt = kTopkQueue - kTopkThreads;   // a queue this full is flushed before the next round
 constexpr size_t kTopkLdsMax = 160 * 1024;
-constexpr size_t kTopkWsBudget = (size_t)256 << 20;   // split workspace at most
 constexpr int kTopkMinPerSplit = 2048;             // refs a split sees at least (so that its list warm-up amortises)
 
 // number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
@@ -227,7 +226,7 @@ int topk_plan(int k, int m, int n, int kn, TopkPlan *p)
     // query-tile width: 16 queries while the lists are short, 8 beyond; ref splits worth their list warm-up
     const LaneScanGrid g = lane_scan_grid(k, m, n, kn <= 16 ? 16 : 8, topk_lds_bytes(1, k, kn), kTopkLdsMax,
                                           kn * 16 > kTopkMinPerSplit ? kn * 16 : kTopkMinPerSplit,
-                                          (size_t)m * kn * sizeof(nns_key), kTopkWsBudget);
+                                          (size_t)m * kn * sizeof(nns_key), kWsBudget);
     p->qt = g.qt;
     p->qgroups = g.qgroups;
     p->splits = g.splits;

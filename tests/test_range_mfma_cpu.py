@@ -2,6 +2,7 @@
 validation before any device is touched, the planner's invariants over a shape grid (batch boundaries included) and the
 flag threshold against the mode-3 error terms recomputed here in fp64."""
 import ctypes
+import json
 import math
 import os
 import re
@@ -107,6 +108,25 @@ def test_plan_range_mfma_invariants(pkg):
     # a batch boundary by hand: 2^20 queries x 70000 refs at k = 8 is 69 words per query: two batches
     p = pkg.plan_range_mfma(8, 1 << 20, 70000)
     assert p["batches"] == 2 and p["batch"] % 512 == 0 and p["batch"] * 69 * 4 <= WS_CAP < (p["batch"] + 512) * 69 * 4
+
+
+def test_plans_are_the_parents(pkg, golden_dir):
+    """nns_plan_range_mfma over the grid of test_plan_range_mfma_invariants, and the two rejected depths: all ten
+    values and the status codes recorded from the commit before the planner took its geometry, its split chooser
+    and its workspace cap from the shared definitions."""
+    with open(os.path.join(golden_dir, "range_mfma_plans_parent.json")) as f:
+        want = {(e["k"], e["m"], e["n"], e["flags"]): (e["status"], e["plan"]) for e in json.load(f)}
+    out = np.zeros(10, np.int32)
+    shapes = [(k, m, n, flags) for k in (8, 16, 17, 64, 128, 129, 256) for m in (64, 65, 513, 4096, 65536, 1 << 20)
+              for n in (33, 1000, 70000, 1 << 20, 1 << 24) for flags in (0, SPLIT_EAGER)]
+    shapes += [(7, 64, 1000, 0), (257, 64, 1000, 0)]
+    assert len(shapes) == 422 and set(shapes) == set(want)
+    for k, m, n, flags in shapes:
+        out[:] = -1
+        status = pkg.lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10)
+        plan = [int(v) for v in out] if status == 0 else None
+        assert (status, plan) == want[(k, m, n, flags)], (k, m, n, flags, status, plan, want[(k, m, n, flags)])
+    assert want[(7, 64, 1000, 0)] == (5, None) and want[(257, 64, 1000, 0)] == (5, None)
 
 
 def test_plan_range_mfma_rejects(pkg):

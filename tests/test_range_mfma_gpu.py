@@ -382,3 +382,98 @@ def test_caller_stream_and_device_restored(pkg):
     ix.close()
     _assert_same(pkg.search_range(q, r, radius2, return_distances=True, range_mfma=True), want, "whole")
     assert torch.cuda.current_device() == dev_before
+
+
+# ---- 14. every pass kind of a profiled index ends in the same bookkeeping -------------------------------------
+STAGES = ("prep_queries_ms", "filter_ms", "finalize_ms", "rerank_ms", "exact_ms")
+
+
+def _check_stats(ix, path, what):
+    """nns_index_stats after one pass: the reported path, every time finite and >= 0, the stages of the pass's path
+    (and only those) within the total.  The stages are consecutive sub-intervals of the total between the same
+    events, so their sum can pass it only by the fp32 roundings of the five elapsed times (2^-24 relative each):
+    1e-5 relative + 1e-6 ms covers them."""
+    st = ix.stats()
+    assert st["path"] == path, (what, st)
+    for name in STAGES + ("prep_refs_ms", "total_ms"):
+        assert np.isfinite(st[name]) and st[name] >= 0.0, (what, name, st)
+    assert st["total_ms"] > 0.0, (what, st)
+    assert sum(st[s] for s in STAGES) <= st["total_ms"] * (1 + 1e-5) + 1e-6, (what, st)
+    if path == MFMA:
+        assert st["exact_ms"] == 0.0, (what, st)
+    else:
+        assert all(st[s] == 0.0 for s in STAGES[:4]), (what, st)
+    return st
+
+
+def test_profiled_index_after_every_pass_kind(pkg):
+    """nns_index_stats and nns_index_range_info after each pass kind on NNS_PROFILE indices: exact 1-NN, MFMA 1-NN,
+    top-K, range count and fill on the exact path (below the filtered path's 64-query floor) and on the filtered path.
+    Expected answers: the V0 oracle, and an exact-path index without either flag.  (nns_stats does not export the
+    query count of the last pass; the filtered count's examined pairs, m x blocks, show it.)"""
+    k, m, n, kn, few = 16, 128, 4096, 8, 32
+    qd = torch.empty((m, k), dtype=torch.float32, device=DEV)
+    rd = torch.empty((n, k), dtype=torch.float32, device=DEV)
+    pkg.fill_uniform(qd, 31)
+    pkg.fill_uniform(rd, 32)
+    torch.cuda.synchronize()
+    q, r = qd.cpu().numpy(), rd.cpu().numpy()
+    d = v0_all(q, r)
+    order = np.argsort(d, axis=1, kind="stable")                 # (distance, index) order: V0's tie rule
+    radius2 = float(np.median(np.take_along_axis(d, order[:, 9:10], axis=1)))   # about ten hits per query
+    want_range = range_oracle(q, r, radius2)
+    want_few = range_oracle(q[:few], r, radius2)
+    assert 5 * m < want_range[0][-1] < 20 * m
+    want_nn = (order[:, 0].astype(np.int32), np.take_along_axis(d, order[:, :1], axis=1)[:, 0])
+    want_topk = (order[:, :kn].astype(np.int32), np.take_along_axis(d, order[:, :kn], axis=1))
+    qfew = qd[:few].contiguous()
+
+    # the exact-path index: the oracle's answers
+    ref = pkg.Index(rd, path="exact")
+    ref_nn = _host(ref.search(qd, return_distances=True))
+    ref_topk = _host(ref.search_topk(qd, kn, return_distances=True))
+    ref_range = _host(ref.search_range(qd, radius2, return_distances=True))
+    ref_few = _host(ref.search_range(qfew, radius2, return_distances=True))
+    ref.close()
+    for got, want in ((ref_nn, want_nn), (ref_topk, want_topk)):
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
+    _assert_same(ref_range, want_range, "exact index")
+    _assert_same(ref_few, want_few, "exact index, few queries")
+
+    def same(got, ref_out, what):                                # (distances by their bits)
+        for a, b in zip(got, ref_out):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), what
+
+    # exact 1-NN
+    ex = pkg.Index(rd, path="exact", profile=True, range_mfma=True)
+    same(_host(ex.search(qd, return_distances=True)), ref_nn, "exact 1-NN")
+    _check_stats(ex, EXACT, "exact 1-NN")
+    ex.close()
+
+    ix = pkg.Index(rd, path="mfma", profile=True, range_mfma=True)
+    # MFMA 1-NN
+    same(_host(ix.search(qd, return_distances=True)), ref_nn, "MFMA 1-NN")
+    st = _check_stats(ix, MFMA, "MFMA 1-NN")
+    assert st["k_tile"] == 16 and st["filter_ms"] > 0.0, st
+    # top-K: an exact pass of the MFMA index
+    same(_host(ix.search_topk(qd, kn, return_distances=True)), ref_topk, "top-K")
+    assert _check_stats(ix, EXACT, "top-K")["exact_ms"] > 0.0
+    # range count and fill, exact path (fewer than 64 queries) and filtered path
+    blocks = pkg.plan_range_mfma(k, m, n)["blocks_per_query"]
+    for what, queries, mm, path, want, ref_out in (("exact range", qfew, few, EXACT, want_few, ref_few),
+                                                   ("filtered range", qd, m, MFMA, want_range, ref_range)):
+        lims = ix.range_count(queries, radius2)
+        _check_stats(ix, path, what + " count")
+        info = ix.range_info()
+        total = int(lims[-1].item())
+        assert info["path"] == path and info["hits"] == total == want[0][-1], (what, info, total)
+        assert info["examined"] == (mm * blocks if path == MFMA else 0), (what, info)
+        if path == MFMA:
+            assert 0 < info["flagged"] <= info["examined"], (what, info)
+        idx, dist = ix.range_fill(queries, radius2, lims, total=total, return_distances=True)
+        _check_stats(ix, path, what + " fill")
+        assert ix.range_info() == info, what                     # the fill leaves the count's record
+        got = _host((lims, idx, dist))
+        _assert_same(got, want, what)
+        same(got, ref_out, what)
+    ix.close()
