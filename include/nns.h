@@ -123,6 +123,12 @@ enum {
                           * distance bits as without the flag.  fp32 points whose filter form is the split one, 8 <= k <=
                           * 256; with bf16 points, NNS_FILTER_F32, NNS_FILTER_BF16 or another k: NNS_ERR_UNSUPPORTED.  Also
                           * accepted by nns_search_f32_range */
+    NNS_TOPK_MFMA = 8192,  /* top-K through the MFMA flag pass (K6m): nns_index_create builds the split-bf16 ref image and norms
+                          * whatever the path bits say (the 1-NN path stays what they say), and nns_index_search_topk bounds
+                          * each query's kn-th distance from a sample of the refs, flags the 32-ref blocks that can hold a ref
+                          * within the bound, and selects among those with V0's arithmetic.  Same keys as without the flag.
+                          * fp32 points whose filter form is the split one, 8 <= k <= 256; with bf16 points, NNS_FILTER_F32,
+                          * NNS_FILTER_BF16 or another k: NNS_ERR_UNSUPPORTED.  Also accepted by nns_search_f32_topk */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -280,7 +286,7 @@ int nns_keys_unpack(const nns_key *keys_dev, int m, int *idx_dev,
 
 /* keys_dev[m][kn] = the kn nearest refs of each query as packed keys, ascending.  q_dev has the index's dtype.
  * Reads the index's point-major refs.  nns_index_stats then reports NNS_PATH_EXACT (with NNS_PROFILE, exact_ms /
- * total_ms cover the scan and merge).  Same one-index-per-stream rule as nns_index_search. */
+ * total_ms cover the scan and merge); an NNS_TOPK_MFMA index: see below.  Same one-index-per-stream rule as nns_index_search. */
 int nns_index_search_topk(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, void *stream);
 /* Per row i of [m][kn]: inout[i] = the kn smallest keys of the union of the ascending rows inout[i] and other[i]
  * (shards with disjoint index ranges): the top-K form of nns_keys_min. */
@@ -290,7 +296,8 @@ int nns_keys_topk_merge(nns_key *inout_dev, const nns_key *other_dev, int m, int
 int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, float *dist_dev, void *stream);
 /* Whole calls: host buffers, idx_out[m][kn], dist_out[m][kn] optional.  num_shards > 1: the V8/V9 contiguous split
  * searched one after another on the one device and merged with nns_keys_topk_merge (as nns_search_f32_ex).  flags:
- * NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE; any other: NNS_ERR_UNSUPPORTED.  Library stream, no
+ * NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and for fp32 points NNS_TOPK_MFMA (below); any other:
+ * NNS_ERR_UNSUPPORTED.  Library stream, no
  * device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is allocated. */
 int nns_search_f32_topk(int k, int m, int n, const float *s_points, const float *r_points, int kn, int *idx_out,
                         float *dist_out, int num_shards, unsigned flags, int device);
@@ -300,6 +307,36 @@ int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const ui
  * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
  * split-workspace keys (0 with one split)}. */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
+
+/* ---- top-K on the matrix cores (NNS_TOPK_MFMA, K6m) -------------------------------
+ * On an index created with NNS_TOPK_MFMA, nns_index_search_topk keeps every contract above (ascending (distance, index)
+ * keys, bit-equal V0 distances, NaN / +INF never selected, NNS_KEY_NONE padding, index_base) and runs in three steps.
+ * Bound: K6's scan over every stride-th 32-ref block gives U_i, the kn-th smallest V0 distance of that sample; the kn-th
+ * smallest over all refs cannot be larger.  Flag: K7m's flag pass with radius2 = U_i per query sets the bit of every
+ * block that can hold a ref with d <= U_i (nns_range_threshold).  Select: V0's distance for the refs of flagged blocks
+ * only, on the original points, the kn smallest keys kept.  The flag bitmap is the one NNS_RANGE_MFMA uses (at most
+ * 256 MiB, query batches beyond), the per-chunk lists use the top-K split workspace; keys_dev holds the sample's rows
+ * in between.  K6 runs instead, decided on the host, when m < 64, the refs hold NaN / INF / |v| >= 1e17, the sample
+ * rule leaves a stride below 2 (few refs for the kn asked), or the flag pass has no plan for the shape.  A QUERY whose
+ * bound is not finite or whose values void the filter's error model gets its flag row filled: its selection is the
+ * exact scan.  nns_index_stats reports NNS_PATH_MFMA after a filtered search; with NNS_PROFILE rerank_ms holds the
+ * bound scan (K6 on the sample), prep_queries_ms K2 on the queries, filter_ms the flag pass, finalize_ms the selection
+ * and merge (several batches: filter_ms covers all but the last batch's selection). */
+
+/* Diagnostic: what the last nns_index_search_topk on this index did.  out[0..3] = {path taken (NNS_PATH_EXACT: K6,
+ * NNS_PATH_MFMA: K6m), flagged (query, 32-ref block) pairs, pairs examined (m x blocks per query), queries whose flag
+ * row was filled}; the last three are 0 on the exact path, all four before any top-K search.  out_len >= 4.  Waits for
+ * the stream the index last worked on (not the device). */
+int nns_index_topk_info(nns_index *ix, int64_t *out, int out_len);
+/* Diagnostic (host only, no device needed): the plan of K6m for a k-D search of m queries over n refs at kn, index flags
+ * `flags`.  out[0..16] = {sample blocks, block stride (0: fewer blocks than the rule asks for), sample refs, filtered
+ * (1: K6m; 0: K6 — stride < 2, m < 64, or no flag-pass plan), then with filtered = 1 (else zeros) the ten fields of
+ * nns_plan_range_mfma, selection chunks per query, flag words per chunk}, and out[16] = LDS bytes of a selection
+ * workgroup.  The sample: sb = max(ceil(sqrt(kn n max(k, 16) / 512)), ceil(max(2048, 16 kn) / 32)) blocks asked for (a
+ * selected ref weighs max(k, 16) / 16 scanned ones; at most every second block unless the unweighted rule asks for more),
+ * stride = floor(ceil(n / 32) / sb), the blocks b with b % stride == 0 taken.  out_len >= 17.  NNS_ERR_UNSUPPORTED for k outside
+ * 8 .. 256, kn above NNS_TOPK_MAX, NNS_FILTER_F32, NNS_FILTER_BF16. */
+int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len);
 
 /* ---- fixed-radius neighbours (range search) -----------------------------------
  * Semantics: a hit of query i is every reference j (global index, index_base added) whose V0 distance d (the value

@@ -66,7 +66,7 @@ static bool auto_exact(unsigned flags, int k, int64_t m, int64_t n, int bf16)
 // deepest dimensionality the MFMA filter tiles (bf16 operands; fp32 operands: 256)
 static const int kMaxFilterK = 1024;
 
-enum { EV_BEGIN = 0, EV_QPREP, EV_FILTER, EV_FINAL, EV_RERANK, EV_END, EV_R0, EV_R1, EV_COUNT };
+enum { EV_BEGIN = 0, EV_QPREP, EV_FILTER, EV_FINAL, EV_RERANK, EV_END, EV_R0, EV_R1, EV_BOUND, EV_COUNT };
 static const int kEvRing = 32;
 
 struct nns_index {
@@ -131,12 +131,26 @@ struct nns_index {
     int range_path = 0;            // 0: no count yet
     int64_t range_examined = 0;
 
+    // NNS_TOPK_MFMA (K6m): the per-query bounds, and what the last top-K search did.  The flag bitmap is K7m's
+    // (range_flags: a K6m pass in between makes a range fill flag again), the counters are range_stat[2 .. 3]
+    bool topk_mfma = false;
+    bool range_flags_stale = false;
+    float *topk_bound = nullptr;
+    size_t topk_bound_cap = 0;
+    int topk_path = 0;             // 0: no top-K search yet
+    int64_t topk_examined = 0;
+
+    // a ref image and K2's scalars exist whatever the 1-NN path (K7m, K6m)
+    bool flag_image() const { return range_mfma || topk_mfma; }
+
     // NNS_PROFILE: a ring of event sets, one per search (refresh + search = one step), so that a
     // caller can time many steps back to back and read the averages once, without a device
     // synchronisation inside every step
     hipEvent_t evr[kEvRing][EV_COUNT] = {};
     bool ev_refreshed[kEvRing] = {};   // set holds a K2-on-refs interval
+    bool ev_bound[kEvRing] = {};       // set holds K6m's bound scan, EV_BEGIN .. EV_BOUND, ahead of K2 on the queries
     int ev_path[kEvRing] = {};         // path of the set's search
+    int ev_last[kEvRing] = {};         // the set's pass ended with this stage event: it and the later ones stand for EV_END
     int ev_slot = 0;                   // set the next refresh / search records into
     int ev_count = 0;                  // searches recorded since the last nns_index_stats
     bool ev_valid = false;
@@ -287,7 +301,7 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     // index's own, still running) are not waited for.  (Round 2: hipDeviceSynchronize() here.)
     void *const blocks[] = {ix->r_own, ix->rimg, ix->rnorm, ix->mean, ix->mean_ws, ix->scal, ix->qimg, ix->qnorm,
                             ix->lists, ix->counts, ix->amb_list, ix->multi_list, ix->exact_ws, ix->topk_ws,
-                            ix->range_ws, ix->range_flags, ix->range_stat};
+                            ix->range_ws, ix->range_flags, ix->range_stat, ix->topk_bound};
     if (stream_idle)
         for (void *b : blocks) pool_free(b);
     else
@@ -323,6 +337,13 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             return NNS_ERR_UNSUPPORTED;
         }
     }
+    if (flags & NNS_TOPK_MFMA) {
+        if (bf16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) || k < 8 || k > 256) {
+            set_error("nns_index_create: the top-K MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256 (k=%d, flags 0x%x)",
+                      k, flags);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    }
     NNS_TRY(ensure_device_ok(device));
     hipStream_t st = (hipStream_t)stream;
 
@@ -337,6 +358,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     ix->bf16 = bf16;
     ix->profile = (flags & NNS_PROFILE) != 0;
     ix->range_mfma = (flags & NNS_RANGE_MFMA) != 0;
+    ix->topk_mfma = (flags & NNS_TOPK_MFMA) != 0;
     ix->last_stream = st;
     {
         const int frc = operand_form(k, bf16 != 0, flags, &ix->mixed, &ix->split);
@@ -387,7 +409,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             }
             ix->ev_valid = true;
         }
-        if (path == NNS_PATH_MFMA || ix->range_mfma) {   // (the range flag builds the image whatever the 1-NN path)
+        if (path == NNS_PATH_MFMA || ix->flag_image()) {   // (the range and top-K flags build the image whatever the 1-NN path)
             if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
                                   (flags & NNS_FILTER_SPLIT_EAGER) != 0)) !=
                 NNS_OK)
@@ -447,10 +469,10 @@ int nns_index_refresh(nns_index *ix, void *stream)
     ix->last_stream = st;
     if (ix->r_soa)   // the caller's dimension-major array may have changed
         NNS_TRY(launch_soa_to_aos(ix->k, ix->n, ix->r_soa, ix->r_own, ix->bf16 ? 2 : 4, st));
-    if (ix->path != NNS_PATH_MFMA && !ix->range_mfma) return NNS_OK;
+    if (ix->path != NNS_PATH_MFMA && !ix->flag_image()) return NNS_OK;
     if (ix->profile) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_R0], st);
     NNS_TRY(prep_refs(ix, st));
-    ix->refs_unknown = ix->range_mfma;
+    ix->refs_unknown = ix->flag_image();
     // The new values may or may not void the error bound (NaN / INF / huge); refresh stays asynchronous,
     // so the next search runs the filter and K5 decides on the device (finalize.hip re-checks K2's max-|v|
     // word and sends every query to the exact scan if it must).  nns_index_stats() re-latches the flag.
@@ -519,8 +541,10 @@ static void end_pass(nns_index *ix, int m, int path, int first, hipStream_t st)
     if (!ix->profile) return;
     for (int e = first; e <= EV_END; ++e) (void)hipEventRecord(ix->evr[ix->ev_slot][e], st);
     ix->ev_path[ix->ev_slot] = path;
+    ix->ev_last[ix->ev_slot] = first;
     ix->ev_slot = (ix->ev_slot + 1) % kEvRing;
     ix->ev_refreshed[ix->ev_slot] = false;
+    ix->ev_bound[ix->ev_slot] = false;
     if (ix->ev_count < kEvRing) ++ix->ev_count;
 }
 
@@ -671,6 +695,54 @@ static int topk_check_kn(const char *where, int kn)
     return NNS_OK;
 }
 
+static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipStream_t st);
+static int ensure_flag_stat(nns_index *ix, hipStream_t st);
+static int latch_refs_bad(nns_index *ix, hipStream_t st);
+
+// K6m: the bound scan over the sample (its rows pass through keys_dev), K2 on the queries, then per query batch the flag
+// pass at the bounds and the selection among the flagged blocks
+static int topk_mfma_pass(nns_index *ix, const TopkMfmaPlan &tp, int m, const void *q_dev, int kn, nns_key *keys_dev,
+                          hipStream_t st)
+{
+    const RangeMfmaPlan &mp = tp.rp;
+    NNS_TRY(ensure_flag_stat(ix, st));
+    if (!grow_index_ws(&ix->topk_ws, &ix->topk_ws_keys, tp.ws_keys, st) ||
+        !grow_index_ws(&ix->range_flags, &ix->range_flags_bytes, mp.flag_bytes, st) ||
+        !grow_index_ws(&ix->topk_bound, &ix->topk_bound_cap, (size_t)m, st)) {
+        set_error("nns_index_search_topk: workspace allocation failed (%zu keys + %zu bytes)", tp.ws_keys, mp.flag_bytes);
+        return NNS_ERR_NOMEM;
+    }
+    const bool prof = ix->profile;
+    hipEvent_t *ev = ix->evr[ix->ev_slot];
+    if (prof) (void)hipEventRecord(ev[EV_BEGIN], st);
+    NNS_TRY(launch_topk_search(tp.sp, ix->k, m, tp.sample_refs, kn, q_dev, ix->r_dev, 0, ix->base, keys_dev, ix->topk_ws, st,
+                               tp.stride));
+    NNS_TRY(launch_topk_bound(keys_dev, m, kn, ix->topk_bound, st));
+    if (prof) (void)hipEventRecord(ev[EV_BOUND], st);
+    ix->ev_bound[ix->ev_slot] = true;
+    NNS_TRY(range_mfma_prep_queries(ix, m, q_dev, st));
+    if (prof) (void)hipEventRecord(ev[EV_QPREP], st);
+    ix->range_flags_stale = true;
+    NNS_HIP(hipMemsetAsync(ix->range_stat + 2, 0, 2 * sizeof(unsigned long long), st));
+    nns_key *out = mp.echunks > 1 ? ix->topk_ws : keys_dev;
+    for (int b = 0; b < mp.batches; ++b) {
+        const int i0 = b * mp.batch;
+        const int rows = m - i0 < mp.batch ? m - i0 : mp.batch;
+        NNS_TRY(launch_range_flags(mp, ix->k, i0, rows, q_dev, ix->qimg, ix->qnorm, ix->rimg, ix->rnorm, ix->scal, 0.0f,
+                                   ix->range_flags, st, ix->topk_bound + i0, ix->range_stat + 3));
+        if (prof && b == mp.batches - 1) (void)hipEventRecord(ev[EV_FILTER], st);
+        NNS_TRY(launch_topk_select(tp, ix->k, i0, rows, m, ix->n, kn, q_dev, ix->r_dev, ix->range_flags, ix->topk_bound,
+                                   ix->base, out, ix->range_stat + 2, st));
+        if (mp.echunks > 1)
+            NNS_TRY(launch_topk_merge_splits(ix->topk_ws + (size_t)i0 * kn, m, rows, kn, mp.echunks,
+                                             keys_dev + (size_t)i0 * kn, st));
+    }
+    ix->topk_path = NNS_PATH_MFMA;
+    ix->topk_examined = (int64_t)m * mp.blocks;
+    end_pass(ix, m, NNS_PATH_MFMA, EV_FINAL, st);
+    return NNS_OK;
+}
+
 static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int kn, nns_key *keys_dev, hipStream_t st)
 {
     if (!ix || !q_dev || !keys_dev || m <= 0) {
@@ -686,6 +758,15 @@ static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int k
     NNS_TRY(topk_plan(ix->k, m, ix->n, kn, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
+    if (ix->topk_mfma) {
+        // K6m when its answer can be trusted and it has something to skip: the plan's conditions, finite refs below 1e17
+        TopkMfmaPlan tp{};
+        NNS_TRY(topk_mfma_plan(ix->k, m, ix->n, kn, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &tp));
+        if (tp.filtered) NNS_TRY(latch_refs_bad(ix, st));
+        if (tp.filtered && !ix->refs_bad) return topk_mfma_pass(ix, tp, m, q_dev, kn, keys_dev, st);
+        ix->topk_path = NNS_PATH_EXACT;
+        ix->topk_examined = 0;
+    }
     if (!grow_index_ws(&ix->topk_ws, &ix->topk_ws_keys, p.ws_keys, st)) {
         set_error("nns_index_search_topk: split workspace allocation failed (%zu keys)", p.ws_keys);
         return NNS_ERR_NOMEM;
@@ -736,6 +817,44 @@ int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int ou
     return NNS_OK;
 }
 
+int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
+{
+    if (!out || out_len < 17 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    NNS_TRY(topk_check_kn("nns_plan_topk_mfma", kn));
+    if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
+    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) {
+        set_error("nns_plan_topk_mfma: the top-K MFMA flag runs on split-bf16 operands only (flags 0x%x)", flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    TopkMfmaPlan t{};
+    NNS_TRY(topk_mfma_plan(k, m, n, kn, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &t));
+    const RangeMfmaPlan &p = t.rp;   // (all zero unless filtered)
+    const int v[17] = {t.sample_blocks, t.stride, t.sample_refs, t.filtered, p.kt, t.filtered ? 32 : 0, p.blocks, p.batch,
+                       p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, p.lazy_img, p.echunks, p.eper, t.lds};
+    memcpy(out, v, sizeof(v));
+    return NNS_OK;
+}
+
+int nns_index_topk_info(nns_index *ix, int64_t *out, int out_len)
+{
+    if (!ix || !out || out_len < 4) {
+        set_error("nns_index_topk_info: bad arguments");
+        return NNS_ERR_INVALID;
+    }
+    out[0] = ix->topk_path;
+    out[1] = out[3] = 0;
+    out[2] = ix->topk_examined;
+    if (ix->topk_path != NNS_PATH_MFMA) return NNS_OK;
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(ix->device));
+    unsigned long long h[2] = {0, 0};
+    NNS_HIP(hipMemcpyAsync(h, ix->range_stat + 2, sizeof(h), hipMemcpyDeviceToHost, ix->last_stream));
+    NNS_HIP(hipStreamSynchronize(ix->last_stream));
+    out[1] = (int64_t)h[0];
+    out[3] = (int64_t)h[1];
+    return NNS_OK;
+}
+
 // ---- range search (K7) ---------------------------------------------------------------------------------------
 // argument checks shared by the split and whole-call entry points (no device touched)
 static int range_check_radius(const char *where, float radius2)
@@ -763,6 +882,18 @@ static int range_check_split(const char *where, nns_index *ix, int m, const void
 }
 
 // ---- K7m: the filtered passes of an NNS_RANGE_MFMA index ---------------------------------------------------------
+// the counters of the flag passes, {K7m: flagged blocks, lims[m]; K6m: flagged blocks, filled rows}, zero at first
+static int ensure_flag_stat(nns_index *ix, hipStream_t st)
+{
+    if (ix->range_stat) return NNS_OK;
+    if (pool_alloc(&ix->range_stat, 4 * sizeof(unsigned long long)) != hipSuccess) {
+        set_error("flag counters: workspace allocation failed");
+        return NNS_ERR_NOMEM;
+    }
+    NNS_HIP(hipMemsetAsync(ix->range_stat, 0, 4 * sizeof(unsigned long long), st));
+    return NNS_OK;
+}
+
 // K2 on the queries, as the 1-NN filter's (the workspaces are shared with it: a fill never relies on them surviving a
 // search in between — one batch keeps its bitmap, several batches prepare the queries again)
 static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipStream_t st)
@@ -774,16 +905,22 @@ static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipS
                              ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st, 2);
 }
 
+// refs_bad as of the last refresh: if the index was refreshed since the flag was latched, read K2's max-|v| word (one
+// wait on this stream)
+static int latch_refs_bad(nns_index *ix, hipStream_t st)
+{
+    if (!ix->refs_unknown) return NNS_OK;
+    DevScalars h{};
+    return read_scalars(ix, st, &h);
+}
+
 // the filtered path runs when its result can be trusted and pays: enough queries for the tiles, finite refs below
 // 1e17, a finite radius, a shape the flag pass plans
 static int range_mfma_choose(nns_index *ix, int m, float radius2, hipStream_t st, RangeMfmaPlan *mp, bool *use)
 {
     *use = false;
     if (!ix->range_mfma || m < kTinyM || !(radius2 < INFINITY)) return NNS_OK;
-    if (ix->refs_unknown) {   // refreshed since the flag was latched: read K2's max-|v| word (one wait on this stream)
-        DevScalars h{};
-        NNS_TRY(read_scalars(ix, st, &h));
-    }
+    NNS_TRY(latch_refs_bad(ix, st));
     if (ix->refs_bad) return NNS_OK;
     *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp) == NNS_OK;
     return NNS_OK;
@@ -796,7 +933,8 @@ static int range_mfma_pass(nns_index *ix, const RangeMfmaPlan &mp, bool fill, in
     const bool prof = ix->profile;
     hipEvent_t *ev = ix->evr[ix->ev_slot];
     if (prof) (void)hipEventRecord(ev[EV_BEGIN], st);
-    const bool prep = !fill || mp.batches > 1;
+    const bool prep = !fill || mp.batches > 1 || ix->range_flags_stale;
+    if (!fill) ix->range_flags_stale = false;
     if (prep) NNS_TRY(range_mfma_prep_queries(ix, m, q_dev, st));
     if (prof) (void)hipEventRecord(ev[EV_QPREP], st);
     if (!fill) NNS_HIP(hipMemsetAsync(ix->range_stat, 0, 2 * sizeof(unsigned long long), st));
@@ -828,10 +966,7 @@ static int index_range_count_impl(nns_index *ix, int m, const void *q_dev, float
     NNS_TRY(range_plan(ix->k, m, ix->n, &p));
     NNS_TRY(ensure_device_ok(ix->device));
     ix->last_stream = st;
-    if (ix->range_mfma && !ix->range_stat && pool_alloc(&ix->range_stat, 2 * sizeof(unsigned long long)) != hipSuccess) {
-        set_error("nns_index_range_count: workspace allocation failed");
-        return NNS_ERR_NOMEM;
-    }
+    if (ix->range_mfma) NNS_TRY(ensure_flag_stat(ix, st));
     RangeMfmaPlan mp{};
     bool filtered = false;
     NNS_TRY(range_mfma_choose(ix, m, radius2, st, &mp, &filtered));
@@ -929,7 +1064,7 @@ int nns_index_range_info(nns_index *ix, int64_t *out, int out_len)
     if (!ix->range_path) return NNS_OK;
     out[2] = ix->range_examined;
     out[3] = -1;   // (an index without NNS_RANGE_MFMA keeps no total)
-    if (!ix->range_stat) return NNS_OK;
+    if (!ix->range_mfma || !ix->range_stat) return NNS_OK;
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(ix->device));
     unsigned long long h[2] = {0, 0};
@@ -970,7 +1105,7 @@ int nns_index_stats(nns_index *ix, nns_stats *out)
     memset(out, 0, sizeof(*out));
     out->path = ix->searched ? ix->last_path : ix->path;
     out->nonfinite = ix->refs_bad ? 1 : 0;
-    if (ix->scal) {   // (an index with a ref image: the MFMA path, or NNS_RANGE_MFMA)
+    if (ix->scal) {   // (an index with a ref image: the MFMA path, NNS_RANGE_MFMA or NNS_TOPK_MFMA)
         if (ix->path == NNS_PATH_MFMA || out->path == NNS_PATH_MFMA) {
             out->k_tile = ix->geom.kt;
             out->splits = ix->geom.splits;
@@ -1006,10 +1141,16 @@ int nns_index_stats(nns_index *ix, nns_stats *out)
                 ++n_refs;
             }
             if (ix->ev_path[set] == NNS_PATH_MFMA) {
-                span(set, EV_BEGIN, EV_QPREP, &acc[1]);
-                span(set, EV_QPREP, EV_FILTER, &acc[2]);
-                span(set, EV_FILTER, EV_FINAL, &acc[3]);
-                span(set, EV_FINAL, EV_RERANK, &acc[4]);
+                // (K6m: its bound scan comes first and is reported as rerank_ms, whose own interval is empty then)
+                // (a pass that ended at an earlier stage recorded its remaining events one after another: its last stage
+                //  runs to EV_END, so that the stages of such a pass add up to the total)
+                const int last = ix->ev_last[set];
+                const auto at = [last](int e) { return e >= last ? (int)EV_END : e; };
+                if (ix->ev_bound[set]) span(set, EV_BEGIN, EV_BOUND, &acc[4]);
+                span(set, ix->ev_bound[set] ? EV_BOUND : EV_BEGIN, at(EV_QPREP), &acc[1]);
+                span(set, at(EV_QPREP), at(EV_FILTER), &acc[2]);
+                span(set, at(EV_FILTER), at(EV_FINAL), &acc[3]);
+                if (at(EV_FINAL) != EV_END) span(set, EV_FINAL, at(EV_RERANK), &acc[4]);
                 ++n_mfma;
             } else {
                 span(set, EV_BEGIN, EV_END, &acc[5]);
@@ -1517,7 +1658,9 @@ static int search_whole(const char *where, int k, int m, int n, const void *s_po
     }));
     flags &= ~(unsigned)NNS_REFS_SOA;   // (the shards index the point-major copy)
     // top-K's shard indexes skip the MFMA filter's ref pre-pass (it reads the point-major refs only)
-    const unsigned create_flags = kn ? NNS_PATH_EXACT | (flags & NNS_PROFILE) | kCreateNoSync : flags;
+    // (NNS_TOPK_MFMA: plus the split-bf16 ref image; that build waits once to learn whether the refs void the error model)
+    const unsigned create_flags =
+        kn ? NNS_PATH_EXACT | (flags & NNS_PROFILE) | ((flags & NNS_TOPK_MFMA) ? (unsigned)NNS_TOPK_MFMA : kCreateNoSync) : flags;
     for (int s = 0; s < num_shards; ++s) {
         const ShardRange sh = shard_range(n, num_shards, s);
         if (sh.cnt <= 0) break;
@@ -1596,7 +1739,11 @@ static int search_topk_host_impl(int k, int m, int n, const void *s_points, cons
         set_error("%s: m * kn too large for one call", where);
         return NNS_ERR_INVALID;
     }
-    NNS_TRY(check_exact_only_flags(where, "top-K", flags));
+    NNS_TRY(check_exact_only_flags(where, "top-K", flags & ~(unsigned)NNS_TOPK_MFMA));
+    if ((flags & NNS_TOPK_MFMA) && (bf16 || k < 8 || k > 256)) {
+        set_error("%s: the top-K MFMA flag takes fp32 points, 8 <= k <= 256 (k=%d)", where, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
     TopkPlan p{};
     NNS_TRY(topk_plan(k, m, n, kn, &p));   // (k beyond the exact path: before any device work)
     DeviceScope keep_device;

@@ -261,6 +261,85 @@ __device__ __forceinline__ void load_query_tile(float *sq, const T *q, int q0, i
     }
 }
 
+// ---- the top-K lists of a workgroup (K6's scan, K6m's selection) ---------------------------------------------------
+constexpr int kTopkThreads = 256;
+constexpr int kTopkQueue = 512;                    // queue capacity per query (keys)
+constexpr int kTopkFlushAt = kTopkQueue - kTopkThreads;   // a queue this full is flushed before the next round
+
+// number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
+__device__ __forceinline__ int tk_rank(const nns_key *a, int len, nns_key v, bool or_equal)
+{
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const nns_key x = a[mid];
+        if (x < v || (or_equal && x == v)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The flush of K6's scan and K6m's selection (topk_mfma.hip), called by all kTopkThreads threads of the workgroup after a
+// barrier that follows the last append: the QT queues (qcnt[u] keys each) are sorted (bitonic, in LDS), merged by rank into
+// the other half of the ping-pong lists [2][QT][kn], `cur` flips, thr[u] becomes list u's kn-th key and the counts are
+// zeroed.  Returns behind a barrier.  Keys are unique within a search, so every rank below is exact.
+template <int QT>
+__device__ __forceinline__ void topk_flush(nns_key *lists, nns_key *queue, int *qcnt, int kn, int &cur, nns_key (&thr)[QT])
+{
+    const int tid = threadIdx.x;
+    int maxc = 0;
+#pragma unroll
+    for (int u = 0; u < QT; ++u) maxc = qcnt[u] > maxc ? qcnt[u] : maxc;
+    if (maxc == 0) return;   // (workgroup-uniform: nothing changes qcnt between the barrier and here)
+    int P = 1;
+    while (P < maxc) P <<= 1;   // <= kTopkQueue
+    nns_key *src = lists + cur * QT * kn, *dst = lists + (cur ^ 1) * QT * kn;
+    for (int e = tid; e < QT * P; e += kTopkThreads) {
+        const int u = e / P, i = e - u * P;
+        if (i >= qcnt[u]) queue[u * kTopkQueue + i] = NNS_KEY_NONE;
+    }
+    for (int e = tid; e < QT * kn; e += kTopkThreads) dst[e] = NNS_KEY_NONE;
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int e = tid; e < QT * (P >> 1); e += kTopkThreads) {
+                const int u = e / (P >> 1), i = e - u * (P >> 1);
+                const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+                nns_key *qq = queue + u * kTopkQueue;
+                const nns_key a = qq[lo], b = qq[hi];
+                const bool up = (lo & size) == 0;
+                if ((a > b) == up) {
+                    qq[lo] = b;
+                    qq[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    // rank merge: an old entry goes before equal queue entries (there are none: keys are unique)
+    for (int e = tid; e < QT * kn; e += kTopkThreads) {
+        const int u = e / kn, i = e - u * kn;
+        const nns_key a = src[e];
+        if (a == NNS_KEY_NONE) continue;
+        const int rk = i + tk_rank(queue + u * kTopkQueue, qcnt[u], a, false);
+        if (rk < kn) dst[u * kn + rk] = a;
+    }
+    const int qtake = P < kn ? P : kn;   // a queue entry at position >= kn cannot land in the first kn
+    for (int e = tid; e < QT * qtake; e += kTopkThreads) {
+        const int u = e / qtake, i = e - u * qtake;
+        if (i >= qcnt[u]) continue;
+        const nns_key b = queue[u * kTopkQueue + i];
+        const int rk = i + tk_rank(src + u * kn, kn, b, true);
+        if (rk < kn) dst[u * kn + rk] = b;
+    }
+    __syncthreads();
+    cur ^= 1;
+#pragma unroll
+    for (int u = 0; u < QT; ++u) thr[u] = dst[u * kn + kn - 1];
+    __syncthreads();   // every thread has read the counts and thresholds before they change
+    if (tid < QT) qcnt[tid] = 0;
+    __syncthreads();
+}
+
 // LDS-DMA (global_load_lds_*): 64 lanes x {16, 4} bytes from per-lane global addresses to
 // LDS at M0 + lane * size, no VGPR destination.  Inline asm on purpose: through the
 // builtin, hipcc (ROCm 7.2) treats every later ds_read as possibly aliasing the
@@ -306,6 +385,8 @@ constexpr int kBf16ImageOrder = 1;
 // the eager split operators' workgroup and ring slot (OpSplitT; filter_plan asserts them), shared by K7m's flag kernel
 constexpr int kSplitWaves = 8;        // waves per workgroup: two per SIMD
 constexpr int kSplitSlotSteps = 32;   // 1 KiB fragment steps per ring slot
+// a chunk of K7m's evaluation and of K6m's selection is whole steps of this many flag words
+constexpr int kRmChunkWords = 64;
 
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
@@ -603,8 +684,11 @@ struct TopkPlan {
 };
 int topk_plan(int k, int m, int n, int kn, TopkPlan *p);
 // keys[m][kn]; ws: p.ws_keys keys (unused with one split)
+// bstride > 1 (K6m's sample): the scan reads every bstride-th 32-ref block of r, n counts the sampled refs
 int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
-                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st);
+                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st, int bstride = 1);
+// rows [0, rows) of ws[splits][m][kn] (m: the row stride of a split) merged into keys[rows][kn]
+int launch_topk_merge_splits(const nns_key *ws, int m, int rows, int kn, int splits, nns_key *keys, hipStream_t st);
 int launch_topk_merge(nns_key *inout, const nns_key *other, int m, int kn, hipStream_t st);
 int launch_topk_unpack(const nns_key *keys, int m, int kn, int *idx, float *dist, hipStream_t st);
 
@@ -645,11 +729,36 @@ struct RangeMfmaPlan {
     size_t offs_bytes, ws_bytes;   // K7's workspace layout: [m][echunks] counts (several chunks), then the tile sums
 };
 int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p);
+// radius2v (optional, K6m): the batch's per-query squared radii, used instead of radius2; a query whose entry is not
+// finite gets its flag row filled like a void query's; filled (optional): += the rows filled
 int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
                        const void *rimg, const float *rnorm, const DevScalars *scal, float radius2, void *flags,
-                       hipStream_t st);
+                       hipStream_t st, const float *radius2v = nullptr, unsigned long long *filled = nullptr);
 int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows, int n, const void *q, const void *r,
                       const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
                       unsigned long long *stat, hipStream_t st);
+
+
+// topk_mfma.hip (K6m: a bound from K6's scan of a block sample, K7m's flag pass at that bound, selection among the
+// flagged blocks)
+struct TopkMfmaPlan {
+    int stride;           // every stride-th 32-ref block is sampled (0: fewer blocks than the sample rule asks for)
+    int sample_blocks;    // blocks the bound scan reads (all of them with stride <= 1)
+    int sample_refs;      // refs in them (the last sampled block may be the refs' partial last block)
+    int filtered;         // 1: K6m runs; 0: K6 (stride < 2, m below the filter's query floor, no flag-pass plan)
+    int lds;              // LDS bytes of a selection workgroup
+    size_t ws_keys;       // the index's top-K workspace: the sample scan's splits, the selection's chunks [echunks][m][kn]
+    TopkPlan sp;          // filtered: K6's plan over the sample
+    RangeMfmaPlan rp;     // filtered: the flag pass (its evaluation chunks are the selection's)
+};
+constexpr int kTopkMfmaMinQueries = 64;   // the filters' query floor
+int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p);
+// bound[i] = the distance of keys[i][kn - 1], +INF for NNS_KEY_NONE
+int launch_topk_bound(const nns_key *keys, int m, int kn, float *bound, hipStream_t st);
+// the selection of one query batch: rows [i0, i0 + rows) of out[chunks][m][kn] (one chunk: the caller's keys); stat: +=
+// the flagged blocks that hold a ref
+int launch_topk_select(const TopkMfmaPlan &p, int k, int i0, int rows, int m, int n, int kn, const void *q, const void *r,
+                       const void *flags, const float *bound, int64_t base, nns_key *out, unsigned long long *stat,
+                       hipStream_t st);
 
 }  // namespace nns

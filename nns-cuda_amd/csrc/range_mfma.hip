@@ -43,7 +43,6 @@ constexpr int kRmAhead = 3;                            // slots in flight ahead 
 constexpr int kRmPpw = kRmSlotSteps / kRmWaves;        // image DMA pieces per wave and slot
 constexpr int kRmEvalThreads = 256;
 constexpr int kRmEvalWaves = kRmEvalThreads / 64;
-constexpr int kRmChunkWords = 64;                      // a chunk of the evaluation is whole 64-word steps
 
 __device__ __forceinline__ rm_f32x16 rm_mma(const float4 &a, const float4 &b, rm_f32x16 acc)
 {
@@ -63,6 +62,7 @@ struct RangeFlagArgs {
     int wpq;                // flag words per query
     int total_slots, slots_per_split, n_pad, kt;
     float radius2;
+    const float *radius2v;  // per-query squared radii of the batch (K6m's bounds); nullptr: radius2 for every query
 };
 
 // SPB: 1 KiB fragment steps per 32-ref block (kt / 8: hi, lo per 16-dim step); QB: 32-query blocks per wave
@@ -94,8 +94,11 @@ __global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFl
             const int qi = (qblk0 + st) * 32 + (lane & 31);
             const float qn = a.qnorm[qi];
             // (padding rows: nothing passes !(s > -INF) but a NaN or -INF score, and their rows are never read.  A norm
-            //  that is not finite comes from a coordinate beyond 1e17: that query's row is filled behind this pass)
-            thr[st] = qi < a.rows_live && qn < __builtin_inff() ? range_threshold(a.kt, qn, ymax2, a.radius2) : -__builtin_inff();
+            //  that is not finite comes from a coordinate beyond 1e17, a per-query radius that is not finite from K6m's
+            //  bound scan: that query's row is filled behind this pass)
+            const bool live = qi < a.rows_live;
+            const float r2 = a.radius2v && live ? a.radius2v[qi] : a.radius2;
+            thr[st] = live && qn < __builtin_inff() && r2 < __builtin_inff() ? range_threshold(a.kt, qn, ymax2, r2) : -__builtin_inff();
             row[st] = a.flags + (size_t)qi * a.wpq;
         }
     }
@@ -205,17 +208,22 @@ __global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFl
     }
 }
 
-// one wave per query of the batch: a non-finite coordinate or |v| >= 1e17 fills the query's flag row
+// one wave per query of the batch: a non-finite coordinate or |v| >= 1e17 — or, with per-query radii, a radius that is
+// not finite — fills the query's flag row; filled (optional): += 1 per filled row
 __global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, int rows, const float *__restrict__ q,
-                                                                         unsigned *__restrict__ flags, int wpq)
+                                                                         unsigned *__restrict__ flags, int wpq,
+                                                                         const float *__restrict__ radius2v,
+                                                                         unsigned long long *__restrict__ filled)
 {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * kRmEvalWaves + (threadIdx.x >> 6);
     if (i >= rows) return;   // (whole waves)
     bool bad = false;
     for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(q[(size_t)i * k + t]) < kHuge);
+    if (radius2v) bad = bad || !(radius2v[i] < __builtin_inff());
     if (__ballot(bad) == 0ull) return;
     for (int w = lane; w < wpq; w += 64) flags[(size_t)i * wpq + w] = 0xFFFFFFFFu;
+    if (filled && lane == 0) atomicAdd(filled, 1ull);
 }
 
 // grid = (queries of the batch / waves per workgroup) x chunks.  One wave: query i0 + (its row), flag words
@@ -365,7 +373,7 @@ static int launch_flag_t(const RangeMfmaPlan &p, const RangeFlagArgs &a, int gx,
 // the stream first, void queries' rows are filled behind the pass
 int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
                        const void *rimg, const float *rnorm, const DevScalars *scal, float radius2, void *flags,
-                       hipStream_t st)
+                       hipStream_t st, const float *radius2v, unsigned long long *filled)
 {
     const int rows_pad = divup(rows, p.qw) * p.qw;
     if (i0 % p.qw != 0 || rows_pad > p.batch) return NNS_ERR_INVALID;
@@ -385,6 +393,7 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
     a.n_pad = p.n_pad;
     a.kt = p.kt;
     a.radius2 = radius2;
+    a.radius2v = radius2v;
     const int gx = rows_pad / p.qw;
     // (spb, qb) of the five eager split operators
     const auto is = [&p](int spb, int qb) { return p.spb == spb && p.qb == qb; };
@@ -398,7 +407,7 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
         return NNS_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(range_void_rows_kernel, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k, rows,
-                       (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq);
+                       (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v, filled);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }

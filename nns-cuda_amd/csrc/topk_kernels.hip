@@ -19,24 +19,8 @@
 
 namespace nns {
 
-constexpr int kTopkThreads = 256;
-constexpr int kTopkQueue = 512;                    // queue capacity per query (keys)
-constexpr int kTopkFlushAt = kTopkQueue - kTopkThreads;   // a queue this full is flushed before the next round
 constexpr size_t kTopkLdsMax = 160 * 1024;
 constexpr int kTopkMinPerSplit = 2048;             // refs a split sees at least (so that its list warm-up amortises)
-
-// number of entries of the sorted row a[0..len) below v (strict), or at most v (or_equal)
-__device__ __forceinline__ int tk_rank(const nns_key *a, int len, nns_key v, bool or_equal)
-{
-    int lo = 0, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const nns_key x = a[mid];
-        if (x < v || (or_equal && x == v)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 static size_t topk_lds_bytes(int qt, int k, int kn)
 {
@@ -45,8 +29,10 @@ static size_t topk_lds_bytes(int qt, int k, int kn)
 }
 
 // LDS: list[2][QT][kn] (ping-pong), queue[QT][kTopkQueue], then the fp32 query tile [QT][k]
+// bstride: the scan's ref j is row (j / 32) * bstride * 32 + j % 32 of r — every bstride-th 32-ref block (K6m's sample,
+// topk_mfma.hip; n then counts the sampled refs).  1: r's rows as they are.
 template <int QT, int VEC, typename T>
-__global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, int n, int per, int kn,
+__global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, int n, int per, int kn, int bstride,
                                                                  const T *__restrict__ q, const T *__restrict__ r,
                                                                  int64_t index_base, nns_key *__restrict__ out)
 {
@@ -76,10 +62,11 @@ __global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, i
         int near_full = 0;
         if (j < j1) {
             float sum[QT];
-            v0_lane_chains<QT, VEC, kLaneScanUnroll<QT>>(k, sq, r + (size_t)j * k, sum);
+            const int jr = bstride == 1 ? j : ((j >> 5) * bstride << 5) + (j & 31);
+            v0_lane_chains<QT, VEC, kLaneScanUnroll<QT>>(k, sq, r + (size_t)jr * k, sum);
 #pragma unroll
             for (int u = 0; u < QT; ++u) {
-                const nns_key key = make_key(sum[u], index_base + j);   // NaN / +INF -> NNS_KEY_NONE: never below thr
+                const nns_key key = make_key(sum[u], index_base + jr);   // NaN / +INF -> NNS_KEY_NONE: never below thr
                 if (key < thr[u]) {
                     const int pos = atomicAdd(&qcnt[u], 1);
                     queue[u * kTopkQueue + pos] = key;
@@ -91,58 +78,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_scan_kernel(int k, int m, i
         const bool flush = __syncthreads_or(near_full) || rd == rounds - 1;
         if (!flush) continue;
 
-        // ---- flush: sort the queues, merge them into the lists, lower the thresholds --------------------------
-        int maxc = 0;
-#pragma unroll
-        for (int u = 0; u < QT; ++u) maxc = qcnt[u] > maxc ? qcnt[u] : maxc;
-        if (maxc == 0) continue;   // (workgroup-uniform: nothing changes qcnt between the barrier and here)
-        int P = 1;
-        while (P < maxc) P <<= 1;   // <= kTopkQueue
-        nns_key *src = lists + cur * QT * kn, *dst = lists + (cur ^ 1) * QT * kn;
-        for (int e = tid; e < QT * P; e += kTopkThreads) {
-            const int u = e / P, i = e - u * P;
-            if (i >= qcnt[u]) queue[u * kTopkQueue + i] = NNS_KEY_NONE;
-        }
-        for (int e = tid; e < QT * kn; e += kTopkThreads) dst[e] = NNS_KEY_NONE;
-        __syncthreads();
-        for (int size = 2; size <= P; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int e = tid; e < QT * (P >> 1); e += kTopkThreads) {
-                    const int u = e / (P >> 1), i = e - u * (P >> 1);
-                    const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
-                    nns_key *qq = queue + u * kTopkQueue;
-                    const nns_key a = qq[lo], b = qq[hi];
-                    const bool up = (lo & size) == 0;
-                    if ((a > b) == up) {
-                        qq[lo] = b;
-                        qq[hi] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        // rank merge: an old entry goes before equal queue entries (there are none: keys are unique)
-        for (int e = tid; e < QT * kn; e += kTopkThreads) {
-            const int u = e / kn, i = e - u * kn;
-            const nns_key a = src[e];
-            if (a == NNS_KEY_NONE) continue;
-            const int rk = i + tk_rank(queue + u * kTopkQueue, qcnt[u], a, false);
-            if (rk < kn) dst[u * kn + rk] = a;
-        }
-        const int qtake = P < kn ? P : kn;   // a queue entry at position >= kn cannot land in the first kn
-        for (int e = tid; e < QT * qtake; e += kTopkThreads) {
-            const int u = e / qtake, i = e - u * qtake;
-            if (i >= qcnt[u]) continue;
-            const nns_key b = queue[u * kTopkQueue + i];
-            const int rk = i + tk_rank(src + u * kn, kn, b, true);
-            if (rk < kn) dst[u * kn + rk] = b;
-        }
-        __syncthreads();
-        cur ^= 1;
-#pragma unroll
-        for (int u = 0; u < QT; ++u) thr[u] = dst[u * kn + kn - 1];
-        __syncthreads();   // every thread has read the counts and thresholds before they change
-        if (tid < QT) qcnt[tid] = 0;
-        __syncthreads();
+        topk_flush<QT>(lists, queue, qcnt, kn, cur, thr);
     }
 
     const nns_key *fin = lists + cur * QT * kn;
@@ -237,30 +173,34 @@ int topk_plan(int k, int m, int n, int kn, TopkPlan *p)
 }
 
 template <typename T>
-static int launch_topk_scan(const TopkPlan &p, int k, int m, int n, int kn, const T *q, const T *r, int64_t base,
-                            nns_key *out, hipStream_t st)
+static int launch_topk_scan(const TopkPlan &p, int k, int m, int n, int kn, int bstride, const T *q, const T *r,
+                            int64_t base, nns_key *out, hipStream_t st)
 {
     const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
     return with_qt<16, 8, 4, 2, 1>(p.qt, [&](auto qt) {
         constexpr int QT = decltype(qt)::value;
         return launch_lds(vec ? topk_scan_kernel<QT, 4, T> : topk_scan_kernel<QT, 1, T>, dim3(p.qgroups, p.splits),
-                          dim3(kTopkThreads), topk_lds_bytes(QT, k, kn), st, k, m, n, p.per, kn, q, r, base, out);
+                          dim3(kTopkThreads), topk_lds_bytes(QT, k, kn), st, k, m, n, p.per, kn, bstride, q, r, base, out);
     });
 }
 
 int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
-                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st)
+                       int64_t base, nns_key *keys, nns_key *ws, hipStream_t st, int bstride)
 {
     nns_key *scan_out = p.splits > 1 ? ws : keys;
     if (bf16)
-        NNS_TRY(launch_topk_scan<uint16_t>(p, k, m, n, kn, (const uint16_t *)q, (const uint16_t *)r, base, scan_out, st));
+        NNS_TRY(launch_topk_scan<uint16_t>(p, k, m, n, kn, bstride, (const uint16_t *)q, (const uint16_t *)r, base, scan_out, st));
     else
-        NNS_TRY(launch_topk_scan<float>(p, k, m, n, kn, (const float *)q, (const float *)r, base, scan_out, st));
-    if (p.splits > 1) {
-        const int threads = (kn + 63) / 64 * 64;
-        hipLaunchKernelGGL(topk_merge_splits_kernel, dim3(m, p.splits), dim3(threads), 0, st, ws, m, kn, p.splits, keys);
-        NNS_HIP(hipGetLastError());
-    }
+        NNS_TRY(launch_topk_scan<float>(p, k, m, n, kn, bstride, (const float *)q, (const float *)r, base, scan_out, st));
+    if (p.splits > 1) NNS_TRY(launch_topk_merge_splits(ws, m, m, kn, p.splits, keys, st));
+    return NNS_OK;
+}
+
+int launch_topk_merge_splits(const nns_key *ws, int m, int rows, int kn, int splits, nns_key *keys, hipStream_t st)
+{
+    const int threads = (kn + 63) / 64 * 64;
+    hipLaunchKernelGGL(topk_merge_splits_kernel, dim3(rows, splits), dim3(threads), 0, st, ws, m, kn, splits, keys);
+    NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
 

@@ -35,6 +35,7 @@ NNS_RECORDS_PER_REF = 512
 NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
 NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three products per tile) at every depth
 NNS_RANGE_MFMA = 4096   # range search through the MFMA flag pass (K7m): fp32 points, split-bf16 operands, 8 <= k <= 256
+NNS_TOPK_MFMA = 8192    # top-K through the bound / flag / select path (K6m): fp32 points, split-bf16 operands, 8 <= k <= 256
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -54,6 +55,7 @@ ABI_SYMBOLS = (
     "nns_search_bf16_topk", "nns_plan_topk",
     "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
     "nns_index_range_info", "nns_plan_range_mfma", "nns_range_threshold",
+    "nns_index_topk_info", "nns_plan_topk_mfma",
 )
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
@@ -143,6 +145,8 @@ def _load() -> ctypes.CDLL:
     lib.nns_index_range_info.argtypes = [c_vp, c_vp, c_int]
     lib.nns_plan_range_mfma.argtypes = [c_int, c_int, c_int, c_u, c_vp, c_int]
     lib.nns_range_threshold.argtypes = [c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp]
+    lib.nns_index_topk_info.argtypes = [c_vp, c_vp, c_int]
+    lib.nns_plan_topk_mfma.argtypes = [c_int, c_int, c_int, c_int, c_u, c_vp, c_int]
     lib.nns_device_count.argtypes = []
     lib.nns_strerror.argtypes = [c_int]
     lib.nns_strerror.restype = ctypes.c_char_p
@@ -247,6 +251,18 @@ def plan_range_mfma(k: int, m: int, n: int, flags: int = 0) -> dict:
     _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
     names = ("kt", "block_refs", "blocks_per_query", "batch", "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes",
              "layout")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def plan_topk_mfma(k: int, m: int, n: int, kn: int, flags: int = 0) -> dict:
+    """nns_plan_topk_mfma: the plan of the MFMA-filtered top-K search (K6m) for a shape (host only): the block sample of
+    the bound scan, whether the filtered path is taken, and then plan_range_mfma's fields, the selection's chunks per
+    query and flag words per chunk (zeros otherwise), and the LDS bytes of a selection workgroup."""
+    out = np.zeros(17, np.int32)
+    _check(lib.nns_plan_topk_mfma(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma")
+    names = ("sample_blocks", "stride", "sample_refs", "filtered", "kt", "block_refs", "blocks_per_query", "batch",
+             "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes", "layout", "chunks", "chunk_words",
+             "select_lds_bytes")
     return dict(zip(names, (int(v) for v in out)))
 
 
@@ -385,7 +401,7 @@ def search_bf16(query_bits, reference_bits, *, return_distances: bool = False, s
     return (idx, dist) if return_distances else idx
 
 
-def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa):
+def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa, topk_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
     m, k = q.shape
@@ -394,18 +410,20 @@ def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_so
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
     fn = lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
-              shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0), device), "nns_search_topk")
+              shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
+           "nns_search_topk")
     return (idx, dist) if return_distances else idx
 
 
 def search_topk(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
-                path: str = "auto", device: int = 0, refs_soa: bool = False):
+                path: str = "auto", device: int = 0, refs_soa: bool = False, topk_mfma: bool = False):
     """The kn nearest references of every query (nns_search_f32_topk): int32 [m][kn] indices in ascending
     (V0 distance, index) order, -1 where fewer than kn references are selectable; optionally the fp32 distances
-    (+INF in those slots).  ``shards`` > 1 rehearses the contiguous ref split merged with keys_topk_merge."""
+    (+INF in those slots).  ``shards`` > 1 rehearses the contiguous ref split merged with keys_topk_merge.
+    topk_mfma: through the bound / flag / select path (NNS_TOPK_MFMA; 8 <= k <= 256), same results."""
     q = _as_f32(query_points, "query_points")
     r = _as_f32(reference_points, "reference_points")
-    return _search_topk(q, r, kn, False, return_distances, shards, path, device, refs_soa)
+    return _search_topk(q, r, kn, False, return_distances, shards, path, device, refs_soa, topk_mfma)
 
 
 def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: bool = False, shards: int = 1,
@@ -486,11 +504,12 @@ class Index:
 
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
                  soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False,
-                 filter_split_eager: bool = False, range_mfma: bool = False):
+                 filter_split_eager: bool = False, range_mfma: bool = False, topk_mfma: bool = False):
         """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
         filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
         filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER).
-        range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA)."""
+        range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA).
+        topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA)."""
         import torch
         if refs.dtype not in (torch.float32, torch.bfloat16) or refs.dim() != 2 or not refs.is_contiguous() \
                 or not refs.is_cuda:
@@ -501,7 +520,8 @@ class Index:
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
             | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
-            | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0) | (NNS_RANGE_MFMA if range_mfma else 0)
+            | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0) | (NNS_RANGE_MFMA if range_mfma else 0) \
+            | (NNS_TOPK_MFMA if topk_mfma else 0)
         self.flags = flags
         h = ctypes.c_void_p()
         create = lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
@@ -564,6 +584,13 @@ class Index:
         """The kn nearest refs of every query: int32 [m][kn] (-1 in unfilled slots), optionally fp32 distances."""
         keys = self.search_topk_keys(queries, kn, stream=stream)
         return keys_topk_unpack(keys, return_distances=return_distances, stream=stream)
+
+    def topk_info(self) -> dict:
+        """nns_index_topk_info: what the last top-K search did — path (1 exact K6, 2 MFMA-filtered K6m), flagged and
+        examined (query, 32-ref block) pairs, queries whose flag row was filled.  Waits for the index's stream."""
+        out = np.zeros(4, np.int64)
+        _check(lib.nns_index_topk_info(self._h, out.ctypes.data, 4), "nns_index_topk_info")
+        return dict(zip(("path", "flagged", "examined", "filled"), (int(v) for v in out)))
 
     def _check_queries(self, queries):
         if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
