@@ -434,6 +434,14 @@ int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const fl
 /* The same tile in the order of the lazy split filter: the kt / 16 hi.hi MFMAs first — out_hh (optional) = the
  * accumulator at that point — then hi.lo and lo.hi of every 16-dim step on the same accumulator: out. */
 int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *c0, float *out, float *out_hh);
+/* The lazy split filter's chain on v_mfma_f32_16x16x32_bf16 (KT = 128): one wave, 32 refs x 64 queries.  q[64][128],
+ * r[32][128], c0[32] are HOST fp32 buffers; the operands are taken from split images written in the 32x32x16 operand
+ * order (as K2 writes them) through the kernel's own gather.  out_hh[ref][query] = the accumulator, seeded with c0[ref],
+ * after the four hi.hi MFMAs; out[ref][query] = after rh.ql and rl.qh of every 32-dim step on top.  [32][64] each. */
+int nns_selftest_mfma_lazy16(const float *q, const float *r, const float *c0, float *out, float *out_hh);
+/* Diagnostic (host only): the MFMA tile of the lazy split kernel this build launches — 16 (v_mfma_f32_16x16x32_bf16, the
+ * default) or 32 (v_mfma_f32_32x32x16_bf16, a build with -DNNS_F_LAZY_T16=0).  Plans, images and lists are the same. */
+int nns_filter_lazy_tile(void);
 /* Diagnostic (host only, no device needed): the launch geometry the MFMA filter would use for a k-D search of
  * m queries over n refs.  out[0..11] = {tile depth kt, bf16 operands, fp32 points rounded to bf16 operands,
  * candidate lists per query, m_pad, n_pad, ring slots in total, ref-range splits (grid.y), slots per split,

@@ -53,6 +53,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 #include "nns_internal.h"
 
@@ -140,6 +141,7 @@ struct OpBase {
     static constexpr int kRingDepth = 4;      // ring slots
     static constexpr bool kDmaBurst = false;  // a slot's ring DMA pieces one per step (true: back to back, see the interval)
     static constexpr bool kTile16 = false;    // 32x32 MFMA tiles: a lane owns one query per query block
+    static constexpr int kLPQ = 2;            // candidate lists (list lanes) per query and split: FilterGeom.lpq
     // the lanes' tau constants (c0, x2 per state) stay in registers: an LDS round trip on the slow path
     // queues behind the whole workgroup's fragment reads (measured: ~900 cycles each under this load)
     static constexpr bool kTauInRegs = true;
@@ -248,6 +250,7 @@ template <int SPB_, int NW_ = 8, int QB_ = 2>
 struct OpBF16T : OpBase {
     static constexpr int kSPB = SPB_;         // 16: KT = 256 (8 k-steps per 16-ref tile); 8: KT = 128 (4 k-steps); 32: KT = 512
     static constexpr bool kTile16 = true;
+    static constexpr int kLPQ = 4;            // every lane keeps the lists of its own rows
     static constexpr bool kLag = false;       // lock-step SIMD partners (lagging them: +1..4 % time on C5)
     static constexpr bool kTauInRegs = false; // 222-234 VGPRs: the four states' constants live in LDS (read on the slow path)
     using Acc = AccSet16;
@@ -343,6 +346,22 @@ struct OpLazySplitT : OpMma32x16 {
     static constexpr int kQB = QB_;
 };
 using OpLazySplit = OpLazySplitT<8, 2>;   // KT = 128: C3
+
+// The lazy schedule on v_mfma_f32_16x16x32_bf16 (KT = 128): OpBF16K128's step (t16_step: in-place asm MFMAs, the
+// retiring tile's minima behind the other tile's MFMAs, one cold branch) over OpLazySplitT's ring (16-step slots of hi
+// fragments, eight deep), reading the SAME image — K2 form 3, whose fragments are in the 32x32x16 operand order — with a
+// per-lane gather (lazy16_gather, nns_internal.h): a 16x16x32 operand of ref tile t, k-step ks is 16 bytes per lane out
+// of the two adjacent 1 KiB fragments 2 ks, 2 ks + 1, every byte of the slot still read once per wave, and each
+// ds_read_b128 lane group covers one 256-byte bank row exactly once.  The masks compare the hi-hi minima against
+// fl(thr + B); a flagged (ref tile, state) gets its cross products on 16x16x32 too (t16_refine).  A query sits on four
+// lanes g = 0 .. 3; the lists stay two per query (kLPQ = 2: the plan, the list format and K5 are OpLazySplit's), owned by
+// the lanes with even g, to which lane g ^ 1 hands its refined scores through a row swap.
+struct OpLazySplit16 : OpBF16T<8> {
+    static constexpr int kSlotSteps = 16;
+    static constexpr int kRingDepth = 8;
+    static constexpr bool kLazy = true;
+    static constexpr int kLPQ = 2;
+};
 
 // min over the lanes that carry the same query: l ^ 32 (32x32 tiles), and l ^ 16 too (16x16 tiles).  Row
 // swaps (v_permlane32_swap / v_permlane16_swap, gfx950), not ds_bpermute: no LDS round trip on the slow
@@ -456,6 +475,11 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     constexpr int QPS = T16 ? 16 : 32;          // queries per state
     constexpr int QFB = LAZY ? 2 * SPB : SPB;   // query fragments per 32-query block (lazy: qh and ql of each hi step)
     constexpr int NBQ = T16 ? SPB / 2 : QFB;    // resident operand fragments per state
+    // the lazy schedule on 16x16 tiles (OpLazySplit16): gathered operands, two lists per query
+    constexpr bool L16 = LAZY && T16;
+    static_assert(!L16 || (OP::kLPQ == 2 && QB == 2 && SPB == 8), "OpLazySplit16: KT = 128, four states, two lists per query");
+    static_assert(L16 || OP::kLPQ == (T16 ? 4 : 2), "list lanes per query: the lanes a query sits on");
+    const int g16 = lane >> 4, i16 = lane & 15;   // (16x16 tiles: the lane's row quarter and query column)
 
     // ---- resident B operands: this wave's QB x 32 queries, all of K (128 VGPRs at QB = 2) ----
     float4 bq[NS][NBQ];
@@ -468,7 +492,11 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
 #pragma unroll
-            for (int b = 0; b < NBQ; ++b) bq[st][b] = src[(st * NBQ + b) * 64];
+            for (int b = 0; b < NBQ; ++b) {
+                // (L16: qh of query tile st, k-step b, gathered out of query block st / 2's interleaved qh | ql fragments)
+                if constexpr (L16) bq[st][b] = a.qimg[(size_t)(qblk0 + (st >> 1)) * (QFB * 64) + lazy16_gather(lane, st & 1, b, 2, 0)];
+                else bq[st][b] = src[(st * NBQ + b) * 64];
+            }
             // (record form 2 keeps no thresholds: skip the margin's double-precision arithmetic, ~1 us of a short stream)
             if (T16 || a.tile_rec != 2)
                 tc[st] = tau_consts(a.kt, a.qnorm[qblk0 * 32 + st * QPS + (lane & (QPS - 1))],
@@ -558,7 +586,11 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // candidate lists are stored [split][state unit][entry][lane] (unit = the 64 lanes' lists of
     // one query block / query tile) so that both the appends of a wave and K5's per-query reads
     // touch consecutive 8-byte words
-    const size_t lblk0 = (size_t)blockIdx.y * (a.m_pad / QPS) + (size_t)qblk0 * (32 / QPS);
+    // (L16: units of 32 queries as on 32x32 tiles; the owner of state st, quarter g, query i — g even — keeps list lane
+    //  32 (g >> 1) + 16 (st & 1) + i of unit st >> 1)
+    constexpr int LQPS = L16 ? 32 : QPS;
+    const size_t lblk0 = (size_t)blockIdx.y * (a.m_pad / LQPS) + (size_t)qblk0 * (32 / LQPS);
+    const bool owner = !L16 || (g16 & 1) == 0;
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
         thr[st] = thrw[st] = __builtin_inff();
@@ -578,7 +610,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         const unsigned lb_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)lb);
         lbase = (char *)(((uintptr_t)lb_hi << 32) | (uintptr_t)lb_lo);
     }
-    const unsigned loff = lane * (unsigned)sizeof(CandEntry);
+    const unsigned loff = (L16 ? 32 * (g16 >> 1) + i16 : lane) * (unsigned)sizeof(CandEntry);
+    // byte offset of state st's list behind lbase + loff
+    auto list_off = [](int st) __attribute__((always_inline)) -> unsigned {
+        if constexpr (L16) return (unsigned)((st >> 1) * (kCandCap * 64) + (st & 1) * 16) * (unsigned)sizeof(CandEntry);
+        else return (unsigned)(st * (kCandCap * 64 * (int)sizeof(CandEntry)));
+    };
     f32x4 nseed0 = {0.0f, 0.0f, 0.0f, 0.0f}, nseed1 = nseed0;   // 16x16 tiles: the two ref tiles' norms
     // accumulators start at |y'_j|^2 of their rows: rows (r&3) + 8(r>>2) + 4h
     auto seed = [&](typename OP::Acc &acc, const char *slot, int blk) __attribute__((always_inline)) {
@@ -685,7 +722,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     auto record = [&](auto st_c, float x, int j, bool roomy) __attribute__((always_inline)) {
         constexpr int st = decltype(st_c)::value;
         if (x <= thr[st]) {
-            const unsigned off = loff + (unsigned)(st * (kCandCap * 64 * (int)sizeof(CandEntry))) +
+            const unsigned off = loff + list_off(st) +
                                  (unsigned)(cnt[st] & (kCandCap - 1)) * (unsigned)(64 * sizeof(CandEntry));
             CandEntry *const dst = reinterpret_cast<CandEntry *>(lbase + off);
             if (__builtin_expect(!roomy, 0)) {
@@ -724,6 +761,11 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         }
     };
     auto frag_ptr = [&](const char *slot, int blk, int f) __attribute__((always_inline)) {
+        if constexpr (L16) {
+            // step F of the slot = block F / SPB, ref tile rt, k-step ks: the gathered operand (lazy16_gather)
+            const int F = blk * SPB + f, rt = (F % SPB) / (SPB / 2), ks = F % (SPB / 2);
+            return reinterpret_cast<const float4 *>(slot + (F / SPB) * BLK_BYTES) + (lazy16_gather(0, rt, ks) + lazy16_gather(lane, 0, 0));
+        } else
         return (reinterpret_cast<const float4 *>(slot + (DEEP ? 0 : blk * BLK_BYTES)) + lane) + f * 64;
     };
     // slow path of one state: every score of the block against the lane's threshold
@@ -929,12 +971,84 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     }
     // threshold test of the retiring ref tile ot of block oblk: ONE wave-uniform branch for the
     // common case (no lane has a record in any of its four states), then per state inside
-    auto t16_test = [&](typename OP::Acc &acc, int oblk, auto ot_c) __attribute__((always_inline)) {
+    // (oslot, oin: where the retiring tile's block still sits in the ring — the lazy form's refinement re-reads its hi
+    //  fragments)
+    auto t16_test = [&](typename OP::Acc &acc, int oblk, auto ot_c, const char *oslot, int oin) __attribute__((always_inline)) {
         if constexpr (T16) {
             constexpr int ot = decltype(ot_c)::value;
             unsigned long long any = 0ull;
 #pragma unroll
             for (int i = 0; i < NT16; ++i) any |= hm[i];
+#ifdef NNS_DIAG
+            diag_tiles += NT16;
+#endif
+            if constexpr (L16) {
+                // LAZY: a flagged (ref tile, state) — some lane's hi-hi minimum within fl(thr + B) — gets its cross products
+                // now, on the same accumulator: rh x ql and rl x qh per k-step, rh out of the ring, rl and ql plain global
+                // loads through the gather (rl: the lo region of the image; ql: the query image, 16 KiB per wave, L2).
+                // The retiring tile may be the last one of the PREVIOUS slot: the partners run in lock-step, so during
+                // interval s every wave is in interval s, and the only DMA issued fills slot s + AHEAD, which is slot
+                // s - 1's ring position only if AHEAD + 1 is a multiple of the ring depth.
+                static_assert(!OP::kLag && (AHEAD + 1) % F_D<OP> != 0, "slot s - 1 is not refilled during interval s");
+                // (the very first retirement of a stream is of the +INF start accumulators: nothing there, and no slot)
+                // (one condition, not a short-circuit pair: hipcc lays a pair out with the cold side falling through)
+                const bool refine = (any != 0ull) & (oblk >= slot0 * BPS);
+                if (__builtin_expect(refine, 0)) {   // cold: laid out off the MFMA stream
+                    constexpr int NKS = SPB / 2;
+                    const float4 *lo = reinterpret_cast<const float4 *>(a.rimg_lo) + (size_t)oblk * (SPB * 64);
+                    const int jbase = oblk * 32 + 16 * ot + 4 * g16;
+                    static_for<NT16>([&](auto st_c) __attribute__((always_inline)) {
+                        constexpr int st = decltype(st_c)::value;
+                        if (hm[st] != 0ull) {
+#ifdef NNS_DIAG
+                            ++diag_slow;
+                            const unsigned long long diag_f0 = __builtin_amdgcn_s_memtime();
+#endif
+                            const float4 *qs = a.qimg + (size_t)(qblk0 + (st >> 1)) * (QFB * 64);
+                            // (every load is issued AND consumed inside the state's branch — a second flagged state of the
+                            //  tile reads rl and rh again: a load left in flight where the branch rejoins the slot loop makes
+                            //  hipcc wait with vmcnt(0) in the loop, in front of the first fragment read that reuses a register)
+                            float4 rl[NKS], rh[NKS], ql[NKS];
+#pragma unroll
+                            for (int ks = 0; ks < NKS; ++ks) rl[ks] = lo[lazy16_gather(lane, ot, ks)];
+#pragma unroll
+                            for (int ks = 0; ks < NKS; ++ks) ql[ks] = qs[lazy16_gather(lane, st & 1, ks, 2, 1)];
+#pragma unroll
+                            for (int ks = 0; ks < NKS; ++ks) rh[ks] = *frag_ptr(oslot, oin, ot * NKS + ks);
+                            // (all of them in flight before the first is used: ONE round trip, see filter_lazy_kernel)
+#pragma unroll
+                            for (int ks = 0; ks < NKS; ++ks) {
+                                asm volatile("" : "+v"(rl[ks].x), "+v"(rl[ks].y), "+v"(rl[ks].z), "+v"(rl[ks].w));
+                                asm volatile("" : "+v"(ql[ks].x), "+v"(ql[ks].y), "+v"(ql[ks].z), "+v"(ql[ks].w));
+                            }
+                            f32x4 &o = acc.template at<ot, st>();
+#pragma unroll
+                            for (int ks = 0; ks < NKS; ++ks) {
+                                OP::mma16(rh[ks], ql[ks], o);
+                                OP::mma16(rl[ks], bq[st][ks], o);
+                            }
+                            // asm MFMAs: the compiler adds no wait states in front of the VALU reads below
+                            asm volatile("s_nop 7" : "+v"(o));
+                            tighten(st_c, fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]));
+                            // Two lists per query: the lanes with even g own them, and lane g ^ 1 hands over its four scores
+                            // (rows 4 (g ^ 1) ..) through a row swap: on an even row, word 1 of swap(x, x) is x of lane + 16.
+                            // The owner tests all eight against its own threshold (tighten: any of the query's lanes' is
+                            // valid, and they have just adopted the smallest); the other lanes append nothing.
+                            const bool roomy = __builtin_amdgcn_ballot_w64((cnt[st] & kCandCountMask) + 8 > kCandCap) == 0ull;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const unsigned ob = __float_as_uint(o[r]);
+                                const auto sw = __builtin_amdgcn_permlane16_swap(ob, ob, false, false);
+                                record(st_c, owner ? o[r] : __builtin_inff(), jbase + r, roomy);
+                                record(st_c, owner ? __uint_as_float(sw[1]) : __builtin_inff(), jbase + 4 + r, roomy);
+                            }
+#ifdef NNS_DIAG
+                            diag_cyc += __builtin_amdgcn_s_memtime() - diag_f0;
+#endif
+                        }
+                    });
+                }
+            } else
             if (__builtin_expect(any != 0ull, 0)) {   // cold: laid out off the MFMA stream
                 const int jbase = oblk * 32 + 16 * ot + 4 * (lane >> 4);
                 static_for<NT16>([&](auto st_c) __attribute__((always_inline)) {
@@ -958,13 +1072,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // SGPR pairs, computed a step before the branch that reads them)
     auto t16_masks = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int st = 0; st < NT16; ++st) hm[st] = __builtin_amdgcn_ballot_w64(tmh[st] <= thr[st]);
+        for (int st = 0; st < NT16; ++st) hm[st] = __builtin_amdgcn_ballot_w64(tmh[st] <= (LAZY ? thrw[st] : thr[st]));
     };
     // step b = 8 rt + ks of the block blk_global: the 4 MFMAs of ref tile rt's k-step ks; at
     // ks = 1 the other tile's four accumulators (finished at its k-step 7, >= 5 MFMAs ago) are
     // reduced, two v_min behind each MFMA; at ks = 2 they are tested.  The other tile of rt = 0
     // is tile 1 of the PREVIOUS block (kernel start: +INF accumulators, nothing to record).
-    auto t16_step = [&](typename OP::Acc &acc, const float4 &frag, int blk_global, auto b_c) __attribute__((always_inline)) {
+    auto t16_step = [&](typename OP::Acc &acc, const float4 &frag, int blk_global, auto b_c, const char *oslot, int oin) __attribute__((always_inline)) {
         if constexpr (T16) {
             constexpr int b = decltype(b_c)::value;
             constexpr int NKS = SPB / 2;              // k-steps of 32 dims per 16-ref tile
@@ -991,7 +1105,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                 }
             });
             if constexpr (ks == RET && (kAblate & 2) == 0) t16_masks();
-            if constexpr (ks == RET + 1 && (kAblate & 2) == 0) t16_test(acc, rt == 0 ? blk_global - 1 : blk_global, std::integral_constant<int, ot>{});
+            if constexpr (ks == RET + 1 && (kAblate & 2) == 0) t16_test(acc, rt == 0 ? blk_global - 1 : blk_global, std::integral_constant<int, ot>{}, oslot, oin);
         }
     };
 
@@ -1086,7 +1200,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             // (LAG 1, very first interval: its first LAGOFF steps chew on a not-yet-written ring
             //  slot; that accumulator is discarded below and re-seeded at the next tile)
             if constexpr (T16) {
-                t16_step(acc, fr[t % RING], blk0_global + blk, std::integral_constant<int, b>{});
+                // (the tile retired during ref tile 0's steps is tile 1 of the block before: the previous slot's last at blk 0)
+                constexpr bool oprev = b < SPB / 2 && blk == 0;
+                t16_step(acc, fr[t % RING], blk0_global + blk, std::integral_constant<int, b>{}, oprev ? prev : cur,
+                         oprev ? BPS - 1 : (b < SPB / 2 ? blk - 1 : blk));
             } else {
                 mma_all(acc, fr[t % RING], std::integral_constant<int, b>{});
                 if constexpr (b == SPB - 1) {                // the tile's epilogue right at its end
@@ -1211,7 +1328,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                 tmh[decltype(qc)::value] = fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]);
             });
             t16_masks();
-            t16_test(acc, (slot0 + ns) * BPS - 1, std::integral_constant<int, 1>{});
+            t16_test(acc, (slot0 + ns) * BPS - 1, std::integral_constant<int, 1>{}, ring(ns - 1), BPS - 1);
         }
     }
     if constexpr (OP::kLag) if (lag) {   // the lagging half block of the last slot; its first PF fragments are in the ring
@@ -1244,7 +1361,13 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         }
     }
 #pragma unroll
-    for (int st = 0; st < NS; ++st) a.counts[(lblk0 + st) * 64 + lane] = cnt[st];
+    for (int st = 0; st < NS; ++st) {
+        if constexpr (L16) {
+            if (owner) a.counts[(lblk0 + (st >> 1)) * 64 + 32 * (g16 >> 1) + 16 * (st & 1) + i16] = cnt[st];
+        } else {
+            a.counts[(lblk0 + st) * 64 + lane] = cnt[st];
+        }
+    }
 #ifdef NNS_DIAG
     if (a.stamps && lane == 0) {   // totals behind the per-workgroup stamps
         unsigned long long *tot = a.stamps + 4 * (size_t)gridDim.x * gridDim.y;
@@ -1280,6 +1403,16 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_lazy_kernel(const FilterA
 {
     filter_main<OP>(a);
 }
+
+// the lazy schedule on 16x16x32 tiles (OpLazySplit16)
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_lazy16_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
+// (the 32x32x16 lazy kernel stays in every build, launched or not: the ISA checks of the two read one compilation)
+template __global__ void filter_lazy_kernel<OpLazySplit>(const FilterArgs a);
+template __global__ void filter_lazy16_kernel<OpLazySplit16>(const FilterArgs a);
 
 // ---- self-test: one 32x32 tile through the same MFMA k-order as the filter --------
 // out[i][j] = accumulate over the image's k order of a[i][.] * b[j][.] seeded with c0[i];
@@ -1379,6 +1512,61 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
     for (int r = 0; r < 16; ++r) out[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[r];
 }
 
+// ---- self-test of OpLazySplit16's operands and chain: one wave, 32 refs x 64 queries at KT = 128 -------------------
+// q [64][128], r [32][128] fp32, c0 [32]: the wave first writes the split images in the order K2 writes them (32x32x16
+// operand order; refs: hi and lo regions as form 3, queries: qh | ql interleaved per 16-dim step as form 2), then takes
+// its 16x16x32 operands out of them through lazy16_gather and runs the kernel's chain: the four hi-hi MFMAs seeded with
+// c0 (-> out_hh), then rh x ql and rl x qh per k-step on the same accumulator (-> out).  Both [ref][query].
+__global__ __launch_bounds__(64) void mfma_lazy16_selftest_kernel(const float *__restrict__ q, const float *__restrict__ r,
+                                                                  const float *__restrict__ c0, float *__restrict__ out,
+                                                                  float *__restrict__ out_hh)
+{
+    constexpr int KT = 128;
+    __shared__ bf16x8 rimg[2][8 * 64];        // [hi | lo][fragment s][lane]
+    __shared__ bf16x8 qimg[2][16 * 64];       // [query block][2 s + part][lane]
+    const int lane = threadIdx.x, hl = lane >> 5, p = lane & 31;
+    auto split8 = [](const float *v, bf16x8 &h, bf16x8 &l) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            h[e] = (__bf16)v[e];
+            l[e] = (__bf16)__fsub_rn(v[e], (float)h[e]);
+        }
+    };
+    for (int s = 0; s < KT / 16; ++s) {       // lane 32 hl + p of fragment s: dims 16 s + 8 hl .. + 7 of point p
+        split8(r + p * KT + 16 * s + 8 * hl, rimg[0][s * 64 + lane], rimg[1][s * 64 + lane]);
+        for (int qb = 0; qb < 2; ++qb)
+            split8(q + (32 * qb + p) * KT + 16 * s + 8 * hl, qimg[qb][(2 * s) * 64 + lane], qimg[qb][(2 * s + 1) * 64 + lane]);
+    }
+    __syncthreads();
+    const int g = lane >> 4, i = lane & 15;
+    for (int rt = 0; rt < 2; ++rt)
+        for (int st = 0; st < 4; ++st) {
+            f32x4 t;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = c0[16 * rt + 4 * g + e];
+            for (int ks = 0; ks < KT / 32; ++ks)
+                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rimg[0][lazy16_gather(lane, rt, ks)],
+                                                            qimg[st >> 1][lazy16_gather(lane, st & 1, ks, 2, 0)], t, 0, 0, 0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out_hh[(16 * rt + 4 * g + e) * 64 + 16 * st + i] = t[e];
+            for (int ks = 0; ks < KT / 32; ++ks) {
+                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rimg[0][lazy16_gather(lane, rt, ks)],
+                                                            qimg[st >> 1][lazy16_gather(lane, st & 1, ks, 2, 1)], t, 0, 0, 0);
+                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rimg[1][lazy16_gather(lane, rt, ks)],
+                                                            qimg[st >> 1][lazy16_gather(lane, st & 1, ks, 2, 0)], t, 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[(16 * rt + 4 * g + e) * 64 + 16 * st + i] = t[e];
+        }
+}
+
+int launch_mfma_lazy16_selftest(const float *q, const float *r, const float *c0, float *out, float *out_hh, hipStream_t st)
+{
+    hipLaunchKernelGGL(mfma_lazy16_selftest_kernel, dim3(1), dim3(64), 0, st, q, r, c0, out, out_hh);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
 // self-test of share_min: out[l] = the value lane l would adopt from in[0..63]
 __global__ __launch_bounds__(64) void lane_share_selftest_kernel(int t16, const float *__restrict__ in, float *__restrict__ out)
 {
@@ -1424,6 +1612,19 @@ constexpr bool lazy_depth(int kt)
     return kt == 128;
 }
 
+// The MFMA shape of the lazy kernel at KT = 128: 1 = OpLazySplit16 (16x16x32), 0 = OpLazySplit (32x32x16).  Both run the same plan
+// on the same image and fill the same lists (A/B builds: tools/build_variant.sh <name> -DNNS_F_LAZY_T16=0).
+#ifndef NNS_F_LAZY_T16
+#define NNS_F_LAZY_T16 1
+#endif
+using LazyOp128 = std::conditional_t<NNS_F_LAZY_T16 != 0, OpLazySplit16, OpLazySplit>;
+static_assert(OpLazySplit16::kQB * OpLazySplit16::kNW * 32 == 512 && OpLazySplit::kQB * OpLazySplit::kNW * 32 == 512,
+              "both lazy operators: 512 queries per workgroup (filter_plan sizes the query groups from the eager twin)");
+int filter_lazy_tile()
+{
+    return LazyOp128::kTile16 ? 16 : 32;
+}
+
 // The one depth-to-operator table: f(OP{}) for the operator that runs geometry g — (bf16, split, lazy, kt).  The kt
 // ladder of filter_plan produces exactly the depths listed here.
 template <class F>
@@ -1440,7 +1641,7 @@ static int with_filter_op(const FilterGeom &g, F &&f)
         case 1024: return f(OpBF16K1024{});
         }
     } else if (g.lazy) {
-        if (g.kt == 128) return f(OpLazySplit{});
+        if (g.kt == 128) return f(LazyOp128{});
     } else if (g.split) {
         switch (g.kt) {
         case 16: return f(OpSplitK16{});
@@ -1500,7 +1701,7 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
         // (K7m's flag kernel, range_mfma.hip, takes its workgroup and ring slot from these two constants)
         if constexpr (OP::kSplit && !OP::kLazy)
             static_assert(OP::kNW == kSplitWaves && OP::kSlotSteps == kSplitSlotSteps, "the eager split operators' workgroup and slot");
-        g->lpq = OP::kTile16 ? 4 : 2;
+        g->lpq = OP::kLPQ;
         g->spb = OP::kSPB;
         g->qb = OP::kQB;
         g->waves = OP::kNW;
@@ -1554,7 +1755,8 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
+        if constexpr (OP::kLazy && OP::kTile16) return filter_lazy16_kernel<OP>;
+        else if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
         else if constexpr (OP::kSplit) return filter_split_kernel<OP>;
         else return filter_kernel<OP>;
     }();

@@ -1240,6 +1240,34 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset, v
 
 static int selftest_mfma_impl(int kt, int bf16, const float *a, const float *b, const float *c0, float *out, float *out_hh);
 
+int nns_selftest_mfma_lazy16(const float *q, const float *r, const float *c0, float *out, float *out_hh)
+{
+    if (!q || !r || !c0 || !out || !out_hh) return NNS_ERR_INVALID;
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(0));
+    constexpr size_t nq = 64 * 128, nr = 32 * 128, no = 32 * 64;
+    float *d = nullptr;
+    NNS_HIP(pool_alloc(&d, (nq + nr + 32 + 2 * no) * sizeof(float)));
+    int rc = NNS_OK;
+    if (hipMemcpy(d, q, nq * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nq, r, nr * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nq + nr, c0, 32 * 4, hipMemcpyHostToDevice) != hipSuccess)
+        rc = NNS_ERR_HIP;
+    float *o = d + nq + nr + 32;
+    if (rc == NNS_OK) rc = launch_mfma_lazy16_selftest(d, d + nq, d + nq + nr, o, o + no, nullptr);
+    if (rc == NNS_OK && (hipMemcpy(out, o, no * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_hh, o + no, no * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = NNS_ERR_HIP;
+    if (rc == NNS_ERR_HIP) set_error("nns_selftest_mfma_lazy16: %s", hipGetErrorString(hipGetLastError()));
+    pool_free(d);
+    return rc;
+}
+
+int nns_filter_lazy_tile(void)
+{
+    return filter_lazy_tile();
+}
+
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0, float *out)
 {
     return selftest_mfma_impl(kt, bf16, a, b, c0, out, nullptr);

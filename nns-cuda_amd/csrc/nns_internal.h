@@ -388,6 +388,19 @@ constexpr int kSplitSlotSteps = 32;   // 1 KiB fragment steps per ring slot
 // a chunk of K7m's evaluation and of K6m's selection is whole steps of this many flag words
 constexpr int kRmChunkWords = 64;
 
+// A v_mfma_f32_16x16x32_bf16 operand out of a 32-point block in the 32x32x16 operand order (K2 forms 2 and 3: 16-dim
+// fragment s holds, at lane 32 hl + p, dims 16 s + 8 hl .. + 7 of point p).  Lane l = 16 g + i of the operand of point
+// tile t (points 16 t + i), k-step ks wants dims 32 ks + 8 g .. + 7: the 16 bytes at fragment 2 ks + (g >> 1), lane
+// 32 (g & 1) + 16 t + i.  Returned as a 16-byte index into the block's fragments; `parts` = 1: fragments of one part
+// back to back (form 3's hi or lo region), 2: hi and lo interleaved per 16-dim step (form 2, the query image), `part`
+// then picks hi (0) or lo (1).  (tools/lazy16_gather_check.cpp checks it against the order-1 definition of
+// prep_kernels.hip and counts the banks of every ds_read_b128 lane group.)
+__host__ __device__ constexpr int lazy16_gather(int lane, int t, int ks, int parts = 1, int part = 0)
+{
+    const int g = lane >> 4, i = lane & 15;
+    return ((2 * ks + (g >> 1)) * parts + part) * 64 + 32 * (g & 1) + 16 * t + i;
+}
+
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
@@ -663,6 +676,8 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = fals
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
                   hipStream_t st);
+int launch_mfma_lazy16_selftest(const float *q, const float *r, const float *c0, float *out, float *out_hh, hipStream_t st);
+int filter_lazy_tile();   // MFMA tile (16 or 32) of the lazy split kernel this build launches (NNS_F_LAZY_T16)
 int launch_mfma_selftest(int kt, int bf16, const float *a, const float *b, const float *c0, float *out,
                          hipStream_t st);
 int launch_lane_share_selftest(int t16, const float *in, float *out, hipStream_t st);

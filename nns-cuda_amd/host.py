@@ -56,7 +56,11 @@ ABI_SYMBOLS = (
     "nns_index_range_count", "nns_index_range_fill", "nns_search_f32_range", "nns_search_bf16_range", "nns_plan_range",
     "nns_index_range_info", "nns_plan_range_mfma", "nns_range_threshold",
     "nns_index_topk_info", "nns_plan_topk_mfma",
+    "nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
 )
+# the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
+# then fail when called); build() requires every symbol of the tree's own library
+OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -153,8 +157,14 @@ def _load() -> ctypes.CDLL:
     lib.nns_last_error.argtypes = []
     lib.nns_last_error.restype = ctypes.c_char_p
     lib.nns_version.argtypes = []
+    optional = {"nns_filter_lazy_tile": [], "nns_selftest_mfma_lazy16": [c_vp, c_vp, c_vp, c_vp, c_vp]}
+    assert set(optional) == set(OPTIONAL_SYMBOLS)
+    absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
+    for name, argtypes in optional.items():
+        if name not in absent:
+            getattr(lib, name).argtypes = argtypes
     for name in ABI_SYMBOLS:
-        if name not in ("nns_strerror", "nns_last_error", "nns_trim"):
+        if name not in ("nns_strerror", "nns_last_error", "nns_trim") + absent:
             getattr(lib, name).restype = c_int
     lib.nns_warmup.argtypes = [c_int]
     lib.nns_trim.argtypes = []
@@ -197,6 +207,25 @@ def selftest_mfma_lazy(a: np.ndarray, b: np.ndarray, c0: np.ndarray):
     _check(lib.nns_selftest_mfma_lazy(a.shape[1], a.ctypes.data, b.ctypes.data, c0.ctypes.data, out.ctypes.data,
                                       out_hh.ctypes.data), "nns_selftest_mfma_lazy")
     return out, out_hh
+
+
+def selftest_mfma_lazy16(q: np.ndarray, r: np.ndarray, c0: np.ndarray):
+    """(out, out_hh) of nns_selftest_mfma_lazy16, [32 refs][64 queries] each: the lazy split chain on 16x16x32 MFMAs
+    (operands gathered from images in the 32x32x16 order) and its hi.hi partial.  q [64][128], r [32][128], c0 [32]."""
+    q = np.ascontiguousarray(q, np.float32)
+    r = np.ascontiguousarray(r, np.float32)
+    c0 = np.ascontiguousarray(c0, np.float32)
+    assert q.shape == (64, 128) and r.shape == (32, 128) and c0.shape == (32,)
+    out = np.empty((32, 64), np.float32)
+    out_hh = np.empty((32, 64), np.float32)
+    _check(lib.nns_selftest_mfma_lazy16(q.ctypes.data, r.ctypes.data, c0.ctypes.data, out.ctypes.data, out_hh.ctypes.data),
+           "nns_selftest_mfma_lazy16")
+    return out, out_hh
+
+
+def filter_lazy_tile() -> int:
+    """nns_filter_lazy_tile: 16 or 32, the MFMA tile of the lazy split kernel this build launches."""
+    return int(lib.nns_filter_lazy_tile())
 
 
 def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:

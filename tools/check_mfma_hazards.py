@@ -147,22 +147,32 @@ def check_kernel(name: str, lines) -> list:
     return sorted(problems)
 
 
+FILTER_KERNELS = r"filter_(?:split_|lazy_|lazy16_)?kernel"
+
+
+def split_kernels(text, which=FILTER_KERNELS, end="s_endpgm") -> dict:
+    """{mangled name: [(line number, text)]} of the kernels of an ISA listing (a list of lines) whose name matches the
+    regex `which`; a kernel's lines run from its label to the first line that contains `end` (".Lfunc_end": the whole
+    function, with what is laid out behind its s_endpgm)."""
+    kernels, cur = {}, None
+    for i, l in enumerate(text, 1):
+        m = re.match(r"^(_Z\w*" + which + r"\w*):", l)
+        if m:
+            cur = kernels.setdefault(m.group(1), [])
+            continue
+        if cur is not None:
+            if end in l:
+                cur = None
+                continue
+            cur.append((i, l))
+    return kernels
+
+
 def main() -> int:
     path = sys.argv[1] if len(sys.argv) > 1 else compile_isa()
     with open(path) as f:
         text = f.read().splitlines()
-    kernels, cur, name = {}, None, None
-    for i, l in enumerate(text, 1):
-        m = re.match(r"^(_Z\w*filter_(?:split_|lazy_)?kernel\w*):", l)
-        if m:
-            name, cur = m.group(1), []
-            kernels[name] = cur
-            continue
-        if cur is not None:
-            if "s_endpgm" in l:
-                cur = None
-                continue
-            cur.append((i, l))
+    kernels = split_kernels(text)
     if not kernels:
         print("no filter kernels found in", path)
         return 2

@@ -10,7 +10,9 @@ usage: probe_split.py ab [k ...]      per-depth A/B at 65536 x 1048576 (default 
                                       the same protocol between two BUILDS of the library (e.g. the parent commit's and
                                       this tree's, or tools/build_variant.sh arms) at 65536 x 1048576 x k (default 128):
                                       the builds alternate, 3 runs of 5 timed searches each, every run in a child process
-                                      of its own (NNS_LIB_PATH), keys compared through their SHA-256
+                                      of its own (NNS_LIB_PATH), keys compared through their SHA-256.  The lazy kernel on
+                                      32x32x16 against 16x16x32 MFMAs: A = a `tools/build_variant.sh lazy32 -DNNS_F_LAZY_T16=0`
+                                      build (or the commit before OpLazySplit16), B = the default build
        probe_split.py c3 split|f32 N  N C3 searches (65536 x 1048576 x 128) of one form (rocprofv3 / PMC runs)
        probe_split.py cluster         tight Gaussian clusters at 65536 x 1048576 x 128: exact-scan (ambiguous) and
                                       multi-candidate queries of each operand form
