@@ -121,14 +121,16 @@ enum {
                           * nns_index_range_count / _fill flag, per query, the 32-ref blocks whose split-bf16 score lies
                           * within a per-query threshold, then evaluate V0's distance only there.  Same lims, indices and
                           * distance bits as without the flag.  fp32 points whose filter form is the split one, 8 <= k <=
-                          * 256; with bf16 points, NNS_FILTER_F32, NNS_FILTER_BF16 or another k: NNS_ERR_UNSUPPORTED.  Also
-                          * accepted by nns_search_f32_range */
+                          * 256, or bf16 points, 32 <= k <= 256 (exact operands on v_mfma_f32_16x16x32_bf16 over the
+                          * order-1 image: one product per score); with NNS_FILTER_F32, NNS_FILTER_BF16 or another k:
+                          * NNS_ERR_UNSUPPORTED.  Also accepted by nns_search_f32_range / nns_search_bf16_range */
     NNS_TOPK_MFMA = 8192,  /* top-K through the MFMA flag pass (K6m): nns_index_create builds the split-bf16 ref image and norms
                           * whatever the path bits say (the 1-NN path stays what they say), and nns_index_search_topk bounds
                           * each query's kn-th distance from a sample of the refs, flags the 32-ref blocks that can hold a ref
                           * within the bound, and selects among those with V0's arithmetic.  Same keys as without the flag.
-                          * fp32 points whose filter form is the split one, 8 <= k <= 256; with bf16 points, NNS_FILTER_F32,
-                          * NNS_FILTER_BF16 or another k: NNS_ERR_UNSUPPORTED.  Also accepted by nns_search_f32_topk */
+                          * fp32 points whose filter form is the split one, 8 <= k <= 256, or bf16 points, 32 <= k <= 256
+                          * (the ref image is then the bf16 filter's); with NNS_FILTER_F32, NNS_FILTER_BF16 or another k:
+                          * NNS_ERR_UNSUPPORTED.  Also accepted by nns_search_f32_topk / nns_search_bf16_topk */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -296,7 +298,8 @@ int nns_keys_topk_merge(nns_key *inout_dev, const nns_key *other_dev, int m, int
 int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, float *dist_dev, void *stream);
 /* Whole calls: host buffers, idx_out[m][kn], dist_out[m][kn] optional.  num_shards > 1: the V8/V9 contiguous split
  * searched one after another on the one device and merged with nns_keys_topk_merge (as nns_search_f32_ex).  flags:
- * NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and for fp32 points NNS_TOPK_MFMA (below); any other:
+ * NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and NNS_TOPK_MFMA (below: fp32 points at 8 <= k <= 256, bf16
+ * points at 32 <= k <= 256); any other:
  * NNS_ERR_UNSUPPORTED.  Library stream, no
  * device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is allocated. */
 int nns_search_f32_topk(int k, int m, int n, const float *s_points, const float *r_points, int kn, int *idx_out,
@@ -321,7 +324,9 @@ int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int ou
  * bound is not finite or whose values void the filter's error model gets its flag row filled: its selection is the
  * exact scan.  nns_index_stats reports NNS_PATH_MFMA after a filtered search; with NNS_PROFILE rerank_ms holds the
  * bound scan (K6 on the sample), prep_queries_ms K2 on the queries, filter_ms the flag pass, finalize_ms the selection
- * and merge (several batches: filter_ms covers all but the last batch's selection). */
+ * and merge (several batches: filter_ms covers all but the last batch's selection).
+ * bf16 points (32 <= k <= 256): the same three steps; the bound scan and the selection widen the bf16 values as K6
+ * does, the flag pass is K7m's for bf16 points (below). */
 
 /* Diagnostic: what the last nns_index_search_topk on this index did.  out[0..3] = {path taken (NNS_PATH_EXACT: K6,
  * NNS_PATH_MFMA: K6m), flagged (query, 32-ref block) pairs, pairs examined (m x blocks per query), queries whose flag
@@ -337,6 +342,10 @@ int nns_index_topk_info(nns_index *ix, int64_t *out, int out_len);
  * stride = floor(ceil(n / 32) / sb), the blocks b with b % stride == 0 taken.  out_len >= 17.  NNS_ERR_UNSUPPORTED for k outside
  * 8 .. 256, kn above NNS_TOPK_MAX, NNS_FILTER_F32, NNS_FILTER_BF16. */
 int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len);
+/* The same plan for bf16 points: the same seventeen fields, the range fields those of nns_plan_range_mfma_bf16.
+ * NNS_ERR_UNSUPPORTED for k outside 32 .. 256 or kn above NNS_TOPK_MAX; NNS_ERR_INVALID for the flags of fp32 points
+ * (NNS_FILTER_F32, NNS_FILTER_BF16, NNS_FILTER_SPLIT_EAGER). */
+int nns_plan_topk_mfma_bf16(int k, int m, int n, int kn, unsigned flags, int *out, int out_len);
 
 /* ---- fixed-radius neighbours (range search) -----------------------------------
  * Semantics: a hit of query i is every reference j (global index, index_base added) whose V0 distance d (the value
@@ -368,8 +377,8 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 /* Whole calls: count, read lims[m], allocate, fill.  lims_out: the caller's host int64[m + 1].  *idx_out (and
  * *dist_out when dist_out != NULL) are malloc()'d by the library with lims[m] entries, never NULL on success; the
  * caller free()s them.  On error both are set to NULL and nothing leaks; output beyond device or host memory gives
- * NNS_ERR_NOMEM.  flags: NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and for fp32 points NNS_RANGE_MFMA
- * (below); any other: NNS_ERR_UNSUPPORTED.
+ * NNS_ERR_NOMEM.  flags: NNS_PATH_AUTO, NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE, and NNS_RANGE_MFMA (below: fp32
+ * points at 8 <= k <= 256, bf16 points at 32 <= k <= 256); any other: NNS_ERR_UNSUPPORTED.
  * Library stream, no device-wide synchronisation, caller's device restored, NNS_MAX_POINTS checked before anything is
  * allocated. */
 int nns_search_f32_range(int k, int m, int n, const float *s_points, const float *r_points, float radius2,
@@ -395,7 +404,11 @@ int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
  * nns_search_f32_range accepts the flag too (with NNS_PATH_AUTO / NNS_PATH_EXACT, NNS_REFS_SOA, NNS_PROFILE).
  * nns_index_stats reports NNS_PATH_MFMA after a filtered pass; with NNS_PROFILE prep_queries_ms is K2 on the queries,
  * filter_ms the flag pass, finalize_ms the evaluation (with several batches: filter_ms covers all but the last
- * batch's evaluation). */
+ * batch's evaluation).
+ * bf16 points (32 <= k <= 256, the depths of the 16x16x32 tiles; nns_search_bf16_range takes the flag too): the flag
+ * pass runs v_mfma_f32_16x16x32_bf16 on K2's order-1 image, the one the 1-NN bf16 filter reads.  The operands are the
+ * points themselves, so a score is ONE product per k-step — no hi / lo parts, no centring — and the threshold is
+ * nns_range_threshold_bf16's.  Ring, bitmap, batches, evaluation, fallbacks, info and stats are the same. */
 
 /* Diagnostic: what the last nns_index_range_count on this index did.  out[0..3] = {path taken (NNS_PATH_EXACT: K7,
  * NNS_PATH_MFMA: K7m), flagged (query, 32-ref block) pairs, pairs examined (m x blocks per query), total hits
@@ -414,6 +427,15 @@ int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_l
  * fl(a + 1.002 tau(a)) (tau: nns_tau_consts mode 3) plus 2^-22 (radius2 + qnorm2).  Every ref with a V0 distance
  * <= radius2 has a score <= *thr_out.  Monotone in radius2. */
 int nns_range_threshold(int kt, float qnorm2, float ymax2, float radius2, float *thr_out);
+/* K7m's geometry for bf16 points: the same ten fields; kt is 128 or 256, and the layout field reads 2: the order-1
+ * 16x16x32 image.  NNS_ERR_UNSUPPORTED for k outside 32 .. 256 (or an n whose flag rows pass the workspace cap);
+ * NNS_ERR_INVALID for the flags of fp32 points (NNS_FILTER_F32, NNS_FILTER_BF16, NNS_FILTER_SPLIT_EAGER), as
+ * nns_plan_filter answers them for bf16 points. */
+int nns_plan_range_mfma_bf16(int k, int m, int n, unsigned flags, int *out, int out_len);
+/* The threshold of a bf16 query (host only): the same form over nns_tau_consts mode 1 (exact operands), with qnorm2 the
+ * query's own squared norm |x|^2 (no centring) and ymax2 the refs' largest |y|^2.  Every ref with a V0 distance
+ * <= radius2 has a 16x16x32 score |y|^2 - 2 x.y <= *thr_out.  Monotone in radius2. */
+int nns_range_threshold_bf16(int kt, float qnorm2, float ymax2, float radius2, float *thr_out);
 
 /* Deterministic synthetic clouds: dev[i] = u24(splitmix64(seed, offset+i)) * 2^-24
  * in [0,1) — bit-identical to oracle/v0_oracle.c:nns_rng_fill on the CPU. */

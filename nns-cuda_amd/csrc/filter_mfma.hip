@@ -1701,6 +1701,10 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
         // (K7m's flag kernel, range_mfma.hip, takes its workgroup and ring slot from these two constants)
         if constexpr (OP::kSplit && !OP::kLazy)
             static_assert(OP::kNW == kSplitWaves && OP::kSlotSteps == kSplitSlotSteps, "the eager split operators' workgroup and slot");
+        // (and its bf16 flag kernel at KT = 128 / 256: the same ring, OpBF16K128 / OpBF16's blocks and query groups)
+        if constexpr (OP::kTile16 && !OP::kSplit && !OP::kLazy && (OP::kSPB == 8 || OP::kSPB == 16))
+            static_assert(OP::kNW == kSplitWaves && OP::kSlotSteps == kSplitSlotSteps && OP::kQB == kFlag16QB,
+                          "the 16x16x32 bf16 operators' workgroup, slot and query blocks per wave");
         g->lpq = OP::kLPQ;
         g->spb = OP::kSPB;
         g->qb = OP::kQB;

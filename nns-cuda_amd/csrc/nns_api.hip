@@ -230,6 +230,14 @@ static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *spl
     return NNS_OK;
 }
 
+// what NNS_RANGE_MFMA / NNS_TOPK_MFMA take: fp32 points whose filter form is the split one, at the split tiles' depths;
+// bf16 points at the depths of the 16x16x32 tiles (below 32 dimensions AUTO does not filter bf16 points either)
+static bool flag_pass_supported(int k, int bf16, unsigned flags)
+{
+    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) return false;
+    return bf16 ? (k >= 32 && k <= 256) : (k >= 8 && k <= 256);
+}
+
 static int prep_refs(nns_index *ix, hipStream_t st)
 {
     const FilterGeom &g = ix->geom;
@@ -330,16 +338,15 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     }
     *out = nullptr;
     if (flags & NNS_RANGE_MFMA) {
-        // (the first version: fp32 points whose filter form is the split one, at the split tiles' depths)
-        if (bf16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) || k < 8 || k > 256) {
-            set_error("nns_index_create: the range-MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256 (k=%d, flags 0x%x)",
+        if (!flag_pass_supported(k, bf16, flags)) {
+            set_error("nns_index_create: the range-MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d, flags 0x%x)",
                       k, flags);
             return NNS_ERR_UNSUPPORTED;
         }
     }
     if (flags & NNS_TOPK_MFMA) {
-        if (bf16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) || k < 8 || k > 256) {
-            set_error("nns_index_create: the top-K MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256 (k=%d, flags 0x%x)",
+        if (!flag_pass_supported(k, bf16, flags)) {
+            set_error("nns_index_create: the top-K MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d, flags 0x%x)",
                       k, flags);
             return NNS_ERR_UNSUPPORTED;
         }
@@ -696,6 +703,8 @@ static int topk_check_kn(const char *where, int kn)
 }
 
 static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipStream_t st);
+static int plan_flag_check_flags(const char *where, unsigned flags, bool bf16);
+static int flag_plan_layout(const RangeMfmaPlan &p);
 static int ensure_flag_stat(nns_index *ix, hipStream_t st);
 static int latch_refs_bad(nns_index *ix, hipStream_t st);
 
@@ -715,8 +724,8 @@ static int topk_mfma_pass(nns_index *ix, const TopkMfmaPlan &tp, int m, const vo
     const bool prof = ix->profile;
     hipEvent_t *ev = ix->evr[ix->ev_slot];
     if (prof) (void)hipEventRecord(ev[EV_BEGIN], st);
-    NNS_TRY(launch_topk_search(tp.sp, ix->k, m, tp.sample_refs, kn, q_dev, ix->r_dev, 0, ix->base, keys_dev, ix->topk_ws, st,
-                               tp.stride));
+    NNS_TRY(launch_topk_search(tp.sp, ix->k, m, tp.sample_refs, kn, q_dev, ix->r_dev, ix->bf16, ix->base, keys_dev,
+                               ix->topk_ws, st, tp.stride));
     NNS_TRY(launch_topk_bound(keys_dev, m, kn, ix->topk_bound, st));
     if (prof) (void)hipEventRecord(ev[EV_BOUND], st);
     ix->ev_bound[ix->ev_slot] = true;
@@ -761,7 +770,7 @@ static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int k
     if (ix->topk_mfma) {
         // K6m when its answer can be trusted and it has something to skip: the plan's conditions, finite refs below 1e17
         TopkMfmaPlan tp{};
-        NNS_TRY(topk_mfma_plan(ix->k, m, ix->n, kn, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &tp));
+        NNS_TRY(topk_mfma_plan(ix->k, m, ix->n, kn, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &tp, ix->bf16 != 0));
         if (tp.filtered) NNS_TRY(latch_refs_bad(ix, st));
         if (tp.filtered && !ix->refs_bad) return topk_mfma_pass(ix, tp, m, q_dev, kn, keys_dev, st);
         ix->topk_path = NNS_PATH_EXACT;
@@ -817,22 +826,30 @@ int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int ou
     return NNS_OK;
 }
 
-int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
+static int plan_topk_mfma_impl(const char *where, int k, int m, int n, int kn, unsigned flags, bool bf16, int *out,
+                               int out_len)
 {
     if (!out || out_len < 17 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
-    NNS_TRY(topk_check_kn("nns_plan_topk_mfma", kn));
+    NNS_TRY(topk_check_kn(where, kn));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
-    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) {
-        set_error("nns_plan_topk_mfma: the top-K MFMA flag runs on split-bf16 operands only (flags 0x%x)", flags);
-        return NNS_ERR_UNSUPPORTED;
-    }
+    NNS_TRY(plan_flag_check_flags(where, flags, bf16));
     TopkMfmaPlan t{};
-    NNS_TRY(topk_mfma_plan(k, m, n, kn, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &t));
+    NNS_TRY(topk_mfma_plan(k, m, n, kn, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &t, bf16));
     const RangeMfmaPlan &p = t.rp;   // (all zero unless filtered)
     const int v[17] = {t.sample_blocks, t.stride, t.sample_refs, t.filtered, p.kt, t.filtered ? 32 : 0, p.blocks, p.batch,
-                       p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, p.lazy_img, p.echunks, p.eper, t.lds};
+                       p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, flag_plan_layout(p), p.echunks, p.eper, t.lds};
     memcpy(out, v, sizeof(v));
     return NNS_OK;
+}
+
+int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
+{
+    return plan_topk_mfma_impl("nns_plan_topk_mfma", k, m, n, kn, flags, false, out, out_len);
+}
+
+int nns_plan_topk_mfma_bf16(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
+{
+    return plan_topk_mfma_impl("nns_plan_topk_mfma_bf16", k, m, n, kn, flags, true, out, out_len);
 }
 
 int nns_index_topk_info(nns_index *ix, int64_t *out, int out_len)
@@ -901,6 +918,9 @@ static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipS
     NNS_TRY(ensure_query_ws(ix, m, st, false));
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
+    if (ix->bf16)   // (the order-1 image and the uncentred norms, as the 1-NN search of a bf16 index prepares them)
+        return launch_prep_image_bf16(kBf16ImageOrder, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg,
+                                      ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st);
     return launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f, (float *)ix->qimg,
                              ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st, 2);
 }
@@ -922,7 +942,7 @@ static int range_mfma_choose(nns_index *ix, int m, float radius2, hipStream_t st
     if (!ix->range_mfma || m < kTinyM || !(radius2 < INFINITY)) return NNS_OK;
     NNS_TRY(latch_refs_bad(ix, st));
     if (ix->refs_bad) return NNS_OK;
-    *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp) == NNS_OK;
+    *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp, ix->bf16 != 0) == NNS_OK;
     return NNS_OK;
 }
 
@@ -1014,7 +1034,7 @@ static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float 
     // (the count's path; either plan depends on k, m, n and the index alone, and the count has made it once already)
     if (ix->range_path == NNS_PATH_MFMA) {
         RangeMfmaPlan mp{};
-        NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp));
+        NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp, ix->bf16 != 0));
         if (!idx_dev && !dist_dev) return NNS_OK;
         return range_mfma_pass(ix, mp, true, m, q_dev, radius2, const_cast<int64_t *>(lims_dev), idx_dev, dist_dev, st);
     }
@@ -1075,25 +1095,57 @@ int nns_index_range_info(nns_index *ix, int64_t *out, int out_len)
     return NNS_OK;
 }
 
-int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_len)
+// the operand flags of a flag-pass plan: fp32 points run on split-bf16 operands only (the other two forms: unsupported);
+// bf16 points take none of the fp32-only flags (invalid, as nns_plan_filter answers them)
+static int plan_flag_check_flags(const char *where, unsigned flags, bool bf16)
+{
+    if (bf16 && (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16 | NNS_FILTER_SPLIT_EAGER))) {
+        set_error("%s: the operand flags apply to fp32 points (flags 0x%x)", where, flags);
+        return NNS_ERR_INVALID;
+    }
+    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) {
+        set_error("%s: the flag pass of fp32 points runs on split-bf16 operands only (flags 0x%x)", where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
+// the plans' `layout`: 0 eager split image, 1 lazy split image, 2 the order-1 16x16x32 image of bf16 points
+static int flag_plan_layout(const RangeMfmaPlan &p) { return p.bf16 ? 2 : p.lazy_img; }
+
+static int plan_range_mfma_impl(const char *where, int k, int m, int n, unsigned flags, bool bf16, int *out, int out_len)
 {
     if (!out || out_len < 10 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
-    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) {
-        set_error("nns_plan_range_mfma: the range-MFMA flag runs on split-bf16 operands only (flags 0x%x)", flags);
-        return NNS_ERR_UNSUPPORTED;
-    }
+    NNS_TRY(plan_flag_check_flags(where, flags, bf16));
     RangeMfmaPlan p{};
-    NNS_TRY(range_mfma_plan(k, m, n, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &p));
-    const int v[10] = {p.kt, 32, p.blocks, p.batch, p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, p.lazy_img};
+    NNS_TRY(range_mfma_plan(k, m, n, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &p, bf16));
+    const int v[10] = {p.kt, 32, p.blocks, p.batch, p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, flag_plan_layout(p)};
     memcpy(out, v, sizeof(v));
     return NNS_OK;
+}
+
+int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_len)
+{
+    return plan_range_mfma_impl("nns_plan_range_mfma", k, m, n, flags, false, out, out_len);
+}
+
+int nns_plan_range_mfma_bf16(int k, int m, int n, unsigned flags, int *out, int out_len)
+{
+    return plan_range_mfma_impl("nns_plan_range_mfma_bf16", k, m, n, flags, true, out, out_len);
 }
 
 int nns_range_threshold(int kt, float qnorm2, float ymax2, float radius2, float *thr_out)
 {
     if (kt <= 0 || !thr_out) return NNS_ERR_INVALID;
     *thr_out = range_threshold(kt, qnorm2, ymax2, radius2);
+    return NNS_OK;
+}
+
+int nns_range_threshold_bf16(int kt, float qnorm2, float ymax2, float radius2, float *thr_out)
+{
+    if (kt <= 0 || !thr_out) return NNS_ERR_INVALID;
+    *thr_out = range_threshold(kt, qnorm2, ymax2, radius2, 1);
     return NNS_OK;
 }
 
@@ -1686,7 +1738,7 @@ static int search_whole(const char *where, int k, int m, int n, const void *s_po
     }));
     flags &= ~(unsigned)NNS_REFS_SOA;   // (the shards index the point-major copy)
     // top-K's shard indexes skip the MFMA filter's ref pre-pass (it reads the point-major refs only)
-    // (NNS_TOPK_MFMA: plus the split-bf16 ref image; that build waits once to learn whether the refs void the error model)
+    // (NNS_TOPK_MFMA: plus the ref image of the flag pass; that build waits once to learn whether the refs void the error model)
     const unsigned create_flags =
         kn ? NNS_PATH_EXACT | (flags & NNS_PROFILE) | ((flags & NNS_TOPK_MFMA) ? (unsigned)NNS_TOPK_MFMA : kCreateNoSync) : flags;
     for (int s = 0; s < num_shards; ++s) {
@@ -1768,8 +1820,8 @@ static int search_topk_host_impl(int k, int m, int n, const void *s_points, cons
         return NNS_ERR_INVALID;
     }
     NNS_TRY(check_exact_only_flags(where, "top-K", flags & ~(unsigned)NNS_TOPK_MFMA));
-    if ((flags & NNS_TOPK_MFMA) && (bf16 || k < 8 || k > 256)) {
-        set_error("%s: the top-K MFMA flag takes fp32 points, 8 <= k <= 256 (k=%d)", where, k);
+    if ((flags & NNS_TOPK_MFMA) && !flag_pass_supported(k, bf16, flags)) {
+        set_error("%s: the top-K MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d)", where, k);
         return NNS_ERR_UNSUPPORTED;
     }
     TopkPlan p{};
@@ -1850,8 +1902,8 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
     NNS_TRY(range_check_radius(where, radius2));
     NNS_TRY(check_exact_only_flags(where, "range search", flags & ~(unsigned)NNS_RANGE_MFMA));
-    if ((flags & NNS_RANGE_MFMA) && (bf16 || k < 8 || k > 256)) {
-        set_error("%s: the range-MFMA flag takes fp32 points, 8 <= k <= 256 (k=%d)", where, k);
+    if ((flags & NNS_RANGE_MFMA) && !flag_pass_supported(k, bf16, flags)) {
+        set_error("%s: the range-MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d)", where, k);
         return NNS_ERR_UNSUPPORTED;
     }
     RangePlan p{};

@@ -385,6 +385,9 @@ constexpr int kBf16ImageOrder = 1;
 // the eager split operators' workgroup and ring slot (OpSplitT; filter_plan asserts them), shared by K7m's flag kernel
 constexpr int kSplitWaves = 8;        // waves per workgroup: two per SIMD
 constexpr int kSplitSlotSteps = 32;   // 1 KiB fragment steps per ring slot
+// 32-query blocks per wave of K7m's flag kernel for bf16 points (range_flag16_kernel): OpBF16K128 / OpBF16's, so that the
+// plan's query groups are filter_plan's
+constexpr int kFlag16QB = 2;
 // a chunk of K7m's evaluation and of K6m's selection is whole steps of this many flag words
 constexpr int kRmChunkWords = 64;
 
@@ -558,10 +561,14 @@ __host__ __device__ inline float record_threshold(const TauConsts &t, float a)
 // plus 2^-22 (radius2 + |x'|^2) for the roundings of the subtraction and of the two sums, which are relative to
 // max(radius2, |x'|^2) — a magnitude tau's own rounding term (sized for scores, <= (X + Y)^2) does not cover once the
 // radius is far larger than the cloud.  Monotone in radius2.  Derivation: DESIGN section 4, "K7m".
-__host__ __device__ inline float range_threshold(int kt, float qnorm2, float ymax2, float radius2)
+//
+// mode 1 (bf16 points, range_flag16_kernel): the same form over tau_consts' mode 1 — exact operands and products, the
+// order-free accumulation model, no centring (e2 = 0) — with qnorm2 = K2's uncentred |x|^2 and ymax2 the refs' largest
+// |y|^2.  Monotone in radius2 as well.  DESIGN section 4, "K7m", "bf16 points".
+__host__ __device__ inline float range_threshold(int kt, float qnorm2, float ymax2, float radius2, int mode = 3)
 {
 #pragma clang fp contract(off)
-    const TauConsts t = tau_consts(kt, qnorm2, ymax2, 3);
+    const TauConsts t = tau_consts(kt, qnorm2, ymax2, mode);
     const float a = radius2 - qnorm2;
     const float thr = record_threshold(t, a);
     return thr + 0x1p-22f * (radius2 + qnorm2);
@@ -736,6 +743,7 @@ struct RangeMfmaPlan {
     int qw;               // queries per workgroup of the flag pass
     int n_pad, total_slots, blocks, wpq;   // K2's padding; ring slots; 32-ref blocks and flag words per query
     int lazy_img;         // the ref image is in the lazy layout
+    int bf16;             // 1: bf16 points (K2's order-1 image, range_flag16_kernel, tau mode 1); 0: fp32 points
     int batch, batches;   // queries per flag-bitmap batch (whole workgroups), batches
     size_t flag_bytes;    // the bitmap of one batch
     int gx, gy, slots_per_split, lds;      // flag pass: grid of a full batch, slots per ref-range split, LDS bytes
@@ -743,7 +751,7 @@ struct RangeMfmaPlan {
     int tiles;            // tiles of the lims scan
     size_t offs_bytes, ws_bytes;   // K7's workspace layout: [m][echunks] counts (several chunks), then the tile sums
 };
-int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p);
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, bool bf16 = false);
 // radius2v (optional, K6m): the batch's per-query squared radii, used instead of radius2; a query whose entry is not
 // finite gets its flag row filled like a void query's; filled (optional): += the rows filled
 int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
@@ -767,7 +775,7 @@ struct TopkMfmaPlan {
     RangeMfmaPlan rp;     // filtered: the flag pass (its evaluation chunks are the selection's)
 };
 constexpr int kTopkMfmaMinQueries = 64;   // the filters' query floor
-int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p);
+int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, bool bf16 = false);
 // bound[i] = the distance of keys[i][kn - 1], +INF for NNS_KEY_NONE
 int launch_topk_bound(const nns_key *keys, int m, int kn, float *bound, hipStream_t st);
 // the selection of one query batch: rows [i0, i0 + rows) of out[chunks][m][kn] (one chunk: the caller's keys); stat: +=

@@ -1,4 +1,5 @@
-// range_mfma.hip — K7m: the MFMA-filtered fixed-radius search (NNS_RANGE_MFMA; fp32 points, split-bf16 operands).
+// range_mfma.hip — K7m: the MFMA-filtered fixed-radius search (NNS_RANGE_MFMA; fp32 points on split-bf16 operands,
+// bf16 points on exact operands).
 //
 // K7 evaluates V0's distance for every (query, ref) pair on the vector ALUs.  K7m asks the matrix cores first which
 // 32-ref blocks can hold a hit at all, and evaluates V0 only there:
@@ -18,19 +19,23 @@
 //               applies K7's hit predicate.  Count writes per-(query, chunk) counts in K7's layout (K7's own kernels
 //               turn them into lims); fill recomputes and writes each hit at chunk start + hits so far + ballot
 //               prefix.  Blocks, lanes and chunks ascend: index order, no atomics, identical buffers every run.
+//   bf16 points: the same ring, bitmap and evaluation; the tile is the 1-NN bf16 filter's (OpBF16T): K2's order-1
+//               image, v_mfma_f32_16x16x32_bf16, ONE product per score (the operands are exact: no hi / lo, no
+//               centring), threshold range_threshold(..., tau mode 1), 32 <= k <= 256.
 // The evaluation alone decides hits; a false flag costs time, never an answer.  Why no hit is missed: DESIGN §4 "K7m".
 //
 // Shared with the rest: the plan's geometry is filter_plan's (FilterGeom: fragment steps per block, query blocks per wave,
 // waves and queries per workgroup, padding and ring slots — the one depth-to-operator table, filter_mfma.hip) and its
 // ref-range splits are ring_pass_splits'; the workgroup and the ring slot are kSplitWaves / kSplitSlotSteps, which
 // filter_mfma.hip asserts of the eager split operators; the hit predicate, the ballot prefix, kHuge and kWsBudget are
-// nns_internal.h's.  The kernel's own: the ring loop below (same schedule as filter_main's, not the same code), the
-// fixed-threshold tile test, the bitmap and the evaluation.
+// nns_internal.h's.  The kernel's own: the ring loop below (same schedule as filter_main's, not the same code; one loop,
+// range_flag_main, for both tile bodies), the fixed-threshold tile test, the bitmap and the evaluation.
 #include "nns_internal.h"
 
 namespace nns {
 
 typedef float rm_f32x16 __attribute__((ext_vector_type(16)));
+typedef float rm_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 rm_bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kRmWaves = kSplitWaves;                  // waves per workgroup: two per SIMD
@@ -43,6 +48,7 @@ constexpr int kRmAhead = 3;                            // slots in flight ahead 
 constexpr int kRmPpw = kRmSlotSteps / kRmWaves;        // image DMA pieces per wave and slot
 constexpr int kRmEvalThreads = 256;
 constexpr int kRmEvalWaves = kRmEvalThreads / 64;
+constexpr int kRmBf16QB = kFlag16QB;                   // bf16 points: 32-query blocks per wave, at both depths
 
 __device__ __forceinline__ rm_f32x16 rm_mma(const float4 &a, const float4 &b, rm_f32x16 acc)
 {
@@ -50,12 +56,19 @@ __device__ __forceinline__ rm_f32x16 rm_mma(const float4 &a, const float4 &b, rm
                                                    0);
 }
 
+__device__ __forceinline__ rm_f32x4 rm_mma16(const float4 &a, const float4 &b, rm_f32x4 acc)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rm_bf16x8, a), __builtin_bit_cast(rm_bf16x8, b), acc, 0, 0,
+                                                   0);
+}
+
 struct RangeFlagArgs {
-    const float4 *qimg;     // the batch's query image (K2 form 2: qh, ql fragment per k-step), [rows / 32][SPB][64]
+    const float4 *qimg;     // the batch's query image (fp32 points: K2 form 2, qh, ql fragment per k-step; bf16 points:
+                            // the order-1 image), [rows / 32][SPB][64]
     const char *rimg;       // K2's ref image
-    const char *rimg_lo;    // lazy layout: the lo region; nullptr: the eager layout
+    const char *rimg_lo;    // lazy layout: the lo region; nullptr: the eager layout (and every bf16 image)
     const float *rnorm;     // [n_pad]
-    const float *qnorm;     // the batch's centred squared norms
+    const float *qnorm;     // the batch's squared norms (fp32 points: centred; bf16 points: as they are)
     const DevScalars *scal;
     unsigned *flags;        // [rows][wpq] words, bit b of a row = block b
     int rows_live;          // queries of the batch (rows beyond are padding: never flagged)
@@ -65,25 +78,33 @@ struct RangeFlagArgs {
     const float *radius2v;  // per-query squared radii of the batch (K6m's bounds); nullptr: radius2 for every query
 };
 
-// SPB: 1 KiB fragment steps per 32-ref block (kt / 8: hi, lo per 16-dim step); QB: 32-query blocks per wave
-template <int SPB, int QB>
-__global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFlagArgs a)
-{
-    constexpr int BPS = kRmSlotSteps / SPB;            // blocks per ring slot
-    constexpr int SLOT_REFS = 32 * BPS;
-    constexpr int NP = SLOT_REFS > 256 ? SLOT_REFS / 256 : 1;   // norm DMA pieces per slot
-    static_assert(kRmSlotSteps % SPB == 0 && SPB >= 2 && SPB % 2 == 0, "whole blocks per slot, hi / lo pairs");
-    static_assert(SLOT_REFS * 4 <= kRmSlotBytes - kRmSlotCoord, "norm room of a ring slot");
-    extern __shared__ __attribute__((aligned(16))) char rm_smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
-    const int qblk0 = (blockIdx.x * kRmWaves + wave) * QB;
+// ---- tile bodies: what a wave keeps resident, and what it does with one 32-ref block of a landed ring slot -------------
+// load(): the wave's B operands, the lanes' fixed thresholds and flag rows; pin(): the loads are waited for before the
+// ring starts (the compiler does not see the asm DMAs); block(): the scores of one block against the wave's queries,
+// the test and the flag.  kt / 16 = SPB 1 KiB fragments per block and QB 32-query blocks per wave, either way.
 
-    // ---- resident B operands and the lanes' fixed thresholds -------------------------------------------------
+// the threshold of query qi of the batch (tau mode MODE) and its flag row
+// (padding rows: nothing passes !(s > -INF) but a NaN or -INF score, and their rows are never read.  A norm that is not
+//  finite comes from a coordinate beyond 1e17, a per-query radius that is not finite from K6m's bound scan: that query's
+//  row is filled behind this pass)
+template <int MODE>
+__device__ __forceinline__ float rm_lane_threshold(const RangeFlagArgs &a, int qi, float ymax2)
+{
+    const float qn = a.qnorm[qi];
+    const bool live = qi < a.rows_live;
+    const float r2 = a.radius2v && live ? a.radius2v[qi] : a.radius2;
+    return live && qn < __builtin_inff() && r2 < __builtin_inff() ? range_threshold(a.kt, qn, ymax2, r2, MODE) : -__builtin_inff();
+}
+
+// fp32 points as split-bf16 operands (K2 form 2 / 3) on v_mfma_f32_32x32x16_bf16: hi, lo fragment per 16-dim step
+template <int SPB, int QB>
+struct RmSplitTile {
+    static_assert(SPB >= 2 && SPB % 2 == 0, "hi / lo pairs");
     float4 bq[QB][SPB];
     float thr[QB];
     unsigned *row[QB];   // the flag row of the lane's query
+
+    __device__ __forceinline__ void load(const RangeFlagArgs &a, int qblk0, int lane)
     {
         const float4 *src = a.qimg + (size_t)qblk0 * (SPB * 64) + lane;
         const float ymax2 = __uint_as_float(a.scal->ymax2_bits);
@@ -92,24 +113,156 @@ __global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFl
 #pragma unroll
             for (int b = 0; b < SPB; ++b) bq[st][b] = src[(st * SPB + b) * 64];
             const int qi = (qblk0 + st) * 32 + (lane & 31);
-            const float qn = a.qnorm[qi];
-            // (padding rows: nothing passes !(s > -INF) but a NaN or -INF score, and their rows are never read.  A norm
-            //  that is not finite comes from a coordinate beyond 1e17, a per-query radius that is not finite from K6m's
-            //  bound scan: that query's row is filled behind this pass)
-            const bool live = qi < a.rows_live;
-            const float r2 = a.radius2v && live ? a.radius2v[qi] : a.radius2;
-            thr[st] = live && qn < __builtin_inff() && r2 < __builtin_inff() ? range_threshold(a.kt, qn, ymax2, r2) : -__builtin_inff();
+            thr[st] = rm_lane_threshold<3>(a, qi, ymax2);
             row[st] = a.flags + (size_t)qi * a.wpq;
         }
     }
-    // the loads are waited for here, before the ring starts (the compiler does not see the asm DMAs)
+    __device__ __forceinline__ void pin()
+    {
 #pragma unroll
-    for (int st = 0; st < QB; ++st) {
+        for (int st = 0; st < QB; ++st) {
 #pragma unroll
-        for (int b = 0; b < SPB; ++b)
-            asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
-        asm volatile("" : "+v"(thr[st]));
+            for (int b = 0; b < SPB; ++b)
+                asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
+            asm volatile("" : "+v"(thr[st]));
+        }
     }
+    // slot: the ring slot; blk: the block within it; bg: the block's number = its bit in a flag row
+    __device__ __forceinline__ void block(const char *slot, int blk, int bg, int lane) const
+    {
+        const int h = lane >> 5;
+        rm_f32x16 acc0, acc1;
+        // accumulators start at |y'_j|^2 of their rows: (r & 3) + 8 (r >> 2) + 4 h
+        const float *nrm = reinterpret_cast<const float *>(slot + kRmSlotCoord) + blk * 32 + 4 * h;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 nv = *reinterpret_cast<const float4 *>(nrm + 8 * g);
+            acc0[4 * g + 0] = nv.x;
+            acc0[4 * g + 1] = nv.y;
+            acc0[4 * g + 2] = nv.z;
+            acc0[4 * g + 3] = nv.w;
+        }
+        acc1 = acc0;
+        const float4 *fp = reinterpret_cast<const float4 *>(slot + blk * (SPB * 1024)) + lane;
+#pragma unroll
+        for (int b = 0; b < SPB; b += 2) {
+            const float4 rh = fp[b * 64], rl = fp[(b + 1) * 64];
+            // ref hi x (qh, ql) of the k-step, ref lo x qh
+            acc0 = rm_mma(rh, bq[0][b], acc0);
+            if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b], acc1);
+            acc0 = rm_mma(rh, bq[0][b + 1], acc0);
+            if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b + 1], acc1);
+            acc0 = rm_mma(rl, bq[0][b], acc0);
+            if constexpr (QB == 2) acc1 = rm_mma(rl, bq[1][b], acc1);
+        }
+#pragma unroll
+        for (int st = 0; st < QB; ++st) {
+            const rm_f32x16 t = st == 0 ? acc0 : acc1;
+            bool pass = false;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) pass = pass || !(t[r] > thr[st]);   // (a NaN score passes)
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(pass) != 0ull, 0)) {   // rare, wave-uniform
+                if (pass) atomicOr(row[st] + (bg >> 5), 1u << (bg & 31));
+            }
+        }
+    }
+};
+
+// bf16 points, exact operands, on v_mfma_f32_16x16x32_bf16 over K2's order-1 image (prep_kernels.hip): fragment
+// (kt / 32) t + ks of a 32-point block holds, at lane l, dims 32 ks + 8 (l >> 4) .. + 7 of point 16 t + (l & 15).  Refs
+// are A, queries B; C lane l holds query column l & 15 and ref rows 4 (l >> 4) .. + 3.  The wave's 2 QB query tiles keep
+// all their k-steps resident (2 QB kt / 32 fragments: 64 registers at kt = 128, 128 at kt = 256); per block, each of
+// the two 16-ref tiles x 2 QB query tiles owns one accumulator, seeded with its four rows' norms.  Through the builtin:
+// the compiler keeps the MFMA hazards.
+template <int SPB, int QB>
+struct RmBf16Tile {
+    static constexpr int NKS = SPB / 2;   // 32-dim k-steps: kt / 32
+    static constexpr int NQT = 2 * QB;    // 16-query tiles per wave
+    static_assert(SPB == 8 || SPB == 16, "kt = 128 / 256: OpBF16K128 / OpBF16's blocks");
+    float4 bq[NQT][NKS];
+    float thr[NQT];
+    unsigned *row[NQT];   // the flag row of the lane's query of tile qt: 16 qt + (lane & 15) of the wave's queries
+
+    __device__ __forceinline__ void load(const RangeFlagArgs &a, int qblk0, int lane)
+    {
+        const float4 *src = a.qimg + (size_t)qblk0 * (SPB * 64) + lane;
+        const float ymax2 = __uint_as_float(a.scal->ymax2_bits);
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+            // query block qt >> 1 of the wave, its point tile qt & 1
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) bq[qt][ks] = src[((qt >> 1) * SPB + (qt & 1) * NKS + ks) * 64];
+            const int qi = qblk0 * 32 + 16 * qt + (lane & 15);
+            thr[qt] = rm_lane_threshold<1>(a, qi, ymax2);
+            row[qt] = a.flags + (size_t)qi * a.wpq;
+        }
+    }
+    __device__ __forceinline__ void pin()
+    {
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks)
+                asm volatile("" : "+v"(bq[qt][ks].x), "+v"(bq[qt][ks].y), "+v"(bq[qt][ks].z), "+v"(bq[qt][ks].w));
+            asm volatile("" : "+v"(thr[qt]));
+        }
+    }
+    __device__ __forceinline__ void block(const char *slot, int blk, int bg, int lane) const
+    {
+        rm_f32x4 acc[2][NQT];
+        // accumulators start at |y_j|^2 of their rows: 16 rt + 4 (lane >> 4) + 0 .. 3
+        const float *nrm = reinterpret_cast<const float *>(slot + kRmSlotCoord) + blk * 32 + 4 * (lane >> 4);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            const float4 nv = *reinterpret_cast<const float4 *>(nrm + 16 * rt);
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) acc[rt][qt] = rm_f32x4{nv.x, nv.y, nv.z, nv.w};
+        }
+        const float4 *fp = reinterpret_cast<const float4 *>(slot + blk * (SPB * 1024)) + lane;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const float4 r0 = fp[ks * 64], r1 = fp[(NKS + ks) * 64];
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) {
+                acc[0][qt] = rm_mma16(r0, bq[qt][ks], acc[0][qt]);
+                acc[1][qt] = rm_mma16(r1, bq[qt][ks], acc[1][qt]);
+            }
+        }
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+            bool pass = false;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pass = pass || !(acc[rt][qt][e] > thr[qt]);   // (a NaN score passes)
+            // (the four lanes of a query, and both ref tiles, set the same bit)
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(pass) != 0ull, 0)) {   // rare, wave-uniform
+                if (pass) atomicOr(row[qt] + (bg >> 5), 1u << (bg & 31));
+            }
+        }
+    }
+};
+
+// The flag pass of one workgroup: the ring over the refs of split blockIdx.y, TILE's body on every block of every slot.
+// SPB: 1 KiB fragment steps per 32-ref block of K2's image (a ring slot is kRmSlotSteps of them, contiguous in the eager
+// addressing); QB: 32-query blocks per wave
+template <int SPB, int QB, class TILE>
+__device__ __forceinline__ void range_flag_main(const RangeFlagArgs &a)
+{
+    constexpr int BPS = kRmSlotSteps / SPB;            // blocks per ring slot
+    constexpr int SLOT_REFS = 32 * BPS;
+    constexpr int NP = SLOT_REFS > 256 ? SLOT_REFS / 256 : 1;   // norm DMA pieces per slot
+    static_assert(kRmSlotSteps % SPB == 0 && SPB >= 2, "whole blocks per slot");
+    static_assert(SLOT_REFS * 4 <= kRmSlotBytes - kRmSlotCoord, "norm room of a ring slot");
+    extern __shared__ __attribute__((aligned(16))) char rm_smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int qblk0 = (blockIdx.x * kRmWaves + wave) * QB;
+
+    // ---- resident B operands and the lanes' fixed thresholds -------------------------------------------------
+    TILE tile;
+    tile.load(a, qblk0, lane);
+    tile.pin();
 
     const int slot0 = blockIdx.y * a.slots_per_split;
     int ns = a.total_slots - slot0;
@@ -168,49 +321,28 @@ __global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFl
         if (s + kRmAhead < ns) issue(s + kRmAhead);
         const char *slot = rm_smem + (s & (kRmRing - 1)) * kRmSlotBytes;
 #pragma unroll 1
-        for (int blk = 0; blk < BPS; ++blk) {
-            rm_f32x16 acc0, acc1;
-            // accumulators start at |y'_j|^2 of their rows: (r & 3) + 8 (r >> 2) + 4 h
-            const float *nrm = reinterpret_cast<const float *>(slot + kRmSlotCoord) + blk * 32 + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 nv = *reinterpret_cast<const float4 *>(nrm + 8 * g);
-                acc0[4 * g + 0] = nv.x;
-                acc0[4 * g + 1] = nv.y;
-                acc0[4 * g + 2] = nv.z;
-                acc0[4 * g + 3] = nv.w;
-            }
-            acc1 = acc0;
-            const float4 *fp = reinterpret_cast<const float4 *>(slot + blk * (SPB * 1024)) + lane;
-#pragma unroll
-            for (int b = 0; b < SPB; b += 2) {
-                const float4 rh = fp[b * 64], rl = fp[(b + 1) * 64];
-                // ref hi x (qh, ql) of the k-step, ref lo x qh
-                acc0 = rm_mma(rh, bq[0][b], acc0);
-                if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b], acc1);
-                acc0 = rm_mma(rh, bq[0][b + 1], acc0);
-                if constexpr (QB == 2) acc1 = rm_mma(rh, bq[1][b + 1], acc1);
-                acc0 = rm_mma(rl, bq[0][b], acc0);
-                if constexpr (QB == 2) acc1 = rm_mma(rl, bq[1][b], acc1);
-            }
-            const int bg = (slot0 + s) * BPS + blk;   // the block's number = its bit in a flag row
-#pragma unroll
-            for (int st = 0; st < QB; ++st) {
-                const rm_f32x16 t = st == 0 ? acc0 : acc1;
-                bool pass = false;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pass = pass || !(t[r] > thr[st]);   // (a NaN score passes)
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(pass) != 0ull, 0)) {   // rare, wave-uniform
-                    if (pass) atomicOr(row[st] + (bg >> 5), 1u << (bg & 31));
-                }
-            }
-        }
+        for (int blk = 0; blk < BPS; ++blk) tile.block(slot, blk, (slot0 + s) * BPS + blk, lane);
     }
+}
+
+// fp32 points: SPB = kt / 8 (hi, lo per 16-dim step)
+template <int SPB, int QB>
+__global__ __launch_bounds__(kRmWaves * 64) void range_flag_kernel(const RangeFlagArgs a)
+{
+    range_flag_main<SPB, QB, RmSplitTile<SPB, QB>>(a);
+}
+
+// bf16 points: SPB = kt / 16 — 8 (kt = 128, four blocks per ring slot) or 16 (kt = 256, two)
+template <int SPB, int QB>
+__global__ __launch_bounds__(kRmWaves * 64) void range_flag16_kernel(const RangeFlagArgs a)
+{
+    range_flag_main<SPB, QB, RmBf16Tile<SPB, QB>>(a);
 }
 
 // one wave per query of the batch: a non-finite coordinate or |v| >= 1e17 — or, with per-query radii, a radius that is
 // not finite — fills the query's flag row; filled (optional): += 1 per filled row
-__global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, int rows, const float *__restrict__ q,
+template <typename T>
+__global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, int rows, const T *__restrict__ q,
                                                                          unsigned *__restrict__ flags, int wpq,
                                                                          const float *__restrict__ radius2v,
                                                                          unsigned long long *__restrict__ filled)
@@ -219,7 +351,7 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, 
     const int64_t i = (int64_t)blockIdx.x * kRmEvalWaves + (threadIdx.x >> 6);
     if (i >= rows) return;   // (whole waves)
     bool bad = false;
-    for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(q[(size_t)i * k + t]) < kHuge);
+    for (int t = lane; t < k; t += 64) bad = bad || !(fabsf(pt_ld1(q + (size_t)i * k + t)) < kHuge);
     if (radius2v) bad = bad || !(radius2v[i] < __builtin_inff());
     if (__ballot(bad) == 0ull) return;
     for (int w = lane; w < wpq; w += 64) flags[(size_t)i * wpq + w] = 0xFFFFFFFFu;
@@ -230,23 +362,23 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_void_rows_kernel(int k, 
 // [c * per, min((c + 1) * per, wpq)).  offs: [m][chunks] (several chunks): count writes the chunk's hits, fill reads the
 // chunk's start within the query's segment.  lims: count writes lims[i + 1] (one chunk), fill reads lims[i], lims[i + 1].
 // stat[0] (count): += the wave's flagged blocks that hold a ref below n.
-template <int VEC, bool FILL>
+template <int VEC, bool FILL, typename T>
 __global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int rows, int i0, int n, int per, int chunks,
-                                                                    int wpq, float radius2, const float *__restrict__ q,
-                                                                    const float *__restrict__ r,
+                                                                    int wpq, float radius2, const T *__restrict__ q,
+                                                                    const T *__restrict__ r,
                                                                     const unsigned *__restrict__ flags, int64_t index_base,
                                                                     int64_t *__restrict__ lims, int *__restrict__ offs,
                                                                     int *__restrict__ idx, float *__restrict__ dist,
                                                                     unsigned long long *__restrict__ stat)
 {
-    extern __shared__ __attribute__((aligned(16))) float rm_sq[];   // [waves][k]: each wave's query
+    extern __shared__ __attribute__((aligned(16))) float rm_sq[];   // [waves][k]: each wave's query, widened to fp32
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * kRmEvalWaves + wave;
     if (row >= rows) return;   // (whole waves; no workgroup barrier below)
     const int64_t i = i0 + row;
     const int c = blockIdx.y;
     float *sq = rm_sq + (size_t)wave * k;
-    for (int t = lane; t < k; t += 64) sq[t] = q[(size_t)i * k + t];
+    for (int t = lane; t < k; t += 64) sq[t] = pt_ld1(q + (size_t)i * k + t);
     // (the wave reads only what it wrote itself: LDS operations of one wave complete in order)
     const unsigned *frow = flags + (size_t)row * wpq;
     const int w0 = c * per, w1 = w0 + per < wpq ? w0 + per : wpq;
@@ -309,19 +441,25 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int r
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p)
+// The flag kernels of bf16 points keep OpBF16K128 / OpBF16's geometry (filter_mfma.hip): 8 or 16 fragments per block, two
+// query blocks per wave (64 / 128 resident operand registers, no scratch), the split operators' workgroup and ring slot
+static_assert(kRmBf16QB * kRmWaves * 32 == 512, "filter_plan's queries per workgroup at the 16x16x32 depths");
+
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, bool bf16)
 {
     if (k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
-    if (k < 8 || k > 256) {
-        set_error("the range-MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
+    if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
+        set_error(bf16 ? "the range-MFMA flag: k = %d outside 32 .. 256 (bf16 points: the 16x16x32 tiles)"
+                       : "the range-MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
     }
     FilterGeom g{};
-    NNS_TRY(filter_plan(k, m, n, false, &g, false, false, true, split_eager));
-    if (!g.split) {
-        set_error("the range-MFMA flag: no split-bf16 tile for k = %d", k);
+    NNS_TRY(filter_plan(k, m, n, bf16, &g, false, false, !bf16, split_eager));
+    if (bf16 ? (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && g.spb != 16)) : !g.split) {
+        set_error("the range-MFMA flag: no %s tile for k = %d", bf16 ? "16x16x32 bf16" : "split-bf16", k);
         return NNS_ERR_UNSUPPORTED;
     }
+    p->bf16 = bf16 ? 1 : 0;
     p->kt = g.kt;
     p->spb = g.spb;
     p->qb = g.qb;
@@ -368,6 +506,11 @@ static int launch_flag_t(const RangeMfmaPlan &p, const RangeFlagArgs &a, int gx,
 {
     return launch_lds(range_flag_kernel<SPB, QB>, dim3(gx, p.gy), dim3(kRmWaves * 64), (size_t)kRmLds, st, a);
 }
+template <int SPB>
+static int launch_flag16_t(const RangeMfmaPlan &p, const RangeFlagArgs &a, int gx, hipStream_t st)
+{
+    return launch_lds(range_flag16_kernel<SPB, kRmBf16QB>, dim3(gx, p.gy), dim3(kRmWaves * 64), (size_t)kRmLds, st, a);
+}
 
 // the flag pass of one query batch: rows [i0, i0 + rows) of the prepared query image / norms; the bitmap is zeroed on
 // the stream first, void queries' rows are filled behind the pass
@@ -395,9 +538,14 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
     a.radius2 = radius2;
     a.radius2v = radius2v;
     const int gx = rows_pad / p.qw;
-    // (spb, qb) of the five eager split operators
+    // (spb, qb) of the two 16x16x32 bf16 operators, of the five eager split operators
     const auto is = [&p](int spb, int qb) { return p.spb == spb && p.qb == qb; };
-    if (is(2, 2)) NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st)));
+    if (p.bf16 && is(8, kRmBf16QB)) NNS_TRY((launch_flag16_t<8>(p, a, gx, st)));
+    else if (p.bf16 && is(16, kRmBf16QB)) NNS_TRY((launch_flag16_t<16>(p, a, gx, st)));
+    else if (p.bf16) {
+        set_error("the range-MFMA flag: no bf16 flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
+        return NNS_ERR_UNSUPPORTED;
+    } else if (is(2, 2)) NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st)));
     else if (is(4, 2)) NNS_TRY((launch_flag_t<4, 2>(p, a, gx, st)));
     else if (is(8, 2)) NNS_TRY((launch_flag_t<8, 2>(p, a, gx, st)));
     else if (is(16, 2)) NNS_TRY((launch_flag_t<16, 2>(p, a, gx, st)));
@@ -406,27 +554,45 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
         set_error("the range-MFMA flag: no flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
         return NNS_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(range_void_rows_kernel, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k, rows,
-                       (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v, filled);
+    if (p.bf16)
+        hipLaunchKernelGGL(range_void_rows_kernel<uint16_t>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k,
+                           rows, (const uint16_t *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v,
+                           filled);
+    else
+        hipLaunchKernelGGL(range_void_rows_kernel<float>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k, rows,
+                           (const float *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v, filled);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
 
 // the evaluation of one query batch (fill: idx / dist; count: the per-(query, chunk) counts and stat[0])
+template <typename T>
+static int launch_range_eval_t(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows, int n, const T *q, const T *r,
+                               const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx,
+                               float *dist, unsigned long long *stat, hipStream_t st)
+{
+    int *offs = p.echunks > 1 ? (int *)ws : nullptr;
+    // (K7's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) aligned)
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    const dim3 grid(divup(rows, kRmEvalWaves), p.echunks);
+    const size_t lds = (size_t)kRmEvalWaves * k * sizeof(float);
+    auto go = [&](auto kern) {
+        return launch_lds(kern, grid, dim3(kRmEvalThreads), lds, st, k, rows, i0, n, p.eper, p.echunks, p.wpq, radius2, q, r,
+                          (const unsigned *)flags, base, lims, offs, idx, dist, stat);
+    };
+    if (fill) return vec ? go(range_eval_kernel<4, true, T>) : go(range_eval_kernel<1, true, T>);
+    return vec ? go(range_eval_kernel<4, false, T>) : go(range_eval_kernel<1, false, T>);
+}
+
 int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows, int n, const void *q, const void *r,
                       const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
                       unsigned long long *stat, hipStream_t st)
 {
-    int *offs = p.echunks > 1 ? (int *)ws : nullptr;
-    const bool vec = (k % 4 == 0) && (((uintptr_t)r & 15) == 0);
-    const dim3 grid(divup(rows, kRmEvalWaves), p.echunks);
-    const size_t lds = (size_t)kRmEvalWaves * k * sizeof(float);
-    auto go = [&](auto kern) {
-        return launch_lds(kern, grid, dim3(kRmEvalThreads), lds, st, k, rows, i0, n, p.eper, p.echunks, p.wpq, radius2,
-                          (const float *)q, (const float *)r, (const unsigned *)flags, base, lims, offs, idx, dist, stat);
-    };
-    if (fill) return vec ? go(range_eval_kernel<4, true>) : go(range_eval_kernel<1, true>);
-    return vec ? go(range_eval_kernel<4, false>) : go(range_eval_kernel<1, false>);
+    if (p.bf16)
+        return launch_range_eval_t(p, fill, k, i0, rows, n, (const uint16_t *)q, (const uint16_t *)r, flags, radius2, base,
+                                   lims, ws, idx, dist, stat, st);
+    return launch_range_eval_t(p, fill, k, i0, rows, n, (const float *)q, (const float *)r, flags, radius2, base, lims, ws,
+                               idx, dist, stat, st);
 }
 
 }  // namespace nns

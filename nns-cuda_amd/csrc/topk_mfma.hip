@@ -1,4 +1,5 @@
-// topk_mfma.hip — K6m: the MFMA-filtered top-K search (NNS_TOPK_MFMA; fp32 points, split-bf16 operands).
+// topk_mfma.hip — K6m: the MFMA-filtered top-K search (NNS_TOPK_MFMA; fp32 points on split-bf16 operands, bf16 points
+// on exact operands: K7m's two flag kernels).
 //
 // K6 evaluates V0's distance for every (query, ref) pair.  K6m first finds, per query, a distance U that the kn-th
 // nearest ref cannot exceed, asks the matrix cores which 32-ref blocks can hold a ref within U, and selects among those:
@@ -39,9 +40,9 @@ __global__ void topk_bound_kernel(const nns_key *__restrict__ keys, int m, int k
 
 // grid = queries of the batch x chunks.  Query i = i0 + blockIdx.x (flag row blockIdx.x), flag words [c * per,
 // min((c + 1) * per, wpq)); its sorted list goes to out[(c * m + i) * kn ...].
-template <int VEC>
+template <int VEC, typename T>
 __global__ __launch_bounds__(kTopkThreads) void topk_select_kernel(int k, int i0, int m, int n, int kn, int per, int wpq,
-                                                                   const float *__restrict__ q, const float *__restrict__ r,
+                                                                   const T *__restrict__ q, const T *__restrict__ r,
                                                                    const unsigned *__restrict__ flags,
                                                                    const float *__restrict__ bound, int64_t index_base,
                                                                    nns_key *__restrict__ out,
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_select_kernel(int k, int i0
     const int64_t i = (int64_t)i0 + blockIdx.x;
     const int c = blockIdx.y;
 
-    for (int t = tid; t < k; t += kTopkThreads) sq[t] = q[(size_t)i * k + t];
+    for (int t = tid; t < k; t += kTopkThreads) sq[t] = pt_ld1(q + (size_t)i * k + t);   // (widened to fp32)
     for (int e = tid; e < 2 * kn; e += kTopkThreads) lists[e] = NNS_KEY_NONE;
     if (tid == 0) qcnt[0] = 0;
     // d0 == U passes, anything above (a false flag's refs) does not; no finite bound: every selectable key passes
@@ -141,15 +142,16 @@ __global__ __launch_bounds__(kTopkThreads) void topk_select_kernel(int k, int i0
 // keeps the scan's list warm-up small against the sample.  Where that asks for more than every second block and the
 // unweighted rule (w = 1) does not, every second block is taken.  Every floor(blocks / sb)-th block is taken, so the
 // sample is spread over the whole ref range.
-int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p)
+int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, bool bf16)
 {
     if (k <= 0 || m <= 0 || n <= 0 || kn <= 0) return NNS_ERR_INVALID;
     if (kn > NNS_TOPK_MAX) {
         set_error("top-K: kn = %d above 256", kn);
         return NNS_ERR_UNSUPPORTED;
     }
-    if (k < 8 || k > 256) {
-        set_error("the top-K MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
+    if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
+        set_error(bf16 ? "the top-K MFMA flag: k = %d outside 32 .. 256 (bf16 points: the 16x16x32 tiles)"
+                       : "the top-K MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
     }
     *p = TopkMfmaPlan{};
@@ -171,7 +173,7 @@ int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *
     p->sample_refs = (int)((int64_t)(p->sample_blocks - 1) * 32 + (n - last < 32 ? n - last : 32));
     p->lds = (int)topk_select_lds(k, kn);
     if (p->stride < 2 || m < kTopkMfmaMinQueries) return NNS_OK;
-    if (range_mfma_plan(k, m, n, split_eager, &p->rp) != NNS_OK) {
+    if (range_mfma_plan(k, m, n, split_eager, &p->rp, bf16) != NNS_OK) {
         p->rp = RangeMfmaPlan{};
         return NNS_OK;
     }
@@ -189,14 +191,27 @@ int launch_topk_bound(const nns_key *keys, int m, int kn, float *bound, hipStrea
     return NNS_OK;
 }
 
+template <typename T>
+static int launch_topk_select_t(const TopkMfmaPlan &p, int k, int i0, int rows, int m, int n, int kn, const T *q, const T *r,
+                                const void *flags, const float *bound, int64_t base, nns_key *out,
+                                unsigned long long *stat, hipStream_t st)
+{
+    // (K6's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) aligned)
+    const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
+    return launch_lds(vec ? topk_select_kernel<4, T> : topk_select_kernel<1, T>, dim3(rows, p.rp.echunks), dim3(kTopkThreads),
+                      topk_select_lds(k, kn), st, k, i0, m, n, kn, p.rp.eper, p.rp.wpq, q, r, (const unsigned *)flags, bound,
+                      base, out, stat);
+}
+
 int launch_topk_select(const TopkMfmaPlan &p, int k, int i0, int rows, int m, int n, int kn, const void *q, const void *r,
                        const void *flags, const float *bound, int64_t base, nns_key *out, unsigned long long *stat,
                        hipStream_t st)
 {
-    const bool vec = (k % 4 == 0) && (((uintptr_t)r & 15) == 0);
-    return launch_lds(vec ? topk_select_kernel<4> : topk_select_kernel<1>, dim3(rows, p.rp.echunks), dim3(kTopkThreads),
-                      topk_select_lds(k, kn), st, k, i0, m, n, kn, p.rp.eper, p.rp.wpq, (const float *)q, (const float *)r,
-                      (const unsigned *)flags, bound, base, out, stat);
+    if (p.rp.bf16)
+        return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const uint16_t *)q, (const uint16_t *)r, flags, bound, base,
+                                    out, stat, st);
+    return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const float *)q, (const float *)r, flags, bound, base, out, stat,
+                                st);
 }
 
 }  // namespace nns

@@ -34,8 +34,10 @@ NNS_KEY_NONE = 0x7F80000000000000
 NNS_RECORDS_PER_REF = 512
 NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
 NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three products per tile) at every depth
-NNS_RANGE_MFMA = 4096   # range search through the MFMA flag pass (K7m): fp32 points, split-bf16 operands, 8 <= k <= 256
-NNS_TOPK_MFMA = 8192    # top-K through the bound / flag / select path (K6m): fp32 points, split-bf16 operands, 8 <= k <= 256
+# range search through the MFMA flag pass (K7m) / top-K through the bound / flag / select path (K6m): fp32 points on
+# split-bf16 operands, 8 <= k <= 256; bf16 points on exact operands, 32 <= k <= 256
+NNS_RANGE_MFMA = 4096
+NNS_TOPK_MFMA = 8192
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -57,10 +59,12 @@ ABI_SYMBOLS = (
     "nns_index_range_info", "nns_plan_range_mfma", "nns_range_threshold",
     "nns_index_topk_info", "nns_plan_topk_mfma",
     "nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
+    "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
-OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16")
+OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
+                    "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -157,7 +161,10 @@ def _load() -> ctypes.CDLL:
     lib.nns_last_error.argtypes = []
     lib.nns_last_error.restype = ctypes.c_char_p
     lib.nns_version.argtypes = []
-    optional = {"nns_filter_lazy_tile": [], "nns_selftest_mfma_lazy16": [c_vp, c_vp, c_vp, c_vp, c_vp]}
+    optional = {"nns_filter_lazy_tile": [], "nns_selftest_mfma_lazy16": [c_vp, c_vp, c_vp, c_vp, c_vp],
+                "nns_plan_range_mfma_bf16": lib.nns_plan_range_mfma.argtypes,
+                "nns_plan_topk_mfma_bf16": lib.nns_plan_topk_mfma.argtypes,
+                "nns_range_threshold_bf16": lib.nns_range_threshold.argtypes}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -273,32 +280,44 @@ def plan_range(k: int, m: int, n: int, bf16: bool = False) -> dict:
     return dict(zip(names, (int(v) for v in out)))
 
 
-def plan_range_mfma(k: int, m: int, n: int, flags: int = 0) -> dict:
+def plan_range_mfma(k: int, m: int, n: int, flags: int = 0, *, bf16: bool = False) -> dict:
     """nns_plan_range_mfma: the launch geometry of the MFMA-filtered range search (K7m) for a shape (host only);
-    flags: the index's (NNS_FILTER_SPLIT_EAGER selects the eager ref image layout)."""
+    flags: the index's (NNS_FILTER_SPLIT_EAGER selects the eager ref image layout).  bf16: the plan for bf16 points
+    (nns_plan_range_mfma_bf16; layout 2 = the order-1 16x16x32 image)."""
     out = np.zeros(10, np.int32)
-    _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
+    if bf16:
+        _check(lib.nns_plan_range_mfma_bf16(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma_bf16")
+    else:
+        _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
     names = ("kt", "block_refs", "blocks_per_query", "batch", "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes",
              "layout")
     return dict(zip(names, (int(v) for v in out)))
 
 
-def plan_topk_mfma(k: int, m: int, n: int, kn: int, flags: int = 0) -> dict:
+def plan_topk_mfma(k: int, m: int, n: int, kn: int, flags: int = 0, *, bf16: bool = False) -> dict:
     """nns_plan_topk_mfma: the plan of the MFMA-filtered top-K search (K6m) for a shape (host only): the block sample of
     the bound scan, whether the filtered path is taken, and then plan_range_mfma's fields, the selection's chunks per
-    query and flag words per chunk (zeros otherwise), and the LDS bytes of a selection workgroup."""
+    query and flag words per chunk (zeros otherwise), and the LDS bytes of a selection workgroup.  bf16: the plan for
+    bf16 points (nns_plan_topk_mfma_bf16)."""
     out = np.zeros(17, np.int32)
-    _check(lib.nns_plan_topk_mfma(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma")
+    if bf16:
+        _check(lib.nns_plan_topk_mfma_bf16(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma_bf16")
+    else:
+        _check(lib.nns_plan_topk_mfma(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma")
     names = ("sample_blocks", "stride", "sample_refs", "filtered", "kt", "block_refs", "blocks_per_query", "batch",
              "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes", "layout", "chunks", "chunk_words",
              "select_lds_bytes")
     return dict(zip(names, (int(v) for v in out)))
 
 
-def range_threshold(kt: int, qnorm2: float, ymax2: float, radius2: float) -> float:
-    """nns_range_threshold: the score threshold K7m's flag pass gives a query (host only)."""
+def range_threshold(kt: int, qnorm2: float, ymax2: float, radius2: float, *, bf16: bool = False) -> float:
+    """nns_range_threshold: the score threshold K7m's flag pass gives a query (host only).  bf16: the threshold of a
+    bf16 query (nns_range_threshold_bf16: exact operands, uncentred norms)."""
     out = np.zeros(1, np.float32)
-    _check(lib.nns_range_threshold(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold")
+    if bf16:
+        _check(lib.nns_range_threshold_bf16(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold_bf16")
+    else:
+        _check(lib.nns_range_threshold(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold")
     return float(out[0])
 
 
@@ -456,13 +475,14 @@ def search_topk(query_points, reference_points, kn: int, *, return_distances: bo
 
 
 def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: bool = False, shards: int = 1,
-                     path: str = "auto", device: int = 0, refs_soa: bool = False):
-    """search_topk() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_topk)."""
+                     path: str = "auto", device: int = 0, refs_soa: bool = False, topk_mfma: bool = False):
+    """search_topk() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_topk).  topk_mfma: NNS_TOPK_MFMA
+    (32 <= k <= 256 for bf16 points)."""
     q = np.ascontiguousarray(query_bits, dtype=np.uint16)
     r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
     if q.ndim != 2 or r.ndim != 2:
         raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
-    return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa)
+    return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa, topk_mfma)
 
 
 def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
@@ -503,13 +523,14 @@ def search_range(query_points, reference_points, radius2: float, *, return_dista
 
 
 def search_range_bf16(query_bits, reference_bits, radius2: float, *, return_distances: bool = False,
-                      path: str = "auto", device: int = 0, refs_soa: bool = False):
-    """search_range() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_range)."""
+                      path: str = "auto", device: int = 0, refs_soa: bool = False, range_mfma: bool = False):
+    """search_range() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_range).  range_mfma:
+    NNS_RANGE_MFMA (32 <= k <= 256 for bf16 points)."""
     q = np.ascontiguousarray(query_bits, dtype=np.uint16)
     r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
     if q.ndim != 2 or r.ndim != 2:
         raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
-    return _search_range(q, r, radius2, True, return_distances, path, device, refs_soa)
+    return _search_range(q, r, radius2, True, return_distances, path, device, refs_soa, range_mfma)
 
 
 # ---------------------------------------------------------------------------
