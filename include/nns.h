@@ -248,11 +248,47 @@ int nns_search_bf16_ex(int k, int m, int n, const uint16_t *s_points,
                        const uint16_t *r_points, int *idx_out, float *dist_out,
                        int num_shards, unsigned flags, int device);
 
+/* fp16 points (IEEE binary16: stored embeddings, point clouds).  Arrays hold raw binary16 bit patterns (uint16_t),
+ * same [points][k] layout.  Semantics: the bf16 contract with one word changed — V0's arithmetic on the values widened
+ * exactly to fp32 (subnormals, INF and NaN included); indices bit-exact, distances bit-equal, lowest index wins ties,
+ * NaN and +INF distances never selected.  An index and its queries must have the same dtype: an fp16 index searched
+ * through nns_index_search / nns_index_search_bf16 (or an fp32 / bf16 index through nns_index_search_f16) returns
+ * NNS_ERR_INVALID.  The dtype-agnostic entry points (nns_index_search_indices, nns_index_search_topk,
+ * nns_index_range_count / nns_index_range_fill, nns_index_refresh, nns_index_stats, nns_index_near_ties) serve an fp16
+ * index like any other; top-K, range search and the nns_keys_* helpers keep their contracts.
+ * Flags: NNS_PATH_AUTO / NNS_PATH_EXACT / NNS_PATH_MFMA, NNS_PROFILE, NNS_REFS_SOA, NNS_RECORDS_PER_REF.  The operand
+ * flags of fp32 points (NNS_FILTER_BF16, NNS_FILTER_F32, NNS_FILTER_SPLIT_EAGER): NNS_ERR_INVALID, as for bf16 points.
+ * NNS_RANGE_MFMA and NNS_TOPK_MFMA are not built for fp16 points: NNS_ERR_UNSUPPORTED (at create, in the whole calls and
+ * in nns_plan_filter), answered like the operand flags before the device is looked up.
+ * MFMA filter: 32 <= k <= 256 with at least 64 queries (the AUTO rule of bf16 points), on v_mfma_f32_16x16x32_f16 at
+ * KT = 128 / 256 over K2's order-1 image of binary16 operands; two binary16 values multiply exactly in fp32, so the margin
+ * is the exact-operand one (nns_tau_consts mode 4, nns_index_filter_form 4).  k < 32 and 256 < k <= 16384 take the exact
+ * kernels under AUTO; NNS_PATH_MFMA with k > 256: NNS_ERR_UNSUPPORTED.
+ * Range guard: the ref image holds -2 v narrowed to binary16, finite only for |v| <= 32752.  Refs with a larger value
+ * (32768 .. 65504), like NaN and INF, void the filter: the index searches with the exact kernels and
+ * nns_stats.nonfinite reads 1.  Queries are not scaled: only their NaN / INF matter (those searches re-rank every query
+ * with the exact scan, as for the other dtypes).
+ * Measured on the MI355X (tests/test_f16_gpu.py; DESIGN section 4, "fp16 points"): the f16 MFMA's worst
+ * |hardware - fp64| is 0.0143 (KT = 128) / 0.0102 (KT = 256) of the mode-4 e3 bound, against the 1/4 allowed, so the
+ * allowance stays 2u per add.  Subnormal binary16 operands (|v| < 2^-14, nonzero) are NOT flushed by the f16 MFMA
+ * (all-subnormal and every-tenth-subnormal operands: 0.0049 / 0.0037 of the bound): they go through the filter like
+ * any value, with no void condition and no floor in tau.  Times (tools/probe_f16.py, profiles/f16_probe.json, next to a
+ * bf16 index on the same values rounded to bf16): 4096 x 1 M x 128 0.845 ms per search (filter 0.758 ms) against 0.806
+ * (0.718) ms, the f16 filter 5.6 % slower; 65536 x 65536 x 32 0.815 against 0.807 ms, equal within the rounds' spread. */
+int nns_index_create_f16(nns_index **out, int device, int k, int n,
+                         const uint16_t *r_dev, int64_t index_base,
+                         unsigned flags, void *stream);
+int nns_index_search_f16(nns_index *ix, int m, const uint16_t *q_dev,
+                         nns_key *keys_dev, void *stream);
+int nns_search_f16_ex(int k, int m, int n, const uint16_t *s_points,
+                      const uint16_t *r_points, int *idx_out, float *dist_out,
+                      int num_shards, unsigned flags, int device);
+
 /* nns_index_search + nns_keys_unpack in one call for the single-shard case (what the reference's
  * cudaCall hands back is indices): keys_dev[m] as above AND idx_dev[m] = index of each key (0 for
  * NNS_KEY_NONE, as V0), dist_dev (optional) = its fp32 distance.  The low-dimensional exact kernel
  * writes all three in its one launch; the other paths append the unpack kernel.  q_dev has the
- * index's dtype (fp32, or bf16 bit patterns). */
+ * index's dtype (fp32, or bf16 / fp16 bit patterns). */
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev,
                              int *idx_dev, float *dist_dev, void *stream);
 
@@ -306,9 +342,13 @@ int nns_search_f32_topk(int k, int m, int n, const float *s_points, const float 
                         float *dist_out, int num_shards, unsigned flags, int device);
 int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
                          int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
+/* fp16 points (binary16 bit patterns): the same call; NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED. */
+int nns_search_f16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
+                        int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the top-K launch geometry for a k-D search of m queries over n refs.
  * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
- * split-workspace keys (0 with one split)}. */
+ * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16 points (the 16-bit types share one
+ * geometry: their refs are widened as they are read). */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
 
 /* ---- top-K on the matrix cores (NNS_TOPK_MFMA, K6m) -------------------------------
@@ -385,9 +425,12 @@ int nns_search_f32_range(int k, int m, int n, const float *s_points, const float
                          int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
                           int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+/* fp16 points (binary16 bit patterns): the same call; NNS_RANGE_MFMA: NNS_ERR_UNSUPPORTED. */
+int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
+                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the range search's launch geometry for a k-D search of m queries over n
  * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
- * workgroup, workspace bytes}. */
+ * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16 points. */
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
 
 /* ---- range search on the matrix cores (NNS_RANGE_MFMA, K7m) ------------------------
@@ -450,7 +493,9 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,
  * (the bf16 filter's shape and lane mapping), on the values cast to bf16 (compared with
  * fp64); bf16 = 3: the split chain of fp32 values (hi = rn_bf16(v), lo = rn_bf16(v - hi);
  * hi.hi + hi.lo + lo.hi per 16-dim step on v_mfma_f32_32x32x16_bf16, the default filter
- * form of fp32 points).  These are the error models behind the filter's proof margin tau. */
+ * form of fp32 points); bf16 = 5: four 16x16 tiles of v_mfma_f32_16x16x32_f16 in mode 2's lane mapping, on the values
+ * cast to binary16 (the fp16 filter's shape; compared with fp64.  4 is taken: the lazy order behind
+ * nns_selftest_mfma_lazy).  These are the error models behind the filter's proof margin tau. */
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0,
                       float *out);
 /* The same tile in the order of the lazy split filter: the kt / 16 hi.hi MFMAs first — out_hh (optional) = the
@@ -472,7 +517,9 @@ int nns_filter_lazy_tile(void);
  * split-bf16 operands} (the geometry fields are the same for both fp32-point forms); with out_len >= 16 also {the split
  * operands run the lazy schedule} (0 with NNS_FILTER_SPLIT_EAGER, at depths without the lazy kernel and on the
  * short-stream record forms; the other fields do not depend on it).  NNS_ERR_UNSUPPORTED beyond
- * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 / NNS_FILTER_SPLIT_EAGER with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split). */
+ * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 / NNS_FILTER_SPLIT_EAGER with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split).
+ * bf16_points: 0 fp32, 1 bf16, 2 fp16 points.  fp16 points plan as bf16 points do, field for field, at 32 <= k <= 256;
+ * k > 256, NNS_RANGE_MFMA or NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED; the operand flags: NNS_ERR_INVALID. */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f
@@ -489,7 +536,8 @@ int nns_selftest_lane_share(int tile16, const float *in64, float *out64);
 /* Diagnostic (host only): the constants of the proof margin tau(a) = c0 + c1 * max(a + x2, 0) the
  * filter and K5 use for a query of squared norm qnorm2 against refs of maximum squared norm ymax2 at
  * tile depth kt; mode 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points
- * as split-bf16 operands.
+ * as split-bf16 operands, 4 fp16 points, exact operands on f16 tiles (mode 1's formula: binary16 products are exact in
+ * fp32).
  * out3 = {c0, c1, x2}.  Lets the tests hold the measured MFMA error against the model. */
 int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3);
 /* Diagnostic (host only): B of the lazy split filter — the bound on how far a pair's three-product score can lie below
@@ -497,8 +545,8 @@ int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3);
  * qnorm2 against refs of maximum squared norm ymax2 at tile depth kt.  out1 = B. */
 int nns_split_lazy_bound(int kt, float qnorm2, float ymax2, float *out1);
 /* The operand form of the index's MFMA filter, as its tau mode: 0 fp32 operands (NNS_FILTER_F32, or a depth without
- * the split form), 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points as split-bf16 operands;
- * -1 on the exact path.  Host only. */
+ * the split form), 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points as split-bf16 operands, 4 fp16
+ * points; -1 on the exact path.  Host only. */
 int nns_index_filter_form(nns_index *ix, int *form_out);
 
 /* ---- the exchange of the one-process-per-GPU form ----------------------------
@@ -529,7 +577,7 @@ const char *nns_last_error(void); /* thread-local detail of the last failure */
 int nns_version(void);            /* major * 1000 + minor */
 /* Explicit replacement for the reference's hidden WarmUP static (ten V9 calls before main(),
  * core.cu:1900-1933): runs one tiny search through every kernel family (exact lane-per-query and
- * lane-per-ref, every fp32 and bf16 tile depth of the MFMA filter) on `device`, so that
+ * lane-per-ref, every fp32, bf16 and fp16 tile depth of the MFMA filter) on `device`, so that
  * code-object loading, the filter's LDS opt-in and the first pool allocations are paid here and
  * not inside a timed call.  Optional: every entry point works without it. */
 int nns_warmup(int device);

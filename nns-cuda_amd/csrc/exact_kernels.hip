@@ -1170,13 +1170,22 @@ __device__ __forceinline__ void widen4(const float4 &raw, const float *, float (
 {
     o[0] = raw.x; o[1] = raw.y; o[2] = raw.z; o[3] = raw.w;
 }
-__device__ __forceinline__ void widen8(const float4 &raw, float (&o)[8])   // 8 bf16 -> 8 fp32
+__device__ __forceinline__ void widen8(const float4 &raw, const uint16_t *, float (&o)[8])   // 8 bf16 -> 8 fp32
 {
     const unsigned w[4] = {__float_as_uint(raw.x), __float_as_uint(raw.y), __float_as_uint(raw.z), __float_as_uint(raw.w)};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         o[2 * e] = __uint_as_float(w[e] << 16);
         o[2 * e + 1] = __uint_as_float(w[e] & 0xFFFF0000u);
+    }
+}
+__device__ __forceinline__ void widen8(const float4 &raw, const f16_t *, float (&o)[8])   // 8 fp16 -> 8 fp32
+{
+    const unsigned w[4] = {__float_as_uint(raw.x), __float_as_uint(raw.y), __float_as_uint(raw.z), __float_as_uint(raw.w)};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        o[2 * e] = f16_widen_lo(w[e]);
+        o[2 * e + 1] = f16_widen_hi(w[e]);
     }
 }
 
@@ -1258,7 +1267,7 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
                     const float4 raw = *reinterpret_cast<const float4 *>(mytile + lane * ROWB + ch * 16);
                     float rv[EPC];
                     if constexpr (EPC == 4) widen4(raw, nullptr, reinterpret_cast<float (&)[4]>(rv));
-                    else widen8(raw, reinterpret_cast<float (&)[8]>(rv));
+                    else widen8(raw, (const T *)nullptr, reinterpret_cast<float (&)[8]>(rv));
                     const int t0 = (c0 + ch) * EPC;
 #pragma unroll
                     for (int u = 0; u < QT; ++u) {
@@ -1731,7 +1740,9 @@ int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, 
         return launch_k1c(p, k, m, n, (const float *)q, (const float *)r, index_base, keys, ws, ws_fresh, idx_out,
                           dist_out, st);
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    if (bf16)
+    if (bf16 == DT_F16)
+        NNS_TRY(launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, nullptr, nullptr, m, index_base, keys, st));
+    else if (bf16)
         NNS_TRY(launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, nullptr, nullptr, m, index_base, keys, st));
     else
         NNS_TRY(launch_k1b(p, k, n, (const float *)q, (const float *)r, nullptr, nullptr, m, index_base, keys, st));
@@ -1750,6 +1761,7 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
     // batch both keep ~2048 workgroups busy.
     ExactPlan p{};
     k1b_plan(k, n, max_listed, 8, &p);
+    if (bf16 == DT_F16) return launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);
     return launch_k1b(p, k, n, (const float *)q, (const float *)r, qlist, qcount, 0, index_base, keys, st);
 }

@@ -72,6 +72,7 @@ __device__ __forceinline__ void static_for(F &&f)
 }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // accumulators of a wave's query blocks as NAMED members (an array of ext-vectors passed by
 // reference is not scalarised by hipcc and lands in scratch)
@@ -135,6 +136,7 @@ constexpr int kAblate = NNS_FILTER_ABLATE;
 // ---- operand traits ---------------------------------------------------------------
 // What every operator has unless it says otherwise.
 struct OpBase {
+    static constexpr bool kF16 = false;       // fp16 points (OpF16T): launched as filter_f16_kernel
     static constexpr bool kSplit = false;     // split-bf16 operands of fp32 points streamed hi, lo per k-step (OpSplitT)
     static constexpr bool kLazy = false;      // the lazy schedule of the split operands (OpLazySplitT)
     static constexpr int kSlotSteps = 32;     // fragment steps (1 KiB each) of a ring slot
@@ -246,7 +248,10 @@ using OpSplitK256 = OpSplitT<32, 1>;
 // not hide it, measured), which cost 7-9 % of this kernel.  Two v_min per MFMA gap fit the 8
 // issue cycles a 16x16x32 leaves free, so the reduction of tile rt's finished scores is spread
 // over k-step 1 of tile 1 - rt, and the threshold test + (rare) slow path follow at k-step 2.
-template <int SPB_, int NW_ = 8, int QB_ = 2>
+//
+// F16_: the same operator for fp16 points (OpF16T below) — v_mfma_f32_16x16x32_f16 has the bf16 form's rate, operand and
+// result layout, so the mnemonic inside the two asm statements is the only difference.
+template <int SPB_, int NW_ = 8, int QB_ = 2, bool F16_ = false>
 struct OpBF16T : OpBase {
     static constexpr int kSPB = SPB_;         // 16: KT = 256 (8 k-steps per 16-ref tile); 8: KT = 128 (4 k-steps); 32: KT = 512
     static constexpr bool kTile16 = true;
@@ -264,9 +269,14 @@ struct OpBF16T : OpBase {
     // the epilogue's fences (mma16_tail_fence, the sched_barriers of t16_step).
     __device__ static __forceinline__ void mma16(const float4 &a, const float4 &b, f32x4 &acc)
     {
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
-                     : "+v"(acc)
-                     : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)));
+        if constexpr (F16_)
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0"
+                         : "+v"(acc)
+                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)));
+        else
+            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0"
+                         : "+v"(acc)
+                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)));
     }
     // First MFMA of a tile: srcC = the refs' norms (three-address form).  The accumulator is an
     // in/out operand although its old value is not read: that pins every tile to ONE register
@@ -275,9 +285,14 @@ struct OpBF16T : OpBase {
     // interval's last MFMAs — a read hazard (caught by tools/check_mfma_hazards.py).
     __device__ static __forceinline__ void mma16_seed(const float4 &a, const float4 &b, f32x4 &acc, const f32x4 &c)
     {
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
-                     : "+v"(acc)
-                     : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)), "v"(c));
+        if constexpr (F16_)
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3"
+                         : "+v"(acc)
+                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)), "v"(c));
+        else
+            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
+                         : "+v"(acc)
+                         : "v"(__builtin_bit_cast(f32x4, a)), "v"(__builtin_bit_cast(f32x4, b)), "v"(c));
     }
     // VALU may read an accumulator 8 wait states after the MFMA that wrote it issued (what hipcc
     // inserts behind the builtin: s_nop 7).  To the compiler an asm MFMA's result is ready at
@@ -297,6 +312,14 @@ using OpBF16K128 = OpBF16T<8>;    // KT = 128: k <= 128 without padding to 256 (
 // waves per SIMD — a partner issues MFMAs while a wave sits in an LDS-DMA issue.  A 1 KiB fragment feeds two MFMAs per
 // wave: LDS fragment reads 32 of every 64 cycles.
 using OpBF16K512T = OpBF16T<32, 8, 1>;
+// fp16 points at KT = 256 / 128: OpBF16 / OpBF16K128 on v_mfma_f32_16x16x32_f16 (K2's order-1 image of binary16 operands,
+// tau mode 4).  Ring, epilogue, lists and plan are the bf16 operators'.
+template <int SPB_>
+struct OpF16T : OpBF16T<SPB_, 8, 2, true> {
+    static constexpr bool kF16 = true;
+};
+using OpF16 = OpF16T<16>;
+using OpF16K128 = OpF16T<8>;
 
 // The deep bf16 tiles whose blocks do not divide a ring slot (KT 384, 640, 768, 1024) run v_mfma_f32_32x32x16_bf16 with
 // ONE query block per wave.
@@ -394,7 +417,7 @@ struct FilterArgs {
     int *counts;            // [splits][m_pad/32][64 lanes]
     int total_slots, slots_per_split, m_pad, kt;
     int bf16;               // tau mode: 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands,
-                            // 3 fp32 points as split-bf16 operands (OpSplitT)
+                            // 3 fp32 points as split-bf16 operands (OpSplitT), 4 fp16 points (OpF16T)
     int share_thr;          // short streams: a query's lanes adopt the smallest of their thresholds
     int tile_rec;           // short streams: ONE record per (lane, ref tile) — (tile minimum, first ref of the lane's
                             // rows) — instead of one per score within the threshold; K5 re-ranks the lane's rows
@@ -1410,6 +1433,12 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_lazy16_kernel(const Filte
 {
     filter_main<OP>(a);
 }
+// fp16 points (OpF16T)
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_f16_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
 // (the 32x32x16 lazy kernel stays in every build, launched or not: the ISA checks of the two read one compilation)
 template __global__ void filter_lazy_kernel<OpLazySplit>(const FilterArgs a);
 template __global__ void filter_lazy16_kernel<OpLazySplit16>(const FilterArgs a);
@@ -1485,6 +1514,27 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
                 for (int r = 0; r < 16; ++r) out[1024 + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[r];
             }
         }
+    } else if (bf16 == 5) {
+        // mode 2's four 16x16 tiles and lane mapping on v_mfma_f32_16x16x32_f16, operands cast to binary16 (OpF16T)
+        const int c = lane & 15, g = lane >> 4;
+        for (int rt = 0; rt < 2; ++rt)
+            for (int qt = 0; qt < 2; ++qt) {
+                f32x4 t;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t[e] = c0[16 * rt + 4 * g + e];
+                for (int ks = 0; ks < kt / 32; ++ks) {
+                    f16x8 av, bv;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        av[e] = (_Float16)a[(16 * rt + c) * kt + 32 * ks + 8 * g + e];
+                        bv[e] = (_Float16)b[(16 * qt + c) * kt + 32 * ks + 8 * g + e];
+                    }
+                    t = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, t, 0, 0, 0);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) out[(16 * rt + 4 * g + e) * 32 + 16 * qt + c] = t[e];
+            }
+        return;
     } else {
         // bf16 == 2: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
         // the operand / result lane mapping the filter's OpBF16T and K2's order 1 image assume
@@ -1630,7 +1680,12 @@ int filter_lazy_tile()
 template <class F>
 static int with_filter_op(const FilterGeom &g, F &&f)
 {
-    if (g.bf16) {
+    if (g.f16) {
+        switch (g.kt) {
+        case 128: return f(OpF16K128{});
+        case 256: return f(OpF16{});
+        }
+    } else if (g.bf16) {
         switch (g.kt) {
         case 128: return f(OpBF16K128{});
         case 256: return f(OpBF16{});
@@ -1663,11 +1718,19 @@ static int with_filter_op(const FilterGeom &g, F &&f)
     return NNS_ERR_UNSUPPORTED;
 }
 
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager)
+int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager,
+                bool f16)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
     int kt = 0;
-    if (bf16) {
+    if (f16) {                         // fp16 points: the two 16x16x32 depths (deeper tiles: not built)
+        if (k <= 128) kt = 128;
+        else if (k <= 256) kt = 256;
+        if (!kt) {
+            set_error("MFMA filter: k = %d exceeds the deepest tile of fp16 points (256)", k);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    } else if (bf16) {
         if (k <= 128) kt = 128;        // OpBF16K128: 4 k-steps per 16-ref tile, 4 blocks per slot
         else if (k <= 256) kt = 256;
         else if (k <= 384) kt = 384;   // OpBF16K384: four 24-step blocks over three ring slots
@@ -1687,6 +1750,7 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
         return NNS_ERR_UNSUPPORTED;
     }
     g->bf16 = bf16 ? 1 : 0;
+    g->f16 = f16 ? 1 : 0;
     g->mixed = mixed ? 1 : 0;
     // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
     g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;
@@ -1759,7 +1823,8 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (OP::kLazy && OP::kTile16) return filter_lazy16_kernel<OP>;
+        if constexpr (OP::kF16) return filter_f16_kernel<OP>;
+        else if constexpr (OP::kLazy && OP::kTile16) return filter_lazy16_kernel<OP>;
         else if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
         else if constexpr (OP::kSplit) return filter_split_kernel<OP>;
         else return filter_kernel<OP>;
@@ -1796,7 +1861,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
     a.slots_per_split = g.slots_per_split;
     a.m_pad = g.m_pad;
     a.kt = g.kt;
-    a.bf16 = g.mixed ? 2 : g.split ? 3 : g.bf16;
+    a.bf16 = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
     a.share_thr = g.share_thr;   // (filter_plan)
     a.tile_rec = g.tile_rec;
 #ifdef NNS_DIAG

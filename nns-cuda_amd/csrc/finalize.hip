@@ -83,6 +83,9 @@ __device__ __forceinline__ float4 load_f4(const uint16_t *p)
     return o;
 }
 
+__device__ __forceinline__ float load_f(const f16_t *p, size_t i) { return pt_ld1(p + i); }   // fp16 -> fp32: exact
+__device__ __forceinline__ float4 load_f4(const f16_t *p) { return pt_ld4(p); }
+
 // V0's exact distance (core.cu:38-43), t ascending; 4 dims per load when aligned
 template <typename T>
 __device__ __forceinline__ float v0_distance(const T *qi, const T *rj, int k, bool vec)
@@ -121,7 +124,8 @@ __global__ __launch_bounds__(256) void finalize_kernel(
     const int i = (unit << ush) + (lane & qmask);               // this lane's query
     const bool live = i < m;
 
-    bool fallback = scal->q_maxabs_bits >= kHugeBits || scal->r_maxabs_bits >= kHugeBits;
+    // (mode 4, fp16 points: a ref beyond kF16RefMax has no finite scaled operand — the host latch's twin)
+    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, bf16 == 4);
     float a = __builtin_inff();
     int over = 0;
     if (!fallback && live) {
@@ -208,7 +212,8 @@ __global__ __launch_bounds__(256) void finalize_wave_kernel(
     if (i >= m) return;
     const int nlists = lpq * splits;
     const int ush = lpq == 4 ? 4 : 5, qmask = (1 << ush) - 1, lsh = lpq == 4 ? 2 : 1;
-    bool fallback = scal->q_maxabs_bits >= kHugeBits || scal->r_maxabs_bits >= kHugeBits;
+    // (mode 4, fp16 points: a ref beyond kF16RefMax has no finite scaled operand — the host latch's twin)
+    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, bf16 == 4);
     float a = __builtin_inff();
     int over = 0;
     for (int l = lane; l < nlists; l += 64) {
@@ -330,10 +335,14 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
                     const CandEntry *lists, const int *counts, const float *qnorm, DevScalars *scal,
                     int64_t index_base, nns_key *keys, int *amb_list, int *multi_list, hipStream_t st)
 {
-    const int mode = g.mixed ? 2 : g.split ? 3 : g.bf16;   // tau mode (nns_internal.h)
-    const bool data_bf16 = g.bf16 && !g.mixed;    // element type of q / r
+    const int mode = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // tau mode (nns_internal.h)
+    const bool data_bf16 = g.bf16 && !g.mixed && !g.f16;    // element type of q / r
     if (g.splits >= 4) {   // few queries, many lists per query: one wave per query
-        if (data_bf16)
+        if (g.f16)
+            hipLaunchKernelGGL(finalize_wave_kernel<f16_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
+                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists,
+                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
+        else if (data_bf16)
             hipLaunchKernelGGL(finalize_wave_kernel<uint16_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
                                g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const uint16_t *)q, (const uint16_t *)r, lists,
                                counts, qnorm, scal, index_base, keys, amb_list, multi_list);
@@ -348,7 +357,11 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
         set_error("internal: tile records need the one-wave-per-query finalize");
         return NNS_ERR_INVALID;
     }
-    if (data_bf16)
+    if (g.f16)
+        hipLaunchKernelGGL(finalize_kernel<f16_t>, dim3(divup(g.m_pad / (64 / g.lpq), 4)), dim3(256), 0, st, g.kt, mode, g.lpq, g.m_pad,
+                           g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists, counts, qnorm,
+                           scal, index_base, keys, amb_list, multi_list);
+    else if (data_bf16)
         hipLaunchKernelGGL(finalize_kernel<uint16_t>, dim3(divup(g.m_pad / (64 / g.lpq), 4)), dim3(256), 0, st, g.kt, mode, g.lpq, g.m_pad,
                            g.splits, k, m, n, (const uint16_t *)q, (const uint16_t *)r, lists, counts, qnorm,
                            scal, index_base, keys, amb_list, multi_list);

@@ -75,10 +75,10 @@ struct nns_index {
     int64_t base = 0;
     unsigned flags = 0;
     int path = NNS_PATH_EXACT;
-    const void *r_dev = nullptr;   // fp32 [n][k] or bf16 bits [n][k]
+    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k]
     const void *r_soa = nullptr;   // NNS_REFS_SOA: the caller's [k][n] array; r_dev is then r_own
     void *r_own = nullptr;         // owned point-major copy of r_soa
-    int bf16 = 0;
+    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16
     bool profile = false;
     bool refs_bad = false;
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
@@ -213,7 +213,7 @@ int order_after_default_stream(hipStream_t st)
 static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
 {
     if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) && bf16) {
-        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16 points use the bf16 filter)");
+        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16 and fp16 points use their own filter)");
         return NNS_ERR_INVALID;
     }
     if ((flags & NNS_FILTER_BF16) && (flags & NNS_FILTER_F32)) {
@@ -231,10 +231,11 @@ static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *spl
 }
 
 // what NNS_RANGE_MFMA / NNS_TOPK_MFMA take: fp32 points whose filter form is the split one, at the split tiles' depths;
-// bf16 points at the depths of the 16x16x32 tiles (below 32 dimensions AUTO does not filter bf16 points either)
+// bf16 points at the depths of the 16x16x32 tiles (below 32 dimensions AUTO does not filter bf16 points either); fp16
+// points: no flag pass is built
 static bool flag_pass_supported(int k, int bf16, unsigned flags)
 {
-    if (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16)) return false;
+    if (bf16 == DT_F16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16))) return false;
     return bf16 ? (k >= 32 && k <= 256) : (k >= 8 && k <= 256);
 }
 
@@ -245,7 +246,7 @@ static int prep_refs(nns_index *ix, hipStream_t st)
     if (ix->bf16) {
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, ix->n, g.n_pad, (const uint16_t *)ix->r_dev, -2.0f, INFINITY,
                                        ix->rimg, ix->rnorm, &ix->scal->ymax2_bits,
-                                       &ix->scal->r_maxabs_bits, st));
+                                       &ix->scal->r_maxabs_bits, st, ix->bf16 == DT_F16));
         return NNS_OK;
     }
     NNS_TRY(launch_prep_mean(ix->k, g.kt, ix->n, (const float *)ix->r_dev, ix->mean_ws, ix->mean,
@@ -257,12 +258,12 @@ static int prep_refs(nns_index *ix, hipStream_t st)
 }
 
 // K2's scalars read back on `st` (one host wait), and the latch they decide: refs that void the error bound (NaN /
-// INF / |v| >= 1e17) go straight to the exact kernels
+// INF / |v| >= 1e17; fp16 points: |v| > 32752, whose scaled operand -2 v is not finite) go straight to the exact kernels
 static int read_scalars(nns_index *ix, hipStream_t st, DevScalars *h)
 {
     NNS_HIP(hipMemcpyAsync(h, ix->scal, sizeof(*h), hipMemcpyDeviceToHost, st));
     NNS_HIP(hipStreamSynchronize(st));
-    ix->refs_bad = h->r_maxabs_bits >= kHugeBits;
+    ix->refs_bad = refs_void(h->r_maxabs_bits, ix->bf16 == DT_F16);
     ix->refs_unknown = false;
     return NNS_OK;
 }
@@ -337,6 +338,16 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         return NNS_ERR_INVALID;
     }
     *out = nullptr;
+    if (bf16 == DT_F16) {   // (what an fp16 index does not take, answered before the device is looked up)
+        if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
+            set_error("nns_index_create_f16: the operand flags apply to fp32 points (flags 0x%x)", flags);
+            return NNS_ERR_INVALID;
+        }
+        if (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA)) {
+            set_error("nns_index_create_f16: the range-MFMA and top-K MFMA flags are not built for fp16 points (flags 0x%x)", flags);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    }
     if (flags & NNS_RANGE_MFMA) {
         if (!flag_pass_supported(k, bf16, flags)) {
             set_error("nns_index_create: the range-MFMA flag takes fp32 points on split-bf16 operands, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d, flags 0x%x)",
@@ -374,7 +385,8 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             return frc;
         }
     }
-    const int kmax = (bf16 || ix->mixed) ? kMaxFilterK : 256;   // deepest tile of the MFMA filter
+    // deepest tile of the MFMA filter (fp16 points: the two 16x16x32 depths)
+    const int kmax = bf16 == DT_F16 ? 256 : (bf16 || ix->mixed) ? kMaxFilterK : 256;
     int path = flags & NNS_PATH_MASK;
     // crossover: from k = 8 the MFMA filter (KT = 16 / 32 tile) beats 3k VALU ops per pair; bf16 tiles
     // are at least 128 deep, so they only pay from k = 32
@@ -418,7 +430,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         }
         if (path == NNS_PATH_MFMA || ix->flag_image()) {   // (the range and top-K flags build the image whatever the 1-NN path)
             if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0)) !=
+                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16 == DT_F16)) !=
                 NNS_OK)
                 break;
             const FilterGeom &g = ix->geom;
@@ -467,6 +479,13 @@ int nns_index_create_bf16(nns_index **out, int device, int k, int n, const uint1
     return index_create_impl(out, device, k, n, r_dev, 1, index_base, flags & ~kCreateNoSync, stream);
 }
 
+int nns_index_create_f16(nns_index **out, int device, int k, int n, const uint16_t *r_dev,
+                         int64_t index_base, unsigned flags, void *stream)
+{
+    DeviceScope keep_device;
+    return index_create_impl(out, device, k, n, r_dev, DT_F16, index_base, flags & ~kCreateNoSync, stream);
+}
+
 int nns_index_refresh(nns_index *ix, void *stream)
 {
     if (!ix) return NNS_ERR_INVALID;
@@ -499,7 +518,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
     FilterGeom g = ix->geom;
     FilterGeom gq{};
     NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0));
+                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, ix->bf16 == DT_F16));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
     (void)g;
     if (gq.m_pad > ix->m_cap) {
@@ -587,7 +606,8 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
                              int *idx_dev = nullptr, float *dist_dev = nullptr)
 {
     if (ix && ix->bf16 != bf16) {
-        set_error("nns_index_search: query dtype does not match the index (%s index)", ix->bf16 ? "bf16" : "fp32");
+        set_error("nns_index_search: query dtype does not match the index (%s index)",
+                  ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
         return NNS_ERR_INVALID;
     }
     if (!ix || !q_dev || !keys_dev || m <= 0) {
@@ -635,7 +655,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
     NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
     if (bf16)
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg, ix->qnorm,
-                                       nullptr, &ix->scal->q_maxabs_bits, st));
+                                       nullptr, &ix->scal->q_maxabs_bits, st, bf16 == DT_F16));
     else
         NNS_TRY(launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f,
                                   (float *)ix->qimg, ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st,
@@ -674,6 +694,12 @@ int nns_index_search_bf16(nns_index *ix, int m, const uint16_t *q_dev, nns_key *
 {
     DeviceScope keep_device;
     return index_search_impl(ix, m, q_dev, 1, keys_dev, stream);
+}
+
+int nns_index_search_f16(nns_index *ix, int m, const uint16_t *q_dev, nns_key *keys_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_search_impl(ix, m, q_dev, DT_F16, keys_dev, stream);
 }
 
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev, int *idx_dev,
@@ -813,7 +839,7 @@ int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, f
 
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16 refs are widened as they are read)
+    (void)bf16_points;   // (same geometry: bf16 and fp16 (2) refs are widened as they are read)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     NNS_TRY(topk_check_kn("nns_plan_topk", kn));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
@@ -1062,7 +1088,7 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16 refs are widened as they are read)
+    (void)bf16_points;   // (same geometry: bf16 and fp16 (2) refs are widened as they are read)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
     RangePlan p{};
@@ -1251,13 +1277,13 @@ int nns_index_filter_form(nns_index *ix, int *form_out)
 {
     if (!ix || !form_out) return NNS_ERR_INVALID;
     const FilterGeom &g = ix->geom;
-    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // = the tau mode
+    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // = the tau mode
     return NNS_OK;
 }
 
 int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3)
 {
-    if (kt <= 0 || mode < 0 || mode > 3 || !out3) return NNS_ERR_INVALID;
+    if (kt <= 0 || mode < 0 || mode > 4 || !out3) return NNS_ERR_INVALID;
     const TauConsts t = tau_consts(kt, qnorm2, ymax2, mode);
     out3[0] = t.c0;
     out3[1] = t.c1;
@@ -1332,7 +1358,8 @@ int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *
 
 static int selftest_mfma_impl(int kt, int bf16, const float *a, const float *b, const float *c0, float *out, float *out_hh)
 {
-    if (kt <= 0 || (kt & 15) || (bf16 == 2 && (kt & 31)) || bf16 < 0 || bf16 > 4 || !a || !b || !c0 || !out)
+    // (mode 4 is the lazy order behind nns_selftest_mfma_lazy; 5: the f16 tiles)
+    if (kt <= 0 || (kt & 15) || ((bf16 == 2 || bf16 == 5) && (kt & 31)) || bf16 < 0 || bf16 > 5 || !a || !b || !c0 || !out)
         return NNS_ERR_INVALID;
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(0));
@@ -1481,9 +1508,13 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
     if (!out || out_len < 12 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     bool mixed = false, split = false;
     NNS_TRY(operand_form(k, bf16_points != 0, flags, &mixed, &split));
+    if (bf16_points == DT_F16 && (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA))) {
+        set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags are not built for fp16 points (flags 0x%x)", flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
     FilterGeom g{};
     NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split,
-                        (flags & NNS_FILTER_SPLIT_EAGER) != 0));
+                        (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16_points == DT_F16));
     const int v[16] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
                        g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split, g.lazy};
     memcpy(out, v, (out_len >= 16 ? 16 : out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
@@ -1596,7 +1627,7 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
     if (flags & (NNS_REFS_SOA | NNS_PROFILE)) return false;
     if (rbytes < kChunkMinBytes || n < 4096 || m < kTinyM) return false;
     const unsigned path = flags & NNS_PATH_MASK;
-    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > kMaxFilterK;
+    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > (bf16 == DT_F16 ? 256 : kMaxFilterK);
     double est_s;
     if (exact) {
         est_s = 3.0 * k * (double)m * (double)n / 45e12;
@@ -1812,7 +1843,7 @@ static int check_exact_only_flags(const char *where, const char *what, unsigned 
 static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
                                  int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
-    const char *where = bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
+    const char *where = bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, idx_out));
     NNS_TRY(topk_check_kn(where, kn));
     if ((int64_t)m * kn > 0x7FFFFFFFll * 4) {
@@ -1821,7 +1852,7 @@ static int search_topk_host_impl(int k, int m, int n, const void *s_points, cons
     }
     NNS_TRY(check_exact_only_flags(where, "top-K", flags & ~(unsigned)NNS_TOPK_MFMA));
     if ((flags & NNS_TOPK_MFMA) && !flag_pass_supported(k, bf16, flags)) {
-        set_error("%s: the top-K MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d)", where, k);
+        set_error("%s: the top-K MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256; not fp16 points (k=%d)", where, k);
         return NNS_ERR_UNSUPPORTED;
     }
     TopkPlan p{};
@@ -1891,7 +1922,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
                                   float radius2, int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags,
                                   int device)
 {
-    const char *where = bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
+    const char *where = bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
     if (idx_out) *idx_out = nullptr;
     if (dist_out) *dist_out = nullptr;
     if (!idx_out) {
@@ -1903,7 +1934,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     NNS_TRY(range_check_radius(where, radius2));
     NNS_TRY(check_exact_only_flags(where, "range search", flags & ~(unsigned)NNS_RANGE_MFMA));
     if ((flags & NNS_RANGE_MFMA) && !flag_pass_supported(k, bf16, flags)) {
-        set_error("%s: the range-MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256 (k=%d)", where, k);
+        set_error("%s: the range-MFMA flag takes fp32 points, 8 <= k <= 256, or bf16 points, 32 <= k <= 256; not fp16 points (k=%d)", where, k);
         return NNS_ERR_UNSUPPORTED;
     }
     RangePlan p{};
@@ -1936,6 +1967,24 @@ int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const u
     return search_range_host_impl(k, m, n, s_points, r_points, 1, radius2, lims_out, idx_out, dist_out, flags, device);
 }
 
+int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
+                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    return search_range_host_impl(k, m, n, s_points, r_points, DT_F16, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_f16_ex(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int *idx_out,
+                      float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_host_impl(k, m, n, s_points, r_points, DT_F16, idx_out, dist_out, num_shards, flags, device);
+}
+
+int nns_search_f16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
+                        int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_topk_host_impl(k, m, n, s_points, r_points, DT_F16, kn, idx_out, dist_out, num_shards, flags, device);
+}
+
 int nns_search_f32_ex(int k, int m, int n, const float *s_points, const float *r_points, int *idx_out,
                       float *dist_out, int num_shards, unsigned flags, int device)
 {
@@ -1966,14 +2015,16 @@ int nns_warmup(int device)
     NNS_TRY(ensure_device_ok(device));
     // (k, m, n, bf16, path): K1a (3-D and 16-D), K1b, the fp32 tile depths 16 / 32 / 64 / 128 / 256 (forced onto the
     // filter: AUTO keeps a 64 x 512 x 16 problem on the exact kernel), the bf16-operand tiles for fp32 points (512 /
-    // 384 / 512 / 640 / 768 / 1024: AUTO), the bf16 tiles 128 / 256 / 384 / 512 / 640 / 768 / 1024
+    // 384 / 512 / 640 / 768 / 1024: AUTO), the bf16 tiles 128 / 256 / 384 / 512 / 640 / 768 / 1024, the fp16 tiles 128 / 256
+    // (dtype 2)
     static const int shapes[][5] = {{3, 64, 512, 0, NNS_PATH_AUTO},    {16, 64, 512, 0, NNS_PATH_AUTO},  {16, 1, 512, 0, NNS_PATH_AUTO},
                                     {16, 64, 512, 0, NNS_PATH_MFMA},   {24, 64, 512, 0, NNS_PATH_MFMA},  {40, 64, 512, 0, NNS_PATH_MFMA},
                                     {100, 64, 512, 0, NNS_PATH_MFMA},  {200, 64, 512, 0, NNS_PATH_MFMA}, {300, 64, 512, 0, NNS_PATH_AUTO},
                                     {400, 64, 512, 0, NNS_PATH_AUTO},  {400, 64, 512, 1, NNS_PATH_MFMA},
                                     {600, 64, 512, 0, NNS_PATH_AUTO},  {700, 64, 512, 0, NNS_PATH_AUTO}, {800, 64, 512, 0, NNS_PATH_AUTO},
                                     {64, 64, 512, 1, NNS_PATH_MFMA},   {200, 64, 512, 1, NNS_PATH_MFMA}, {300, 64, 512, 1, NNS_PATH_MFMA},
-                                    {600, 64, 512, 1, NNS_PATH_MFMA},  {700, 64, 512, 1, NNS_PATH_MFMA}, {800, 64, 512, 1, NNS_PATH_MFMA}};
+                                    {600, 64, 512, 1, NNS_PATH_MFMA},  {700, 64, 512, 1, NNS_PATH_MFMA}, {800, 64, 512, 1, NNS_PATH_MFMA},
+                                    {64, 64, 512, 2, NNS_PATH_MFMA},   {200, 64, 512, 2, NNS_PATH_MFMA}};
     const int kmax = 800, mmax = 64, nmax = 512;
     float *q = (float *)malloc(sizeof(float) * kmax * mmax), *r = (float *)malloc(sizeof(float) * kmax * nmax);
     int *idx = (int *)malloc(sizeof(int) * mmax);
@@ -1989,21 +2040,21 @@ int nns_warmup(int device)
     int rc = NNS_OK;
     for (const auto &sh : shapes) {
         if (sh[3]) {
-            // the same numbers as bf16 bit patterns (truncated: this is a warm-up, not a result)
+            // the same numbers as bf16 bit patterns (truncated: this is a warm-up, not a result); dtype 2: as fp16 bit
+            // patterns, truncated likewise (the values lie in [0, 1): below 2^-14 they become 0)
+            const auto bits16 = [&](float v) {
+                unsigned u;
+                memcpy(&u, &v, 4);
+                if (sh[3] != DT_F16) return (uint16_t)(u >> 16);
+                const int e = (int)(u >> 23) - 127 + 15;
+                return (uint16_t)(e <= 0 ? 0 : (e << 10) | ((u >> 13) & 0x3FF));
+            };
             uint16_t *qb = (uint16_t *)malloc(sizeof(uint16_t) * sh[0] * sh[1]);
             uint16_t *rb = (uint16_t *)malloc(sizeof(uint16_t) * sh[0] * sh[2]);
             if (qb && rb) {
-                for (int i = 0; i < sh[0] * sh[1]; ++i) {
-                    unsigned u;
-                    memcpy(&u, &q[i], 4);
-                    qb[i] = (uint16_t)(u >> 16);
-                }
-                for (int i = 0; i < sh[0] * sh[2]; ++i) {
-                    unsigned u;
-                    memcpy(&u, &r[i], 4);
-                    rb[i] = (uint16_t)(u >> 16);
-                }
-                rc = search_host_impl(sh[0], sh[1], sh[2], qb, rb, 1, idx, nullptr, 1, (unsigned)sh[4], device);
+                for (int i = 0; i < sh[0] * sh[1]; ++i) qb[i] = bits16(q[i]);
+                for (int i = 0; i < sh[0] * sh[2]; ++i) rb[i] = bits16(r[i]);
+                rc = search_host_impl(sh[0], sh[1], sh[2], qb, rb, sh[3], idx, nullptr, 1, (unsigned)sh[4], device);
             } else {
                 rc = NNS_ERR_NOMEM;
             }

@@ -67,6 +67,7 @@ struct DeviceScope {
 int order_after_default_stream(hipStream_t st);
 void stager_release();         // free the small whole calls' pinned scratch (nns_api.hip)
 // the overlapped upload of a contiguous host ref range (nns_api.hip), shared with nns_search_*_multi's shards
+// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16 or DT_F16)
 bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes);
 int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
                             int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp);
@@ -197,8 +198,24 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
     return __fadd_rn(sum, __fmul_rn(diff, diff));
 }
 
-// point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16)
-// aligned row; bf16 bits are widened exactly
+// ---- point element types ------------------------------------------------------------------------------------------
+// The dtype of an index and of its queries, the `int bf16` argument of the launchers: fp32, bf16 bit patterns, IEEE
+// binary16 (fp16) bit patterns.  Element size: dtype ? 2 : 4.
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
+// uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
+struct f16_t {
+    uint16_t bits;
+};
+static_assert(sizeof(f16_t) == 2 && alignof(f16_t) == 2, "f16_t is the raw 16-bit pattern");
+// binary16 -> fp32 (v_cvt_f32_f16: exact, subnormals, INF and NaN included) and the two halves of a 32-bit word
+__device__ __forceinline__ float f16_widen(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
+__device__ __forceinline__ float f16_widen_lo(unsigned w) { return f16_widen((unsigned short)(w & 0xFFFFu)); }
+__device__ __forceinline__ float f16_widen_hi(unsigned w) { return f16_widen((unsigned short)(w >> 16)); }
+// fp32 -> binary16 bits, round to nearest even (v_cvt_f16_f32; overflow gives INF, NaN stays NaN)
+__device__ __forceinline__ unsigned f16_narrow(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
+
+// point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16, fp16)
+// aligned row; bf16 and fp16 bits are widened exactly
 __device__ __forceinline__ float pt_ld1(const float *p) { return *p; }
 __device__ __forceinline__ float pt_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
 __device__ __forceinline__ float4 pt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -210,6 +227,17 @@ __device__ __forceinline__ float4 pt_ld4(const uint16_t *p)
     o.y = __uint_as_float(v.x & 0xFFFF0000u);
     o.z = __uint_as_float(v.y << 16);
     o.w = __uint_as_float(v.y & 0xFFFF0000u);
+    return o;
+}
+__device__ __forceinline__ float pt_ld1(const f16_t *p) { return f16_widen(p->bits); }
+__device__ __forceinline__ float4 pt_ld4(const f16_t *p)
+{
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);   // 4 fp16, widened exactly
+    float4 o;
+    o.x = f16_widen_lo(v.x);
+    o.y = f16_widen_hi(v.x);
+    o.z = f16_widen_lo(v.y);
+    o.w = f16_widen_hi(v.y);
     return o;
 }
 
@@ -406,6 +434,7 @@ __host__ __device__ constexpr int lazy16_gather(int lane, int t, int ks, int par
 
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
+    int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; tau mode 4)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
     int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
@@ -453,7 +482,10 @@ struct TauConsts {
 };
 
 // mode: 0 fp32 operands, 1 bf16 points (operands exact), 2 fp32 points ROUNDED to bf16 operands, 3 fp32 points as
-// SPLIT bf16 operands (hi + lo, three products: OpSplitT)
+// SPLIT bf16 operands (hi + lo, three products: OpSplitT), 4 fp16 points (operands exact) on v_mfma_f32_16x16x32_f16:
+// two binary16 values multiply exactly in fp32 (11 + 11 significand bits), so mode 1's formula — exact products, the
+// order-free accumulation model at kMode4AddUlps u per add, no centring — holds as it stands ("fp16 points")
+constexpr double kMode4AddUlps = 2.0;
 __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax2, int mode)
 {
     const bool bf16 = mode != 0;
@@ -485,7 +517,8 @@ __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax
     } else {
         // bf16 products are exact in fp32; the accumulation order/rounding inside
         // v_mfma_f32_32x32x16_bf16 is not documented: allow 2u per add, kt + kt/16 adds
-        const double gf = 2.0 * (kt + kt / 16 + 2) * u / (1.0 - 2.0 * (kt + kt / 16 + 2) * u);
+        const double pa = mode == 4 ? kMode4AddUlps : 2.0;   // allowance per add, in u
+        const double gf = pa * (kt + kt / 16 + 2) * u / (1.0 - pa * (kt + kt / 16 + 2) * u);
         e3 = gf * (Y2 + 2.0 * X * Y) + 2.0 * u * Y2;
         e2 = 0.0;                            // no centring on the bf16 path
         if (mode == 2) {
@@ -609,6 +642,17 @@ __host__ __device__ inline float k1f_threshold(float a, float xn, float y2)
 constexpr float kHuge = 1e17f;
 constexpr unsigned kHugeBits = 0x5BB1A2BCu;
 static_assert(__builtin_bit_cast(unsigned, kHuge) == kHugeBits, "kHugeBits is kHuge's bit pattern");
+// fp16 points: K2 narrows the refs' scaled value -2 v back to binary16, finite only for |v| <= 32752 (the largest
+// binary16 value whose double does not round to INF: 65504 / 2).  A larger ref value (32768 .. 65504, INF, NaN) voids the
+// filter as kHuge does for the other types.  Queries are not scaled: only their NaN / INF matter.
+constexpr float kF16RefMax = 32752.0f;
+constexpr unsigned kF16RefMaxBits = 0x46FFE000u;
+static_assert(__builtin_bit_cast(unsigned, kF16RefMax) == kF16RefMaxBits, "kF16RefMaxBits is kF16RefMax's bit pattern");
+// K2's max-|ref value| word voids the filter (host latch and K5's device-side twin agree on this)
+__host__ __device__ inline bool refs_void(unsigned r_maxabs_bits, bool f16)
+{
+    return f16 ? r_maxabs_bits > kF16RefMaxBits : r_maxabs_bits >= kHugeBits;
+}
 
 // device-side scalars shared between kernels of one index
 struct DevScalars {
@@ -671,14 +715,17 @@ int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts,
 // core.cu:293-306); esz = 4 (fp32) or 2 (bf16 bits)
 int launch_soa_to_aos(int k, int n, const void *src, void *dst, int esz, hipStream_t st);
 // order: 0 = 32x32x16 operands, 1 = 16x16x32 operands (fragment 8 * tile + k-step)
+// f16: pts are fp16 bit patterns -> the same image of binary16 operands (order 1, kt = 128 / 256), value * scale narrowed
+// with a real conversion; norms and the max-|v| word from the widened values
 int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale,
                            float pad_norm, void *img, float *norms, unsigned *max_norm_bits,
-                           unsigned *maxabs_bits, hipStream_t st);
+                           unsigned *maxabs_bits, hipStream_t st, bool f16 = false);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
 // split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth
+// f16 (with bf16 = true): fp16 points — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
-                bool split = false, bool split_eager = false);
+                bool split = false, bool split_eager = false, bool f16 = false);
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,

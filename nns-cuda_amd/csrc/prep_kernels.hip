@@ -575,7 +575,13 @@ int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, c
 // one k-step ks of 32 dims; lane l holds dims 32 ks + 8 (l >> 4) .. + 7 of point 16 t + (l & 15);
 // the block stores fragment (KT / 32) t + ks (the filter walks a ref tile's k-steps in a row; a wave
 // keeps all k-steps of its four query tiles in registers).  order 0: the 32x32x16 layout above.
-template <int KT>
+//
+// F16 (fp16 points, order 1, KT = 128 / 256: v_mfma_f32_16x16x32_f16 operands): the same permutation of 16-bit words.
+// Values are widened with v_cvt_f32_f16 for the fp64 norms and for the max-|v| word (kept as fp32 bits, so the host's and
+// K5's comparisons read it like the other types'), and the scaled value is narrowed with a real conversion: -2 v is
+// exact in binary16 for |v| <= 32752 (subnormals included: doubling is exact); beyond, the image holds INF and the
+// max-|v| word voids the filter (kF16RefMax, nns_internal.h).
+template <int KT, bool F16 = false>
 __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int npts, const uint16_t *__restrict__ pts,
                                                          float scale, float pad_norm,
                                                          uint16_t *__restrict__ img, float *__restrict__ norms,
@@ -597,7 +603,14 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
             const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const unsigned lo = (w[u] << 16) & 0x7FFFFFFFu, hi = w[u] & 0x7FFF0000u;
+                unsigned lo, hi;
+                if constexpr (F16) {
+                    lo = __float_as_uint(f16_widen_lo(w[u] & 0x7FFF7FFFu));
+                    hi = __float_as_uint(f16_widen_hi(w[u] & 0x7FFF7FFFu));
+                } else {
+                    lo = (w[u] << 16) & 0x7FFFFFFFu;
+                    hi = w[u] & 0x7FFF0000u;
+                }
                 mx = max(mx, max(lo, hi));
             }
             *reinterpret_cast<uint4 *>(&tile[i * LD + 8 * t8]) = v;
@@ -608,7 +621,7 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
             uint16_t v = 0;
             if (t < k && p0 + i < npts) {
                 v = pts[(size_t)(p0 + i) * k + t];
-                const unsigned b = ((unsigned)v << 16) & 0x7FFFFFFFu;
+                const unsigned b = F16 ? __float_as_uint(f16_widen(v & 0x7FFFu)) : ((unsigned)v << 16) & 0x7FFFFFFFu;
                 mx = b > mx ? b : mx;
             }
             tile[i * LD + t] = v;
@@ -619,7 +632,7 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
         const int i = tid >> 3, part = tid & 7;
         double acc = 0.0;
         for (int t = part; t < KT; t += 8) {
-            const double v = (double)__uint_as_float((unsigned)tile[i * LD + t] << 16);
+            const double v = (double)(F16 ? f16_widen(tile[i * LD + t]) : __uint_as_float((unsigned)tile[i * LD + t] << 16));
             acc += v * v;
         }
         nrm[i][part] = acc;
@@ -660,6 +673,11 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
         unsigned w[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
+            if constexpr (F16) {
+                // scale in fp32, ONE conversion back to binary16: exact for scale in {1, -2} while |v| <= 32752
+                w[e] = f16_narrow(f16_widen_lo(in[e]) * scale) | (f16_narrow(f16_widen_hi(in[e]) * scale) << 16);
+                continue;
+            }
             // scale in fp32 and narrow back: exact for scale in {1, -2} (no overflow below 1e17)
             const float lo = __uint_as_float(in[e] << 16) * scale;
             const float hi = __uint_as_float(in[e] & 0xFFFF0000u) * scale;
@@ -677,8 +695,22 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
 
 int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale, float pad_norm,
                            void *img, float *norms, unsigned *max_norm_bits, unsigned *maxabs_bits,
-                           hipStream_t st)
+                           hipStream_t st, bool f16)
 {
+    if (f16) {   // fp16 points: the order-1 image at the depths of the 16x16x32 tiles
+        if (order == 1 && kt == 256)
+            hipLaunchKernelGGL((image_bf16_kernel<256, true>), dim3(npts_pad / 32), dim3(256), 0, st, order, k, npts, pts,
+                               scale, pad_norm, (uint16_t *)img, norms, max_norm_bits, maxabs_bits);
+        else if (order == 1 && kt == 128)
+            hipLaunchKernelGGL((image_bf16_kernel<128, true>), dim3(npts_pad / 32), dim3(256), 0, st, order, k, npts, pts,
+                               scale, pad_norm, (uint16_t *)img, norms, max_norm_bits, maxabs_bits);
+        else {
+            set_error("prep: unsupported fp16 tile K %d (order %d)", kt, order);
+            return NNS_ERR_UNSUPPORTED;
+        }
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
+    }
     if (kt == 256)
         hipLaunchKernelGGL(image_bf16_kernel<256>, dim3(npts_pad / 32), dim3(256), 0, st, order, k, npts, pts, scale,
                            pad_norm, (uint16_t *)img, norms, max_norm_bits, maxabs_bits);

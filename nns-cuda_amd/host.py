@@ -60,11 +60,14 @@ ABI_SYMBOLS = (
     "nns_index_topk_info", "nns_plan_topk_mfma",
     "nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
     "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
+    "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk", "nns_search_f16_range",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
 OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
-                    "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16")
+                    "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
+                    "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk",
+                    "nns_search_f16_range")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -164,7 +167,12 @@ def _load() -> ctypes.CDLL:
     optional = {"nns_filter_lazy_tile": [], "nns_selftest_mfma_lazy16": [c_vp, c_vp, c_vp, c_vp, c_vp],
                 "nns_plan_range_mfma_bf16": lib.nns_plan_range_mfma.argtypes,
                 "nns_plan_topk_mfma_bf16": lib.nns_plan_topk_mfma.argtypes,
-                "nns_range_threshold_bf16": lib.nns_range_threshold.argtypes}
+                "nns_range_threshold_bf16": lib.nns_range_threshold.argtypes,
+                "nns_index_create_f16": lib.nns_index_create.argtypes,
+                "nns_index_search_f16": lib.nns_index_search.argtypes,
+                "nns_search_f16_ex": lib.nns_search_f32_ex.argtypes,
+                "nns_search_f16_topk": lib.nns_search_f32_topk.argtypes,
+                "nns_search_f16_range": lib.nns_search_f32_range.argtypes}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -192,7 +200,7 @@ def _check(status: int, where: str) -> None:
 
 def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: int = 0) -> np.ndarray:
     """out[i][j] of one 32x32 MFMA tile (diagnostic, see include/nns.h).  bf16: 0 fp32, 1 bf16 32x32x16, 2 bf16
-    16x16x32, 3 the split chain of fp32 values."""
+    16x16x32, 3 the split chain of fp32 values, 5 f16 16x16x32 (the values cast to binary16)."""
     a = np.ascontiguousarray(a, np.float32)
     b = np.ascontiguousarray(b, np.float32)
     c0 = np.ascontiguousarray(c0, np.float32)
@@ -243,7 +251,8 @@ def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
 
 
 def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0, schedule: bool = False) -> dict:
-    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  "split": 1 when fp32 points
+    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  bf16: False / True, or 2 for fp16
+    points (here and in plan_topk / plan_range).  "split": 1 when fp32 points
     take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0).  schedule=True asks for the
     16th field too, "lazy": 1 when the split operands run the lazy schedule (0 with NNS_FILTER_SPLIT_EAGER)."""
     nf = 16 if schedule else 15
@@ -331,7 +340,7 @@ def selftest_lane_share(values, tile16: bool) -> np.ndarray:
 
 
 def tau_consts(kt: int, qnorm2: float, ymax2: float, mode: int):
-    """(c0, c1, x2) of the proof margin tau(a) = c0 + c1 * max(a + x2, 0) (nns_tau_consts)."""
+    """(c0, c1, x2) of the proof margin tau(a) = c0 + c1 * max(a + x2, 0) (nns_tau_consts; mode 0 .. 4, 4: fp16 points)."""
     out = np.empty(3, np.float32)
     _check(lib.nns_tau_consts(kt, qnorm2, ymax2, mode, out.ctypes.data), "nns_tau_consts")
     return float(out[0]), float(out[1]), float(out[2])
@@ -449,6 +458,38 @@ def search_bf16(query_bits, reference_bits, *, return_distances: bool = False, s
     return (idx, dist) if return_distances else idx
 
 
+def to_f16_bits(a) -> np.ndarray:
+    """A numpy float16 array, or uint16 bit patterns, as contiguous 2-D uint16 binary16 bit patterns (no conversion of
+    values: other dtypes are refused, so that nothing is rounded silently)."""
+    a = np.asarray(a)
+    if a.dtype == np.float16:
+        a = np.ascontiguousarray(a).view(np.uint16)
+    elif a.dtype != np.uint16:
+        raise ValueError("fp16 point sets must be numpy float16 arrays or uint16 bit patterns")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("fp16 point sets must be 2-D arrays")
+    return a
+
+
+def search_f16(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
+               path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """search() for fp16 point sets (numpy float16, or uint16 binary16 bit patterns) [points][k]: V0's arithmetic on the
+    values widened exactly to fp32 (nns_search_f16_ex).  refs_soa: reference_points is dimension-major [k][n]."""
+    q = to_f16_bits(query_points)
+    r = to_f16_bits(reference_points)
+    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
+        raise ValueError("query and reference dimensionality differ")
+    m, k = q.shape
+    n = r.shape[1] if refs_soa else r.shape[0]
+    idx = np.empty(m, dtype=np.int32)
+    dist = np.empty(m, dtype=np.float32) if return_distances else None
+    _check(lib.nns_search_f16_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
+                                 dist.ctypes.data if dist is not None else None, shards,
+                                 _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0), device), "nns_search_f16_ex")
+    return (idx, dist) if return_distances else idx
+
+
 def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa, topk_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
@@ -456,7 +497,7 @@ def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_so
     n = r.shape[1] if refs_soa else r.shape[0]
     idx = np.empty((m, max(kn, 0)), dtype=np.int32)
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
-    fn = lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
+    fn = lib.nns_search_f16_topk if bf16 == 2 else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
               shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
            "nns_search_topk")
@@ -485,6 +526,13 @@ def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: b
     return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa, topk_mfma)
 
 
+def search_topk_f16(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
+                    path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """search_topk() for fp16 point sets (numpy float16 or uint16 bit patterns; nns_search_f16_topk)."""
+    return _search_topk(to_f16_bits(query_points), to_f16_bits(reference_points), kn, 2, return_distances, shards, path,
+                        device, refs_soa)
+
+
 def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
@@ -493,7 +541,7 @@ def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa,
     lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
     pidx = ctypes.POINTER(ctypes.c_int)()
     pdist = ctypes.POINTER(ctypes.c_float)()
-    fn = lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
+    fn = lib.nns_search_f16_range if bf16 == 2 else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
               ctypes.byref(pdist) if return_distances else None,
               _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_RANGE_MFMA if range_mfma else 0),
@@ -533,6 +581,13 @@ def search_range_bf16(query_bits, reference_bits, radius2: float, *, return_dist
     return _search_range(q, r, radius2, True, return_distances, path, device, refs_soa, range_mfma)
 
 
+def search_range_f16(query_points, reference_points, radius2: float, *, return_distances: bool = False,
+                     path: str = "auto", device: int = 0, refs_soa: bool = False):
+    """search_range() for fp16 point sets (numpy float16 or uint16 bit patterns; nns_search_f16_range)."""
+    return _search_range(to_f16_bits(query_points), to_f16_bits(reference_points), radius2, 2, return_distances, path,
+                         device, refs_soa)
+
+
 # ---------------------------------------------------------------------------
 # device-resident API (torch tensors are only the owners of device memory)
 # ---------------------------------------------------------------------------
@@ -561,10 +616,11 @@ class Index:
         range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA).
         topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA)."""
         import torch
-        if refs.dtype not in (torch.float32, torch.bfloat16) or refs.dim() != 2 or not refs.is_contiguous() \
-                or not refs.is_cuda:
-            raise ValueError("refs must be a contiguous fp32 or bf16 [n][k] tensor on a HIP device")
+        if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16) or refs.dim() != 2 \
+                or not refs.is_contiguous() or not refs.is_cuda:
+            raise ValueError("refs must be a contiguous fp32, bf16 or fp16 [n][k] tensor on a HIP device")
         self.bf16 = refs.dtype == torch.bfloat16
+        self.f16 = refs.dtype == torch.float16
         self.refs = refs  # keep alive: the index reads the original values
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
         self.device = refs.device.index or 0
@@ -574,7 +630,7 @@ class Index:
             | (NNS_TOPK_MFMA if topk_mfma else 0)
         self.flags = flags
         h = ctypes.c_void_p()
-        create = lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
+        create = lib.nns_index_create_f16 if self.f16 else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
         self._h = h
@@ -592,7 +648,7 @@ class Index:
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
-        fn = lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
+        fn = lib.nns_index_search_f16 if self.f16 else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
         _check(fn(self._h, m, queries.data_ptr(), keys.data_ptr(), _stream_ptr(stream)), "nns_index_search")
         return keys
 
@@ -703,10 +759,11 @@ class Index:
         _check(lib.nns_index_stats(self._h, ctypes.byref(st)), "nns_index_stats")
         d = st.asdict()
         # the filter's operand form the index uses: "split" (split-bf16, fp32 points by default), "fp32"
-        # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16); None: exact path
+        # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16), "f16" (fp16 points);
+        # None: exact path
         form = ctypes.c_int(-1)
         _check(lib.nns_index_filter_form(self._h, ctypes.byref(form)), "nns_index_filter_form")
-        d["filter_form"] = {-1: None, 0: "fp32", 1: "bf16", 2: "bf16", 3: "split"}[form.value]
+        d["filter_form"] = {-1: None, 0: "fp32", 1: "bf16", 2: "bf16", 3: "split", 4: "f16"}[form.value]
         return d
 
     def near_ties(self) -> np.ndarray:

@@ -13,8 +13,8 @@ generated code after every build:
   that reads them as A/B operand or as a DIFFERENT (partially overlapping) C tuple.
   (An MFMA accumulating in place on exactly the same tuple is the supported back-to-back form.)
 
-WAIT = 8 for the 4-pass 16x16x32 (what hipcc itself inserts behind the builtin: s_nop 7) — the
-only MFMA the kernels issue from inline asm.  The 32x32x16 / 32x32x2 forms go through the
+WAIT = 8 for the 4-pass 16x16x32 (what hipcc itself inserts behind the builtin: s_nop 7), bf16 and
+f16 — the only MFMAs the kernels issue from inline asm.  The 32x32x16 / 32x32x2 forms go through the
 compiler builtins: hipcc's own hazard recognizer places their wait states (e.g. exactly 11 in
 front of a VALU overwrite of an 8-pass result) and they are not re-checked here.
 s_nop N counts N + 1 wait states, every other
@@ -34,7 +34,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nns-cuda_amd", "csrc")
 
-WAITS = {"v_mfma_f32_16x16x32_bf16": 8}   # the inline-asm MFMA; builtin forms are the compiler's business
+# the inline-asm MFMAs (the bf16 filter's and its f16 twin for fp16 points); builtin forms are the compiler's business
+WAITS = {"v_mfma_f32_16x16x32_bf16": 8, "v_mfma_f32_16x16x32_f16": 8}
 
 
 def compile_isa() -> str:
@@ -147,7 +148,7 @@ def check_kernel(name: str, lines) -> list:
     return sorted(problems)
 
 
-FILTER_KERNELS = r"filter_(?:split_|lazy_|lazy16_)?kernel"
+FILTER_KERNELS = r"filter_(?:split_|lazy_|lazy16_|f16_)?kernel"
 
 
 def split_kernels(text, which=FILTER_KERNELS, end="s_endpgm") -> dict:
