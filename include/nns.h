@@ -284,11 +284,42 @@ int nns_search_f16_ex(int k, int m, int n, const uint16_t *s_points,
                       const uint16_t *r_points, int *idx_out, float *dist_out,
                       int num_shards, unsigned flags, int device);
 
+/* int8 points (quantised embeddings, 8-bit descriptors).  Arrays are const int8_t *, same [points][k] layout.
+ * Semantics: the fp16 contract with one word changed — V0's arithmetic on the values widened exactly to fp32; indices
+ * bit-exact, distances bit-equal, lowest index wins ties, index 0 when nothing is selectable.  An index and its queries
+ * must have the same dtype: any mix with the fp32 / bf16 / fp16 entry points returns NNS_ERR_INVALID.  The dtype-agnostic
+ * entry points (nns_index_search_indices, nns_index_search_topk, nns_index_range_count / nns_index_range_fill,
+ * nns_index_refresh, nns_index_stats, nns_index_near_ties) serve an int8 index like any other.
+ * Exactness: each |q - r| <= 255, so a squared term is at most 65 025 and any sum of at most 256 of them at most
+ * 16 646 400 < 2^24: for k <= 256 V0's fp32 chain never rounds and the V0 distance IS the integer squared distance.
+ * (Beyond k = 258 the chain does round; the contract covers that: the exact kernels run V0's own arithmetic.)
+ * int8 has no non-finite or out-of-range value: nns_stats.nonfinite is always 0, and there is NO void or guard condition
+ * for refs or queries.
+ * Flags: NNS_PATH_AUTO / NNS_PATH_EXACT / NNS_PATH_MFMA, NNS_PROFILE, NNS_RECORDS_PER_REF.  NNS_FILTER_BF16,
+ * NNS_FILTER_F32 and NNS_FILTER_SPLIT_EAGER: NNS_ERR_INVALID.  NNS_RANGE_MFMA, NNS_TOPK_MFMA and NNS_REFS_SOA are not
+ * built for int8 points: NNS_ERR_UNSUPPORTED (at create, in the whole calls and in nns_plan_filter), answered like the
+ * operand flags before the device is looked up.
+ * MFMA filter: 32 <= k <= 256 with at least 64 queries (the AUTO rule of the 16-bit types), on v_mfma_i32_16x16x64_i8
+ * with i32 accumulators at KT = 256 for every such k (k <= 128 pads to 256: no 128-deep form is built) over K2's int8
+ * image — the values themselves, the factor -2 is applied where a tile retires.  The score |y|^2 - 2 x.y is an integer
+ * of magnitude < 2^24, exact in the accumulator and exact as fp32: the hardware contributes no error to the margin.
+ * nns_index_filter_form reports 5; the margin formula is nns_tau_consts mode 1's (there is no mode 5).  k < 32 and
+ * 256 < k <= 16384 take the exact kernels under AUTO; NNS_PATH_MFMA with k > 256: NNS_ERR_UNSUPPORTED.
+ * Times (tools/probe_i8.py, profiles/i8_probe.json): see README. */
+int nns_index_create_i8(nns_index **out, int device, int k, int n,
+                        const int8_t *r_dev, int64_t index_base,
+                        unsigned flags, void *stream);
+int nns_index_search_i8(nns_index *ix, int m, const int8_t *q_dev,
+                        nns_key *keys_dev, void *stream);
+int nns_search_i8_ex(int k, int m, int n, const int8_t *s_points,
+                     const int8_t *r_points, int *idx_out, float *dist_out,
+                     int num_shards, unsigned flags, int device);
+
 /* nns_index_search + nns_keys_unpack in one call for the single-shard case (what the reference's
  * cudaCall hands back is indices): keys_dev[m] as above AND idx_dev[m] = index of each key (0 for
  * NNS_KEY_NONE, as V0), dist_dev (optional) = its fp32 distance.  The low-dimensional exact kernel
  * writes all three in its one launch; the other paths append the unpack kernel.  q_dev has the
- * index's dtype (fp32, or bf16 / fp16 bit patterns). */
+ * index's dtype (fp32, bf16 / fp16 bit patterns, or int8). */
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev,
                              int *idx_dev, float *dist_dev, void *stream);
 
@@ -345,10 +376,13 @@ int nns_search_bf16_topk(int k, int m, int n, const uint16_t *s_points, const ui
 /* fp16 points (binary16 bit patterns): the same call; NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_f16_topk(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int kn,
                         int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
+/* int8 points: the same call; NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED. */
+int nns_search_i8_topk(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the top-K launch geometry for a k-D search of m queries over n refs.
  * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
- * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16 points (the 16-bit types share one
- * geometry: their refs are widened as they are read). */
+ * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points (the narrow types share
+ * one geometry: their refs are widened as they are read). */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
 
 /* ---- top-K on the matrix cores (NNS_TOPK_MFMA, K6m) -------------------------------
@@ -428,9 +462,12 @@ int nns_search_bf16_range(int k, int m, int n, const uint16_t *s_points, const u
 /* fp16 points (binary16 bit patterns): the same call; NNS_RANGE_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, float radius2,
                          int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+/* int8 points: the same call; NNS_RANGE_MFMA: NNS_ERR_UNSUPPORTED. */
+int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the range search's launch geometry for a k-D search of m queries over n
  * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
- * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16 points. */
+ * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points. */
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
 
 /* ---- range search on the matrix cores (NNS_RANGE_MFMA, K7m) ------------------------
@@ -495,7 +532,10 @@ int nns_fill_uniform(float *dev, size_t count, uint64_t seed, uint64_t offset,
  * hi.hi + hi.lo + lo.hi per 16-dim step on v_mfma_f32_32x32x16_bf16, the default filter
  * form of fp32 points); bf16 = 5: four 16x16 tiles of v_mfma_f32_16x16x32_f16 in mode 2's lane mapping, on the values
  * cast to binary16 (the fp16 filter's shape; compared with fp64.  4 is taken: the lazy order behind
- * nns_selftest_mfma_lazy).  These are the error models behind the filter's proof margin tau. */
+ * nns_selftest_mfma_lazy); bf16 = 6: four 16x16 tiles of v_mfma_i32_16x16x64_i8 in mode 2's lane mapping (the int8
+ * filter's shape: kt a multiple of 64, operands cast to int8, the i32 accumulator seeded with (int)c0 and returned as
+ * fp32 — exact integers: the check of the operand lane map).  These are the error models behind the filter's proof
+ * margin tau. */
 int nns_selftest_mfma(int kt, int bf16, const float *a, const float *b, const float *c0,
                       float *out);
 /* The same tile in the order of the lazy split filter: the kt / 16 hi.hi MFMAs first — out_hh (optional) = the
@@ -519,7 +559,9 @@ int nns_filter_lazy_tile(void);
  * short-stream record forms; the other fields do not depend on it).  NNS_ERR_UNSUPPORTED beyond
  * the deepest tile; NNS_ERR_INVALID for NNS_FILTER_BF16 / NNS_FILTER_F32 / NNS_FILTER_SPLIT_EAGER with bf16 points or together.  Lets CPU tests check the planner's invariants (coverage, padding, whole blocks per split).
  * bf16_points: 0 fp32, 1 bf16, 2 fp16 points.  fp16 points plan as bf16 points do, field for field, at 32 <= k <= 256;
- * k > 256, NNS_RANGE_MFMA or NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED; the operand flags: NNS_ERR_INVALID. */
+ * k > 256, NNS_RANGE_MFMA or NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED; the operand flags: NNS_ERR_INVALID.
+ * 3 int8 points: kt = 256 for every k <= 256, every other field the bf16 plan's at a 128-deep tile (k <= 128) — the
+ * int8 block has that tile's bytes and fragments; rejections as for fp16 points, NNS_REFS_SOA with them. */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f
@@ -546,7 +588,8 @@ int nns_tau_consts(int kt, float qnorm2, float ymax2, int mode, float *out3);
 int nns_split_lazy_bound(int kt, float qnorm2, float ymax2, float *out1);
 /* The operand form of the index's MFMA filter, as its tau mode: 0 fp32 operands (NNS_FILTER_F32, or a depth without
  * the split form), 1 bf16 points, 2 fp32 points rounded to bf16 operands, 3 fp32 points as split-bf16 operands, 4 fp16
- * points; -1 on the exact path.  Host only. */
+ * points, 5 int8 points (exact integer scores on v_mfma_i32_16x16x64_i8; 5 is not a tau mode: the margin formula is
+ * nns_tau_consts mode 1's); -1 on the exact path.  Host only. */
 int nns_index_filter_form(nns_index *ix, int *form_out);
 
 /* ---- the exchange of the one-process-per-GPU form ----------------------------
@@ -577,7 +620,7 @@ const char *nns_last_error(void); /* thread-local detail of the last failure */
 int nns_version(void);            /* major * 1000 + minor */
 /* Explicit replacement for the reference's hidden WarmUP static (ten V9 calls before main(),
  * core.cu:1900-1933): runs one tiny search through every kernel family (exact lane-per-query and
- * lane-per-ref, every fp32, bf16 and fp16 tile depth of the MFMA filter) on `device`, so that
+ * lane-per-ref, every fp32, bf16 and fp16 tile depth of the MFMA filter and the int8 tile) on `device`, so that
  * code-object loading, the filter's LDS opt-in and the first pool allocations are paid here and
  * not inside a timed call.  Optional: every entry point works without it. */
 int nns_warmup(int device);

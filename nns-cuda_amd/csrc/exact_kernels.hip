@@ -1188,6 +1188,15 @@ __device__ __forceinline__ void widen8(const float4 &raw, const f16_t *, float (
         o[2 * e + 1] = f16_widen_hi(w[e]);
     }
 }
+__device__ __forceinline__ void widen16(const float4 &raw, const i8_t *, float (&o)[16])   // 16 int8 -> 16 fp32
+{
+    const unsigned w[4] = {__float_as_uint(raw.x), __float_as_uint(raw.y), __float_as_uint(raw.z), __float_as_uint(raw.w)};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) o[4 * e + b] = i8_widen(w[e], b);
+    }
+}
 
 template <int QT, typename T>
 __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
@@ -1195,7 +1204,7 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
     const int *__restrict__ qlist, const int *__restrict__ qcount, int mq,
     int64_t index_base, nns_key *__restrict__ keys)
 {
-    constexpr int EPC = 16 / sizeof(T);          // elements per 16-byte chunk (4 fp32 / 8 bf16)
+    constexpr int EPC = 16 / sizeof(T);          // elements per 16-byte chunk (4 fp32 / 8 bf16, fp16 / 16 int8)
     constexpr int ROWB = 8 * 16 + 16;            // padded LDS row: 8 chunks + 16 B
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     float *sq = smem_f;                                            // [QT][k] fp32 queries
@@ -1267,7 +1276,8 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
                     const float4 raw = *reinterpret_cast<const float4 *>(mytile + lane * ROWB + ch * 16);
                     float rv[EPC];
                     if constexpr (EPC == 4) widen4(raw, nullptr, reinterpret_cast<float (&)[4]>(rv));
-                    else widen8(raw, (const T *)nullptr, reinterpret_cast<float (&)[8]>(rv));
+                    else if constexpr (EPC == 8) widen8(raw, (const T *)nullptr, reinterpret_cast<float (&)[8]>(rv));
+                    else widen16(raw, (const T *)nullptr, reinterpret_cast<float (&)[16]>(rv));
                     const int t0 = (c0 + ch) * EPC;
 #pragma unroll
                     for (int u = 0; u < QT; ++u) {
@@ -1740,7 +1750,9 @@ int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, 
         return launch_k1c(p, k, m, n, (const float *)q, (const float *)r, index_base, keys, ws, ws_fresh, idx_out,
                           dist_out, st);
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    if (bf16 == DT_F16)
+    if (bf16 == DT_I8)
+        NNS_TRY(launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, nullptr, nullptr, m, index_base, keys, st));
+    else if (bf16 == DT_F16)
         NNS_TRY(launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, nullptr, nullptr, m, index_base, keys, st));
     else if (bf16)
         NNS_TRY(launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, nullptr, nullptr, m, index_base, keys, st));
@@ -1761,6 +1773,7 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
     // batch both keep ~2048 workgroups busy.
     ExactPlan p{};
     k1b_plan(k, n, max_listed, 8, &p);
+    if (bf16 == DT_I8) return launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16 == DT_F16) return launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);
     return launch_k1b(p, k, n, (const float *)q, (const float *)r, qlist, qcount, 0, index_base, keys, st);

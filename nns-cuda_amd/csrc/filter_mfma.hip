@@ -73,6 +73,7 @@ __device__ __forceinline__ void static_for(F &&f)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // accumulators of a wave's query blocks as NAMED members (an array of ext-vectors passed by
 // reference is not scalarised by hipcc and lands in scratch)
@@ -137,6 +138,7 @@ constexpr int kAblate = NNS_FILTER_ABLATE;
 // What every operator has unless it says otherwise.
 struct OpBase {
     static constexpr bool kF16 = false;       // fp16 points (OpF16T): launched as filter_f16_kernel
+    static constexpr bool kI8 = false;        // int8 points (OpI8): i32 accumulators, launched as filter_i8_kernel
     static constexpr bool kSplit = false;     // split-bf16 operands of fp32 points streamed hi, lo per k-step (OpSplitT)
     static constexpr bool kLazy = false;      // the lazy schedule of the split operands (OpLazySplitT)
     static constexpr int kSlotSteps = 32;     // fragment steps (1 KiB each) of a ring slot
@@ -320,6 +322,47 @@ struct OpF16T : OpBF16T<SPB_, 8, 2, true> {
 };
 using OpF16 = OpF16T<16>;
 using OpF16K128 = OpF16T<8>;
+
+// int8 points at KT = 256: v_mfma_i32_16x16x64_i8.  A 1 KiB fragment is 16 points x 64 dims of bytes, so a 32-ref block is
+// 2 ref tiles x 4 k-steps = 8 fragments — OpBF16K128's geometry byte for byte (8 KiB blocks, 4 per ring slot, four
+// resident query fragments per 16-query tile: 64 operand registers), and ring, step schedule, record forms,
+// thresholds, lists and slow path are that operator's.  What differs:
+//   * the accumulators are i32, seeded with 0 (the inline constant as srcC), and hold x.y exactly: |x.y| <= 256 * 128^2 = 2^22;
+//   * -2 v does not fit int8, so the image holds the values and the factor is applied where a tile RETIRES (t16_step,
+//     k-step RET of the other tile; the stream's tail): retire() turns the tile's four accumulator registers IN PLACE into
+//     the fp32 scores s = fma(-2, (float)acc, |y|^2) — v_cvt_f32_i32 + v_fma_f32 per element, both exact: (float)acc is an
+//     integer of magnitude <= 2^22, the fp32 norm an integer <= 2^22, so |s| <= 2^22 + 2^23 < 2^24 is an integer fp32
+//     holds, and the fma rounds nothing.  The norms are the registers the bf16 operator seeds its tiles with (nseed0 /
+//     nseed1): tile rt's are loaded two steps before its first MFMA and stay until two steps before its next block's,
+//     which is after its retirement.  Padding refs carry the norm +INF: fma(-2, x, +INF) = +INF, never recorded;
+//   * everything behind the retirement (tile minimum, masks, threshold test, records) reads fp32 scores out of the same
+//     registers as before, and the tile's next seed MFMA overwrites them without reading (srcC = 0).
+// The MFMA is the compiler builtin: with 64 resident operand registers instead of OpBF16's 128 the allocator has room
+// for the three-address form (no spills: tests/test_i8_cpu.py reads the ISA), and hipcc's hazard recognizer places the
+// wait states between an MFMA and the VALU reads of its result, which the asm form leaves to hand-placed fences.
+struct OpI8 : OpBF16T<8> {
+    static constexpr bool kI8 = true;
+    __device__ static __forceinline__ void mma16(const float4 &a, const float4 &b, f32x4 &acc)
+    {
+        acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b),
+                                                                             __builtin_bit_cast(i32x4, acc), 0, 0, 0));
+    }
+    // first MFMA of a tile: srcC = 0 (the norms enter at the retirement)
+    __device__ static __forceinline__ void mma16_seed(const float4 &a, const float4 &b, f32x4 &acc, const f32x4 &)
+    {
+        const i32x4 z = {0, 0, 0, 0};
+        acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), z, 0, 0, 0));
+    }
+    // (builtin MFMAs: the compiler keeps the read hazards)
+    __device__ static __forceinline__ void mma16_tail_fence(AccSet16 &) {}
+    // a finished tile's i32 dot products -> fp32 scores |y|^2 - 2 x.y, in place (exact: see above)
+    __device__ static __forceinline__ void retire(f32x4 &acc, const f32x4 &norm)
+    {
+        const i32x4 d = __builtin_bit_cast(i32x4, acc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(-2.0f, (float)d[e], norm[e]);
+    }
+};
 
 // The deep bf16 tiles whose blocks do not divide a ring slot (KT 384, 640, 768, 1024) run v_mfma_f32_32x32x16_bf16 with
 // ONE query block per wave.
@@ -640,6 +683,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         else return (unsigned)(st * (kCandCap * 64 * (int)sizeof(CandEntry)));
     };
     f32x4 nseed0 = {0.0f, 0.0f, 0.0f, 0.0f}, nseed1 = nseed0;   // 16x16 tiles: the two ref tiles' norms
+    // (OpI8: the stream's first retirement is of the start accumulators — 0 under the norm +INF: score +INF, nothing to record)
+    if constexpr (OP::kI8) nseed1 = f32x4{__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
     // accumulators start at |y'_j|^2 of their rows: rows (r&3) + 8(r>>2) + 4h
     auto seed = [&](typename OP::Acc &acc, const char *slot, int blk) __attribute__((always_inline)) {
         if constexpr (T16) {
@@ -1121,6 +1166,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     // seed MFMA, whose in/out constraint "reads" them): 16 of the 74 VALU instructions of an
                     // interval, in a loop where every VALU issue cycle is an MFMA issue cycle lost.
                     asm volatile("" : "+v"(acc.template at<ot, qt>()));
+                    // (OpI8: the retiring tile's i32 dot products become its fp32 scores here, under its own norms)
+                    if constexpr (OP::kI8) OP::retire(acc.template at<ot, qt>(), ot == 0 ? nseed0 : nseed1);
                     const f32x4 o = acc.template at<ot, qt>();
                     if constexpr ((kAblate & 2) != 0) asm volatile("" ::"v"(o));
                     else tmh[qt] = fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]);
@@ -1148,7 +1195,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     static_assert(PF < RING && SPS % RING == 0 && (!OP::kLag || PF <= LAGOFF), "prefetch ring");
     typename OP::Acc acc;
     if constexpr (T16) {
-        const f32x4 inf4 = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
+        // (OpI8: i32 zeros, retired under the norm +INF — see nseed1)
+        const float inf0 = OP::kI8 ? 0.0f : __builtin_inff();
+        const f32x4 inf4 = {inf0, inf0, inf0, inf0};
         static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
             acc.template at<0, decltype(qc)::value>() = inf4;
             acc.template at<1, decltype(qc)::value>() = inf4;
@@ -1347,6 +1396,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         OP::mma16_tail_fence(acc);
         if constexpr ((kAblate & 2) == 0) {
             static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
+                if constexpr (OP::kI8) OP::retire(acc.template at<1, decltype(qc)::value>(), nseed1);
                 const f32x4 &o = acc.template at<1, decltype(qc)::value>();
                 tmh[decltype(qc)::value] = fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]);
             });
@@ -1439,6 +1489,12 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_f16_kernel(const FilterAr
 {
     filter_main<OP>(a);
 }
+// int8 points (OpI8)
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_i8_kernel(const FilterArgs a)
+{
+    filter_main<OP>(a);
+}
 // (the 32x32x16 lazy kernel stays in every build, launched or not: the ISA checks of the two read one compilation)
 template __global__ void filter_lazy_kernel<OpLazySplit>(const FilterArgs a);
 template __global__ void filter_lazy16_kernel<OpLazySplit16>(const FilterArgs a);
@@ -1514,6 +1570,35 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
                 for (int r = 0; r < 16; ++r) out[1024 + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[r];
             }
         }
+    } else if (bf16 == 6) {
+        // mode 2's four 16x16 tiles and lane mapping on v_mfma_i32_16x16x64_i8 (OpI8 and K2's int8 image): lane l holds dims
+        // 64 ks + 16 (l >> 4) .. + 15 of row l & 15, byte j of the four operand registers = dim j of the sixteen; operands
+        // cast to int8, the i32 accumulator seeded with c0 and returned as fp32
+        const int c = lane & 15, g = lane >> 4;
+        for (int rt = 0; rt < 2; ++rt)
+            for (int qt = 0; qt < 2; ++qt) {
+                i32x4 t;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t[e] = (int)c0[16 * rt + 4 * g + e];
+                for (int ks = 0; ks < kt / 64; ++ks) {
+                    i32x4 av, bv;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        unsigned aw = 0, bw = 0;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            aw |= (unsigned)(unsigned char)(int8_t)(int)a[(16 * rt + c) * kt + 64 * ks + 16 * g + 4 * w + j] << (8 * j);
+                            bw |= (unsigned)(unsigned char)(int8_t)(int)b[(16 * qt + c) * kt + 64 * ks + 16 * g + 4 * w + j] << (8 * j);
+                        }
+                        av[w] = (int)aw;
+                        bv[w] = (int)bw;
+                    }
+                    t = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, bv, t, 0, 0, 0);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) out[(16 * rt + 4 * g + e) * 32 + 16 * qt + c] = (float)t[e];
+            }
+        return;
     } else if (bf16 == 5) {
         // mode 2's four 16x16 tiles and lane mapping on v_mfma_f32_16x16x32_f16, operands cast to binary16 (OpF16T)
         const int c = lane & 15, g = lane >> 4;
@@ -1680,7 +1765,9 @@ int filter_lazy_tile()
 template <class F>
 static int with_filter_op(const FilterGeom &g, F &&f)
 {
-    if (g.f16) {
+    if (g.i8) {
+        if (g.kt == 256) return f(OpI8{});
+    } else if (g.f16) {
         switch (g.kt) {
         case 128: return f(OpF16K128{});
         case 256: return f(OpF16{});
@@ -1719,11 +1806,17 @@ static int with_filter_op(const FilterGeom &g, F &&f)
 }
 
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager,
-                bool f16)
+                bool f16, bool i8)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
     int kt = 0;
-    if (f16) {                         // fp16 points: the two 16x16x32 depths (deeper tiles: not built)
+    if (i8) {                          // int8 points: the one 16x16x64 depth (k <= 128 pads to it too)
+        if (k <= 256) kt = 256;
+        if (!kt) {
+            set_error("MFMA filter: k = %d exceeds the deepest tile of int8 points (256)", k);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    } else if (f16) {                         // fp16 points: the two 16x16x32 depths (deeper tiles: not built)
         if (k <= 128) kt = 128;
         else if (k <= 256) kt = 256;
         if (!kt) {
@@ -1751,6 +1844,7 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     }
     g->bf16 = bf16 ? 1 : 0;
     g->f16 = f16 ? 1 : 0;
+    g->i8 = i8 ? 1 : 0;
     g->mixed = mixed ? 1 : 0;
     // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
     g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;
@@ -1823,7 +1917,8 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (OP::kF16) return filter_f16_kernel<OP>;
+        if constexpr (OP::kI8) return filter_i8_kernel<OP>;
+        else if constexpr (OP::kF16) return filter_f16_kernel<OP>;
         else if constexpr (OP::kLazy && OP::kTile16) return filter_lazy16_kernel<OP>;
         else if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
         else if constexpr (OP::kSplit) return filter_split_kernel<OP>;
@@ -1851,7 +1946,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
     FilterArgs a;
     a.qimg = reinterpret_cast<const float4 *>(qimg);
     a.rimg = reinterpret_cast<const char *>(rimg);
-    a.rimg_lo = g.lazy_img ? a.rimg + (size_t)g.n_pad * g.kt * 2 : nullptr;
+    a.rimg_lo = g.lazy_img ? a.rimg + (size_t)g.n_pad * g.kt * 2 : nullptr;   // (split operands only)
     a.rnorm = rnorm;
     a.qnorm = qnorm;
     a.scal = scal;

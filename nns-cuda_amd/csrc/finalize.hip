@@ -90,6 +90,8 @@ __device__ __forceinline__ float4 load_f4(const uint16_t *p)
 
 __device__ __forceinline__ float load_f(const f16_t *p, size_t i) { return pt_ld1(p + i); }   // fp16 -> fp32: exact
 __device__ __forceinline__ float4 load_f4(const f16_t *p) { return pt_ld4(p); }
+__device__ __forceinline__ float load_f(const i8_t *p, size_t i) { return pt_ld1(p + i); }    // int8 -> fp32: exact
+__device__ __forceinline__ float4 load_f4(const i8_t *p) { return pt_ld4(p); }
 
 // V0's exact distance (core.cu:38-43), t ascending; 4 dims per load when aligned
 template <typename T>
@@ -637,10 +639,15 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
                     const CandEntry *lists, const int *counts, const float *qnorm, DevScalars *scal,
                     int64_t index_base, nns_key *keys, int *amb_list, int *multi_list, hipStream_t st)
 {
-    const int mode = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // tau mode (nns_internal.h)
-    const bool data_bf16 = g.bf16 && !g.mixed && !g.f16;    // element type of q / r
+    // tau mode (nns_internal.h; int8 points: mode 1 — exact scores, exact V0 distances, so mode 1's margin is a valid one)
+    const int mode = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
+    const bool data_bf16 = g.bf16 && !g.mixed && !g.f16 && !g.i8;    // element type of q / r
     if (g.splits >= 4) {   // few queries, many lists per query: one wave per query
-        if (g.f16)
+        if (g.i8)
+            hipLaunchKernelGGL(finalize_wave_kernel<i8_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
+                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists,
+                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
+        else if (g.f16)
             hipLaunchKernelGGL(finalize_wave_kernel<f16_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
                                g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists,
                                counts, qnorm, scal, index_base, keys, amb_list, multi_list);
@@ -669,7 +676,11 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
         NNS_HIP(hipMemsetAsync(diag, 0, (size_t)units * 8 * sizeof(unsigned long long), st));
     }
 #endif
-    if (g.f16)
+    if (g.i8)
+        hipLaunchKernelGGL(K5_UNIT_KERNEL<i8_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
+                           g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists, counts, qnorm,
+                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
+    else if (g.f16)
         hipLaunchKernelGGL(K5_UNIT_KERNEL<f16_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
                            g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists, counts, qnorm,
                            scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);

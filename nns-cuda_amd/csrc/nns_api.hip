@@ -32,7 +32,7 @@ void set_error(const char *fmt, ...)
 using namespace nns;
 
 // one point of a tile image
-static size_t img_row_bytes(const FilterGeom &g) { return (size_t)g.kt * (g.bf16 ? 2 : 4); }
+static size_t img_row_bytes(const FilterGeom &g) { return (size_t)g.kt * (g.i8 ? 1 : g.bf16 ? 2 : 4); }
 // The filter's ring DMA runs up to three slots (32 KiB of image, slot_pts norms each) past the last one without a
 // bounds branch: images and norm arrays carry that much padding (+ the over-read of a 128-norm piece)
 static size_t img_bytes(const FilterGeom &g, int pts_pad) { return (size_t)pts_pad * img_row_bytes(g) + 3 * 32768 + 4096; }
@@ -75,10 +75,10 @@ struct nns_index {
     int64_t base = 0;
     unsigned flags = 0;
     int path = NNS_PATH_EXACT;
-    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k]
+    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k], or int8 [n][k]
     const void *r_soa = nullptr;   // NNS_REFS_SOA: the caller's [k][n] array; r_dev is then r_own
     void *r_own = nullptr;         // owned point-major copy of r_soa
-    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16
+    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8
     bool profile = false;
     bool refs_bad = false;
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
@@ -213,7 +213,7 @@ int order_after_default_stream(hipStream_t st)
 static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
 {
     if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) && bf16) {
-        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16 and fp16 points use their own filter)");
+        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16, fp16 and int8 points use their own filter)");
         return NNS_ERR_INVALID;
     }
     if ((flags & NNS_FILTER_BF16) && (flags & NNS_FILTER_F32)) {
@@ -232,10 +232,10 @@ static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *spl
 
 // what NNS_RANGE_MFMA / NNS_TOPK_MFMA take: fp32 points whose filter form is the split one, at the split tiles' depths;
 // bf16 points at the depths of the 16x16x32 tiles (below 32 dimensions AUTO does not filter bf16 points either); fp16
-// points: no flag pass is built
+// and int8 points: no flag pass is built
 static bool flag_pass_supported(int k, int bf16, unsigned flags)
 {
-    if (bf16 == DT_F16 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16))) return false;
+    if (bf16 == DT_F16 || bf16 == DT_I8 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16))) return false;
     return bf16 ? (k >= 32 && k <= 256) : (k >= 8 && k <= 256);
 }
 
@@ -243,6 +243,11 @@ static int prep_refs(nns_index *ix, hipStream_t st)
 {
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(ix->scal, 0, sizeof(DevScalars), st));
+    if (ix->bf16 == DT_I8) {   // (the values themselves: the filter applies the -2; no max-|v| word: nothing voids the filter)
+        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, ix->n, g.n_pad, (const int8_t *)ix->r_dev, INFINITY, ix->rimg, ix->rnorm,
+                                     &ix->scal->ymax2_bits, st));
+        return NNS_OK;
+    }
     if (ix->bf16) {
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, ix->n, g.n_pad, (const uint16_t *)ix->r_dev, -2.0f, INFINITY,
                                        ix->rimg, ix->rnorm, &ix->scal->ymax2_bits,
@@ -338,6 +343,16 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         return NNS_ERR_INVALID;
     }
     *out = nullptr;
+    if (bf16 == DT_I8) {   // (what an int8 index does not take, answered before the device is looked up)
+        if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
+            set_error("nns_index_create_i8: the operand flags apply to fp32 points (flags 0x%x)", flags);
+            return NNS_ERR_INVALID;
+        }
+        if (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA | NNS_REFS_SOA)) {
+            set_error("nns_index_create_i8: the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points (flags 0x%x)", flags);
+            return NNS_ERR_UNSUPPORTED;
+        }
+    }
     if (bf16 == DT_F16) {   // (what an fp16 index does not take, answered before the device is looked up)
         if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
             set_error("nns_index_create_f16: the operand flags apply to fp32 points (flags 0x%x)", flags);
@@ -385,8 +400,8 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             return frc;
         }
     }
-    // deepest tile of the MFMA filter (fp16 points: the two 16x16x32 depths)
-    const int kmax = bf16 == DT_F16 ? 256 : (bf16 || ix->mixed) ? kMaxFilterK : 256;
+    // deepest tile of the MFMA filter (fp16 points: the two 16x16x32 depths; int8 points: the 256-deep 16x16x64 tile)
+    const int kmax = (bf16 == DT_F16 || bf16 == DT_I8) ? 256 : (bf16 || ix->mixed) ? kMaxFilterK : 256;
     int path = flags & NNS_PATH_MASK;
     // crossover: from k = 8 the MFMA filter (KT = 16 / 32 tile) beats 3k VALU ops per pair; bf16 tiles
     // are at least 128 deep, so they only pay from k = 32
@@ -400,7 +415,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     ix->path = path;
     if (flags & NNS_REFS_SOA) {
         // dimension-major refs: one transpose into a point-major copy the index owns
-        const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+        const size_t esz = dt_size(bf16);
         ix->r_soa = r_dev;
         if (pool_alloc(&ix->r_own, (size_t)n * k * esz) != hipSuccess) {
             set_error("nns_index_create: device allocation failed (point-major copy of %d x %d refs)", n, k);
@@ -430,7 +445,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         }
         if (path == NNS_PATH_MFMA || ix->flag_image()) {   // (the range and top-K flags build the image whatever the 1-NN path)
             if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16 == DT_F16)) !=
+                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16 == DT_F16, bf16 == DT_I8)) !=
                 NNS_OK)
                 break;
             const FilterGeom &g = ix->geom;
@@ -486,6 +501,13 @@ int nns_index_create_f16(nns_index **out, int device, int k, int n, const uint16
     return index_create_impl(out, device, k, n, r_dev, DT_F16, index_base, flags & ~kCreateNoSync, stream);
 }
 
+int nns_index_create_i8(nns_index **out, int device, int k, int n, const int8_t *r_dev,
+                        int64_t index_base, unsigned flags, void *stream)
+{
+    DeviceScope keep_device;
+    return index_create_impl(out, device, k, n, r_dev, DT_I8, index_base, flags & ~kCreateNoSync, stream);
+}
+
 int nns_index_refresh(nns_index *ix, void *stream)
 {
     if (!ix) return NNS_ERR_INVALID;
@@ -494,7 +516,7 @@ int nns_index_refresh(nns_index *ix, void *stream)
     hipStream_t st = (hipStream_t)stream;
     ix->last_stream = st;
     if (ix->r_soa)   // the caller's dimension-major array may have changed
-        NNS_TRY(launch_soa_to_aos(ix->k, ix->n, ix->r_soa, ix->r_own, ix->bf16 ? 2 : 4, st));
+        NNS_TRY(launch_soa_to_aos(ix->k, ix->n, ix->r_soa, ix->r_own, (int)dt_size(ix->bf16), st));
     if (ix->path != NNS_PATH_MFMA && !ix->flag_image()) return NNS_OK;
     if (ix->profile) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_R0], st);
     NNS_TRY(prep_refs(ix, st));
@@ -518,7 +540,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
     FilterGeom g = ix->geom;
     FilterGeom gq{};
     NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, ix->bf16 == DT_F16));
+                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, ix->bf16 == DT_F16, ix->bf16 == DT_I8));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
     (void)g;
     if (gq.m_pad > ix->m_cap) {
@@ -607,7 +629,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
 {
     if (ix && ix->bf16 != bf16) {
         set_error("nns_index_search: query dtype does not match the index (%s index)",
-                  ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
+                  ix->bf16 == DT_I8 ? "int8" : ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
         return NNS_ERR_INVALID;
     }
     if (!ix || !q_dev || !keys_dev || m <= 0) {
@@ -653,7 +675,9 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
                       offsetof(DevScalars, multi_count) == offsetof(DevScalars, amb_count) + sizeof(int),
                   "per-search scalars must be adjacent");
     NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
-    if (bf16)
+    if (bf16 == DT_I8)
+        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st));
+    else if (bf16)
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg, ix->qnorm,
                                        nullptr, &ix->scal->q_maxabs_bits, st, bf16 == DT_F16));
     else
@@ -700,6 +724,12 @@ int nns_index_search_f16(nns_index *ix, int m, const uint16_t *q_dev, nns_key *k
 {
     DeviceScope keep_device;
     return index_search_impl(ix, m, q_dev, DT_F16, keys_dev, stream);
+}
+
+int nns_index_search_i8(nns_index *ix, int m, const int8_t *q_dev, nns_key *keys_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_search_impl(ix, m, q_dev, DT_I8, keys_dev, stream);
 }
 
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev, int *idx_dev,
@@ -839,7 +869,7 @@ int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, f
 
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16 and fp16 (2) refs are widened as they are read)
+    (void)bf16_points;   // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     NNS_TRY(topk_check_kn("nns_plan_topk", kn));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
@@ -1088,7 +1118,7 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16 and fp16 (2) refs are widened as they are read)
+    (void)bf16_points;   // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
     RangePlan p{};
@@ -1277,7 +1307,8 @@ int nns_index_filter_form(nns_index *ix, int *form_out)
 {
     if (!ix || !form_out) return NNS_ERR_INVALID;
     const FilterGeom &g = ix->geom;
-    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;   // = the tau mode
+    // = the tau mode (5, int8 points: no tau mode of its own, the margin is mode 1's)
+    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.i8 ? 5 : g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
     return NNS_OK;
 }
 
@@ -1358,8 +1389,9 @@ int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *
 
 static int selftest_mfma_impl(int kt, int bf16, const float *a, const float *b, const float *c0, float *out, float *out_hh)
 {
-    // (mode 4 is the lazy order behind nns_selftest_mfma_lazy; 5: the f16 tiles)
-    if (kt <= 0 || (kt & 15) || ((bf16 == 2 || bf16 == 5) && (kt & 31)) || bf16 < 0 || bf16 > 5 || !a || !b || !c0 || !out)
+    // (mode 4 is the lazy order behind nns_selftest_mfma_lazy; 5: the f16 tiles; 6: the i8 tiles, 64 dims per step)
+    if (kt <= 0 || (kt & 15) || ((bf16 == 2 || bf16 == 5) && (kt & 31)) || (bf16 == 6 && (kt & 63)) || bf16 < 0 || bf16 > 6 ||
+        !a || !b || !c0 || !out)
         return NNS_ERR_INVALID;
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(0));
@@ -1512,9 +1544,13 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
         set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags are not built for fp16 points (flags 0x%x)", flags);
         return NNS_ERR_UNSUPPORTED;
     }
+    if (bf16_points == DT_I8 && (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA | NNS_REFS_SOA))) {
+        set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points (flags 0x%x)", flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
     FilterGeom g{};
     NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split,
-                        (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16_points == DT_F16));
+                        (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16_points == DT_F16, bf16_points == DT_I8));
     const int v[16] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
                        g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split, g.lazy};
     memcpy(out, v, (out_len >= 16 ? 16 : out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
@@ -1556,7 +1592,7 @@ int nns_selftest_lane_share(int tile16, const float *in64, float *out64)
 static int search_host_small(int k, int m, int n, const void *s_points, const void *r_points, int bf16,
                              int *idx_out, float *dist_out, unsigned flags, int device)
 {
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = dt_size(bf16);
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz;
     const size_t off_r = up(qb), in_bytes = off_r + rb;
@@ -1627,12 +1663,12 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
     if (flags & (NNS_REFS_SOA | NNS_PROFILE)) return false;
     if (rbytes < kChunkMinBytes || n < 4096 || m < kTinyM) return false;
     const unsigned path = flags & NNS_PATH_MASK;
-    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > (bf16 == DT_F16 ? 256 : kMaxFilterK);
+    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > ((bf16 == DT_F16 || bf16 == DT_I8) ? 256 : kMaxFilterK);
     double est_s;
     if (exact) {
         est_s = 3.0 * k * (double)m * (double)n / 45e12;
     } else {
-        int kt = bf16 ? 128 : 16;
+        int kt = bf16 == DT_I8 ? 256 : bf16 ? 128 : 16;
         while (kt < k) kt *= 2;
         const bool bf16_ops = bf16 || k > 256 || (flags & NNS_FILTER_BF16);
         // fp32 points: split-bf16 operands unless NNS_FILTER_F32 (3 bf16 MFMAs per 16 dims: ~5x the fp32 operands' rate)
@@ -1647,7 +1683,7 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
 static int search_range_overlapped_impl(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d,
                                         int bf16, int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp)
 {
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = dt_size(bf16);
     hipStream_t st = lib_stream_acquire();
     if (!st) return NNS_ERR_UNSUPPORTED;
     // the caller's query upload (synchronous copy) happens before the first search
@@ -1715,7 +1751,7 @@ int search_range_overlapped(int device, int k, int m, int n, const void *q_d, co
 static int search_host_chunked(int k, int m, int n, const void *s_points, const void *r_points, int bf16,
                                int *idx_out, float *dist_out, unsigned flags, int device)
 {
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = dt_size(bf16);
     const size_t qb = (size_t)m * k * esz, rb = (size_t)n * k * esz;
     HostCall call(nullptr);   // (the overlapped core takes a stream of its own; unpack and copies: default stream)
     char *q_d = nullptr, *r_d = nullptr;
@@ -1754,7 +1790,7 @@ static int search_host_chunked(int k, int m, int n, const void *s_points, const 
 static int search_whole(const char *where, int k, int m, int n, const void *s_points, const void *r_points, int bf16,
                         int kn, int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = dt_size(bf16);
     const size_t rows = (size_t)m * (kn ? kn : 1);
     // kernels on a non-blocking stream of the library (nullptr if none can be made: the default stream then)
     HostCall call(lib_stream_acquire());
@@ -1807,10 +1843,26 @@ static int search_whole(const char *where, int k, int m, int n, const void *s_po
     return NNS_OK;
 }
 
+// what the whole calls of int8 points do not take, answered (like create's own check) before the device is looked up
+static int check_i8_flags(const char *where, int bf16, unsigned flags)
+{
+    if (bf16 != DT_I8) return NNS_OK;
+    if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
+        set_error("%s: the operand flags apply to fp32 points (flags 0x%x)", where, flags);
+        return NNS_ERR_INVALID;
+    }
+    if (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA | NNS_REFS_SOA)) {
+        set_error("%s: the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points (flags 0x%x)", where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
 static int search_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16,
                             int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
     NNS_TRY(check_whole_call("nns_search_f32", k, m, n, s_points, r_points, idx_out));
+    NNS_TRY(check_i8_flags("nns_search_i8_ex", bf16, flags));
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(device));
     if (num_shards < 1) num_shards = 1;
@@ -1820,7 +1872,7 @@ static int search_host_impl(int k, int m, int n, const void *s_points, const voi
         const int src = search_host_small(k, m, n, s_points, r_points, bf16, idx_out, dist_out, flags, device);
         if (src != NNS_ERR_UNSUPPORTED) return src;
     }
-    if (num_shards == 1 && chunked_pays(k, m, n, bf16, flags, (size_t)n * k * (bf16 ? 2 : 4))) {
+    if (num_shards == 1 && chunked_pays(k, m, n, bf16, flags, (size_t)n * k * dt_size(bf16))) {
         const int crc = search_host_chunked(k, m, n, s_points, r_points, bf16, idx_out, dist_out, flags, device);
         if (crc != NNS_ERR_UNSUPPORTED) return crc;   // (UNSUPPORTED: no stream -> plain path)
     }
@@ -1843,8 +1895,9 @@ static int check_exact_only_flags(const char *where, const char *what, unsigned 
 static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
                                  int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
-    const char *where = bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
+    const char *where = bf16 == DT_I8 ? "nns_search_i8_topk" : bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, idx_out));
+    NNS_TRY(check_i8_flags(where, bf16, flags));
     NNS_TRY(topk_check_kn(where, kn));
     if ((int64_t)m * kn > 0x7FFFFFFFll * 4) {
         set_error("%s: m * kn too large for one call", where);
@@ -1871,7 +1924,7 @@ static int search_whole_range(const char *where, int k, int m, int n, const void
                               int bf16, float radius2, int64_t *lims_out, int **hidx, float **hdist, unsigned flags,
                               int device)
 {
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = dt_size(bf16);
     const size_t lb = ((size_t)m + 1) * sizeof(int64_t);
     HostCall call(lib_stream_acquire());
     const hipStream_t st = call.st;
@@ -1922,7 +1975,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
                                   float radius2, int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags,
                                   int device)
 {
-    const char *where = bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
+    const char *where = bf16 == DT_I8 ? "nns_search_i8_range" : bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
     if (idx_out) *idx_out = nullptr;
     if (dist_out) *dist_out = nullptr;
     if (!idx_out) {
@@ -1931,6 +1984,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     }
     // (lims_out stands for the output buffer of the shared check)
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
+    NNS_TRY(check_i8_flags(where, bf16, flags));
     NNS_TRY(range_check_radius(where, radius2));
     NNS_TRY(check_exact_only_flags(where, "range search", flags & ~(unsigned)NNS_RANGE_MFMA));
     if ((flags & NNS_RANGE_MFMA) && !flag_pass_supported(k, bf16, flags)) {
@@ -1971,6 +2025,24 @@ int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const ui
                          int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
 {
     return search_range_host_impl(k, m, n, s_points, r_points, DT_F16, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    return search_range_host_impl(k, m, n, s_points, r_points, DT_I8, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_i8_ex(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int *idx_out,
+                     float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_host_impl(k, m, n, s_points, r_points, DT_I8, idx_out, dist_out, num_shards, flags, device);
+}
+
+int nns_search_i8_topk(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_topk_host_impl(k, m, n, s_points, r_points, DT_I8, kn, idx_out, dist_out, num_shards, flags, device);
 }
 
 int nns_search_f16_ex(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int *idx_out,
@@ -2016,7 +2088,7 @@ int nns_warmup(int device)
     // (k, m, n, bf16, path): K1a (3-D and 16-D), K1b, the fp32 tile depths 16 / 32 / 64 / 128 / 256 (forced onto the
     // filter: AUTO keeps a 64 x 512 x 16 problem on the exact kernel), the bf16-operand tiles for fp32 points (512 /
     // 384 / 512 / 640 / 768 / 1024: AUTO), the bf16 tiles 128 / 256 / 384 / 512 / 640 / 768 / 1024, the fp16 tiles 128 / 256
-    // (dtype 2)
+    // (dtype 2), the int8 tile (dtype 3: v_mfma_i32_16x16x64_i8, 256-deep)
     static const int shapes[][5] = {{3, 64, 512, 0, NNS_PATH_AUTO},    {16, 64, 512, 0, NNS_PATH_AUTO},  {16, 1, 512, 0, NNS_PATH_AUTO},
                                     {16, 64, 512, 0, NNS_PATH_MFMA},   {24, 64, 512, 0, NNS_PATH_MFMA},  {40, 64, 512, 0, NNS_PATH_MFMA},
                                     {100, 64, 512, 0, NNS_PATH_MFMA},  {200, 64, 512, 0, NNS_PATH_MFMA}, {300, 64, 512, 0, NNS_PATH_AUTO},
@@ -2024,7 +2096,8 @@ int nns_warmup(int device)
                                     {600, 64, 512, 0, NNS_PATH_AUTO},  {700, 64, 512, 0, NNS_PATH_AUTO}, {800, 64, 512, 0, NNS_PATH_AUTO},
                                     {64, 64, 512, 1, NNS_PATH_MFMA},   {200, 64, 512, 1, NNS_PATH_MFMA}, {300, 64, 512, 1, NNS_PATH_MFMA},
                                     {600, 64, 512, 1, NNS_PATH_MFMA},  {700, 64, 512, 1, NNS_PATH_MFMA}, {800, 64, 512, 1, NNS_PATH_MFMA},
-                                    {64, 64, 512, 2, NNS_PATH_MFMA},   {200, 64, 512, 2, NNS_PATH_MFMA}};
+                                    {64, 64, 512, 2, NNS_PATH_MFMA},   {200, 64, 512, 2, NNS_PATH_MFMA},
+                                    {64, 64, 512, DT_I8, NNS_PATH_MFMA}};
     const int kmax = 800, mmax = 64, nmax = 512;
     float *q = (float *)malloc(sizeof(float) * kmax * mmax), *r = (float *)malloc(sizeof(float) * kmax * nmax);
     int *idx = (int *)malloc(sizeof(int) * mmax);
@@ -2039,7 +2112,20 @@ int nns_warmup(int device)
     for (int i = 0; i < kmax * nmax; ++i) r[i] = (float)((x = x * 1664525u + 1013904223u) >> 8) * (1.0f / 16777216.0f);
     int rc = NNS_OK;
     for (const auto &sh : shapes) {
-        if (sh[3]) {
+        if (sh[3] == DT_I8) {
+            // the same numbers (in [0, 1)) as int8 values -128 .. 127
+            int8_t *qb = (int8_t *)malloc((size_t)sh[0] * sh[1]);
+            int8_t *rb = (int8_t *)malloc((size_t)sh[0] * sh[2]);
+            if (qb && rb) {
+                for (int i = 0; i < sh[0] * sh[1]; ++i) qb[i] = (int8_t)((int)(q[i] * 256.0f) - 128);
+                for (int i = 0; i < sh[0] * sh[2]; ++i) rb[i] = (int8_t)((int)(r[i] * 256.0f) - 128);
+                rc = search_host_impl(sh[0], sh[1], sh[2], qb, rb, DT_I8, idx, nullptr, 1, (unsigned)sh[4], device);
+            } else {
+                rc = NNS_ERR_NOMEM;
+            }
+            free(qb);
+            free(rb);
+        } else if (sh[3]) {
             // the same numbers as bf16 bit patterns (truncated: this is a warm-up, not a result); dtype 2: as fp16 bit
             // patterns, truncated likewise (the values lie in [0, 1): below 2^-14 they become 0)
             const auto bits16 = [&](float v) {

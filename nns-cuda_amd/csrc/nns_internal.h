@@ -67,7 +67,7 @@ struct DeviceScope {
 int order_after_default_stream(hipStream_t st);
 void stager_release();         // free the small whole calls' pinned scratch (nns_api.hip)
 // the overlapped upload of a contiguous host ref range (nns_api.hip), shared with nns_search_*_multi's shards
-// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16 or DT_F16)
+// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16, DT_F16 or DT_I8)
 bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes);
 int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
                             int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp);
@@ -200,8 +200,9 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
 
 // ---- point element types ------------------------------------------------------------------------------------------
 // The dtype of an index and of its queries, the `int bf16` argument of the launchers: fp32, bf16 bit patterns, IEEE
-// binary16 (fp16) bit patterns.  Element size: dtype ? 2 : 4.
-enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };
+// binary16 (fp16) bit patterns, int8 values.  Element size: dt_size(dtype).
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3 };
+inline size_t dt_size(int dt) { return dt == DT_I8 ? 1 : dt ? 2 : 4; }
 // uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
 struct f16_t {
     uint16_t bits;
@@ -214,8 +215,8 @@ __device__ __forceinline__ float f16_widen_hi(unsigned w) { return f16_widen((un
 // fp32 -> binary16 bits, round to nearest even (v_cvt_f16_f32; overflow gives INF, NaN stays NaN)
 __device__ __forceinline__ unsigned f16_narrow(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
 
-// point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16, fp16)
-// aligned row; bf16 and fp16 bits are widened exactly
+// point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16, fp16) /
+// 4-byte (int8) aligned row; bf16 and fp16 bits and int8 values are widened exactly
 __device__ __forceinline__ float pt_ld1(const float *p) { return *p; }
 __device__ __forceinline__ float pt_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
 __device__ __forceinline__ float4 pt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -227,6 +228,24 @@ __device__ __forceinline__ float4 pt_ld4(const uint16_t *p)
     o.y = __uint_as_float(v.x & 0xFFFF0000u);
     o.z = __uint_as_float(v.y << 16);
     o.w = __uint_as_float(v.y & 0xFFFF0000u);
+    return o;
+}
+// int8 points travel as i8_t; every int8 value is exact in fp32
+struct i8_t {
+    int8_t v;
+};
+static_assert(sizeof(i8_t) == 1 && alignof(i8_t) == 1, "i8_t is the raw byte");
+// byte e (0 .. 3) of a 32-bit word as a signed value, widened to fp32 (v_bfe_i32 + v_cvt_f32_i32: exact)
+__device__ __forceinline__ float i8_widen(unsigned w, int e) { return (float)((int)(w << (24 - 8 * e)) >> 24); }
+__device__ __forceinline__ float pt_ld1(const i8_t *p) { return (float)p->v; }
+__device__ __forceinline__ float4 pt_ld4(const i8_t *p)
+{
+    const unsigned v = *reinterpret_cast<const unsigned *>(p);   // 4 int8 of a 4-byte aligned row, widened exactly
+    float4 o;
+    o.x = i8_widen(v, 0);
+    o.y = i8_widen(v, 1);
+    o.z = i8_widen(v, 2);
+    o.w = i8_widen(v, 3);
     return o;
 }
 __device__ __forceinline__ float pt_ld1(const f16_t *p) { return f16_widen(p->bits); }
@@ -435,6 +454,8 @@ __host__ __device__ constexpr int lazy16_gather(int lane, int t, int ks, int par
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
     int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; tau mode 4)
+    int i8;               // 1: int8 points on v_mfma_i32_16x16x64_i8 (OpI8: kt = 256 on the 128-deep bf16 geometry, bf16 = 1
+                          // too; exact integer scores, tau mode 1's margin, filter form 5)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
     int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
@@ -720,12 +741,20 @@ int launch_soa_to_aos(int k, int n, const void *src, void *dst, int esz, hipStre
 int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale,
                            float pad_norm, void *img, float *norms, unsigned *max_norm_bits,
                            unsigned *maxabs_bits, hipStream_t st, bool f16 = false);
+// int8 points: the operand image of v_mfma_i32_16x16x64_i8 at kt = 256 (1 KiB fragment 4 * tile + k-step: lane l holds
+// dims 64 ks + 16 (l >> 4) .. + 15 of point 16 tile + (l & 15)), the VALUES themselves (no scale: -2 v does not fit int8,
+// the filter applies it), zero-padded; norms = the exact integer |v|^2 as fp32 (pad points: pad_norm); max_norm_bits as
+// the bf16 form's.  No max-|v| word: int8 has no value that voids the filter.
+int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img,
+                         float *norms, unsigned *max_norm_bits, hipStream_t st);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
 // split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth
 // f16 (with bf16 = true): fp16 points — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
+// i8 (with bf16 = true): int8 points — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of
+// bytes = a 16x16x32 fragment of bf16: 8 fragments per 32-ref block either way); k > 256: unsupported
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
-                bool split = false, bool split_eager = false, bool f16 = false);
+                bool split = false, bool split_eager = false, bool f16 = false, bool i8 = false);
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,

@@ -740,6 +740,99 @@ int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, con
     return NNS_OK;
 }
 
+// ---- int8 image (the operands of v_mfma_i32_16x16x64_i8) -----------------------------------
+// One workgroup = one block of 32 points at KT = 256: eight 1 KiB fragments, fragment 4 t + ks = 16-point tile t x k-step
+// ks of 64 dims; lane l holds dims 64 ks + 16 (l >> 4) .. + 15 of point 16 t + (l & 15), one operand (4 VGPRs) per
+// ds_read_b128.  The bytes, blocks and fragment order of the 128-deep order-1 bf16 image.  The image holds the VALUES
+// (-2 v does not fit int8: the filter applies the factor), zero-padded to KT; the norms are exact integers <= 2^22,
+// stored as fp32.  int8 has no NaN / INF / huge value: no max-|v| word.
+template <int KT>
+__global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const int8_t *__restrict__ pts, float pad_norm,
+                                                       uint4 *__restrict__ img, float *__restrict__ norms,
+                                                       unsigned *__restrict__ max_norm_bits)
+{
+    constexpr int LD = KT + 16, NKS = KT / 64;   // (rows stay 16-byte aligned)
+    __shared__ __attribute__((aligned(16))) int8_t tile[32 * LD];
+    const int tid = threadIdx.x;
+    const int blk = blockIdx.x;
+    const int p0 = blk * 32;
+    if ((k & 15) == 0 && (((uintptr_t)pts) & 15) == 0) {
+        // sixteen values per load, only the chunks that exist: the block's rows are one contiguous run of 32 k bytes
+        const int kc = k >> 4, nrows = min(32, npts - p0);
+        const uint4 *src = reinterpret_cast<const uint4 *>(pts + (size_t)p0 * k);
+        for (int e = tid; e < nrows * kc; e += 256) {
+            const int i = e / kc, c = e - i * kc;
+            *reinterpret_cast<uint4 *>(&tile[i * LD + 16 * c]) = src[e];
+        }
+        for (int e = tid; e < 32 * (KT / 16); e += 256) {   // zero padding: dims k .. KT - 1, rows past the last point
+            const int i = e / (KT / 16), c = e - i * (KT / 16);
+            if (c >= kc || i >= nrows) *reinterpret_cast<uint4 *>(&tile[i * LD + 16 * c]) = make_uint4(0u, 0u, 0u, 0u);
+        }
+    } else if ((k & 3) == 0 && (((uintptr_t)pts) & 3) == 0) {
+        for (int e = tid; e < 32 * (KT / 4); e += 256) {   // four values per load
+            const int i = e / (KT / 4), t4 = e - i * (KT / 4);
+            unsigned v = 0;
+            if (4 * t4 < k && p0 + i < npts) v = *reinterpret_cast<const unsigned *>(pts + (size_t)(p0 + i) * k + 4 * t4);
+            *reinterpret_cast<unsigned *>(&tile[i * LD + 4 * t4]) = v;
+        }
+    } else {
+        for (int e = tid; e < 32 * KT; e += 256) {
+            const int i = e / KT, t = e - i * KT;
+            int8_t v = 0;
+            if (t < k && p0 + i < npts) v = pts[(size_t)(p0 + i) * k + t];
+            tile[i * LD + t] = v;
+        }
+    }
+    __syncthreads();
+    {
+        // point i = tid >> 3: eight lanes, 32 values each (KT / 4 words strided by 8), summed in int32
+        const int i = tid >> 3, part = tid & 7;
+        int acc = 0;
+        for (int t4 = part; t4 < KT / 4; t4 += 8) {
+            const unsigned w = *reinterpret_cast<const unsigned *>(&tile[i * LD + 4 * t4]);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int v = (int)(w << (24 - 8 * b)) >> 24;
+                acc += v * v;
+            }
+        }
+#pragma unroll
+        for (int off = 4; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        float nv = (float)acc;   // <= 256 * 128^2 = 2^22: exact
+        unsigned nb = 0;
+        if (p0 + i >= npts) nv = pad_norm;
+        else nb = __float_as_uint(nv);
+        if (part == 0) norms[p0 + i] = nv;
+        if (max_norm_bits) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned o = __shfl_xor(nb, off, 64);
+                nb = o > nb ? o : nb;
+            }
+            if ((tid & 63) == 0) max_word(max_norm_bits, nb);
+        }
+    }
+    uint4 *out = img + (size_t)blk * (32 * KT / 16);
+    for (int f = tid; f < (32 * KT / 16); f += 256) {
+        const int s = f >> 6, lane = f & 63;
+        const int t = s / NKS, ks = s % NKS;
+        out[f] = *reinterpret_cast<const uint4 *>(&tile[(16 * t + (lane & 15)) * LD + 64 * ks + 16 * (lane >> 4)]);
+    }
+}
+
+int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img, float *norms,
+                         unsigned *max_norm_bits, hipStream_t st)
+{
+    if (kt != 256 || k > kt) {
+        set_error("prep: unsupported int8 tile K %d (k = %d)", kt, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(image_i8_kernel<256>, dim3(npts_pad / 32), dim3(256), 0, st, k, npts, pts, pad_norm, (uint4 *)img,
+                       norms, max_norm_bits);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
 // ---- SoA -> AoS (NNS_REFS_SOA) --------------------------------------------------------------
 // Tile = 32 dims x 64 points through LDS: reads are 64 consecutive points of one dimension row
 // (256 B / 128 B runs), writes 32 consecutive dims of one point (128 B / 64 B runs).  HBM-bound:

@@ -61,13 +61,16 @@ ABI_SYMBOLS = (
     "nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
     "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
     "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk", "nns_search_f16_range",
+    "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk", "nns_search_i8_range",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
 OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
                     "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
                     "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk",
-                    "nns_search_f16_range")
+                    "nns_search_f16_range",
+                    "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk",
+                    "nns_search_i8_range")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -172,7 +175,12 @@ def _load() -> ctypes.CDLL:
                 "nns_index_search_f16": lib.nns_index_search.argtypes,
                 "nns_search_f16_ex": lib.nns_search_f32_ex.argtypes,
                 "nns_search_f16_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_f16_range": lib.nns_search_f32_range.argtypes}
+                "nns_search_f16_range": lib.nns_search_f32_range.argtypes,
+                "nns_index_create_i8": lib.nns_index_create.argtypes,
+                "nns_index_search_i8": lib.nns_index_search.argtypes,
+                "nns_search_i8_ex": lib.nns_search_f32_ex.argtypes,
+                "nns_search_i8_topk": lib.nns_search_f32_topk.argtypes,
+                "nns_search_i8_range": lib.nns_search_f32_range.argtypes}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -200,7 +208,8 @@ def _check(status: int, where: str) -> None:
 
 def selftest_mfma(a: np.ndarray, b: np.ndarray, c0: np.ndarray, bf16: int = 0) -> np.ndarray:
     """out[i][j] of one 32x32 MFMA tile (diagnostic, see include/nns.h).  bf16: 0 fp32, 1 bf16 32x32x16, 2 bf16
-    16x16x32, 3 the split chain of fp32 values, 5 f16 16x16x32 (the values cast to binary16)."""
+    16x16x32, 3 the split chain of fp32 values, 5 f16 16x16x32 (the values cast to binary16), 6 i8 16x16x64 (the values
+    cast to int8, i32 accumulation seeded with int(c0), returned as fp32; kt a multiple of 64)."""
     a = np.ascontiguousarray(a, np.float32)
     b = np.ascontiguousarray(b, np.float32)
     c0 = np.ascontiguousarray(c0, np.float32)
@@ -251,8 +260,8 @@ def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
 
 
 def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0, schedule: bool = False) -> dict:
-    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  bf16: False / True, or 2 for fp16
-    points (here and in plan_topk / plan_range).  "split": 1 when fp32 points
+    """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  bf16: False / True, 2 for fp16 or 3
+    for int8 points (here and in plan_topk / plan_range).  "split": 1 when fp32 points
     take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0).  schedule=True asks for the
     16th field too, "lazy": 1 when the split operands run the lazy schedule (0 with NNS_FILTER_SPLIT_EAGER)."""
     nf = 16 if schedule else 15
@@ -490,6 +499,35 @@ def search_f16(query_points, reference_points, *, return_distances: bool = False
     return (idx, dist) if return_distances else idx
 
 
+def to_i8(a) -> np.ndarray:
+    """A numpy int8 array as a contiguous 2-D int8 array (other dtypes are refused: nothing is quantised silently)."""
+    a = np.asarray(a)
+    if a.dtype != np.int8:
+        raise ValueError("int8 point sets must be numpy int8 arrays")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("int8 point sets must be 2-D arrays")
+    return a
+
+
+def search_i8(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
+              path: str = "auto", device: int = 0):
+    """search() for int8 point sets (numpy int8) [points][k]: V0's arithmetic on the values widened exactly to fp32
+    (nns_search_i8_ex).  For k <= 256 the distances are the exact integer squared distances."""
+    q = to_i8(query_points)
+    r = to_i8(reference_points)
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("query and reference dimensionality differ")
+    m, k = q.shape
+    n = r.shape[0]
+    idx = np.empty(m, dtype=np.int32)
+    dist = np.empty(m, dtype=np.float32) if return_distances else None
+    _check(lib.nns_search_i8_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
+                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
+           "nns_search_i8_ex")
+    return (idx, dist) if return_distances else idx
+
+
 def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa, topk_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
@@ -497,7 +535,8 @@ def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_so
     n = r.shape[1] if refs_soa else r.shape[0]
     idx = np.empty((m, max(kn, 0)), dtype=np.int32)
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
-    fn = lib.nns_search_f16_topk if bf16 == 2 else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
+    fn = lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
+        else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
               shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
            "nns_search_topk")
@@ -533,6 +572,12 @@ def search_topk_f16(query_points, reference_points, kn: int, *, return_distances
                         device, refs_soa)
 
 
+def search_topk_i8(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
+                   path: str = "auto", device: int = 0):
+    """search_topk() for int8 point sets (numpy int8; nns_search_i8_topk)."""
+    return _search_topk(to_i8(query_points), to_i8(reference_points), kn, 3, return_distances, shards, path, device, False)
+
+
 def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
@@ -541,7 +586,8 @@ def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa,
     lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
     pidx = ctypes.POINTER(ctypes.c_int)()
     pdist = ctypes.POINTER(ctypes.c_float)()
-    fn = lib.nns_search_f16_range if bf16 == 2 else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
+    fn = lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
+        else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
               ctypes.byref(pdist) if return_distances else None,
               _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_RANGE_MFMA if range_mfma else 0),
@@ -588,6 +634,12 @@ def search_range_f16(query_points, reference_points, radius2: float, *, return_d
                          device, refs_soa)
 
 
+def search_range_i8(query_points, reference_points, radius2: float, *, return_distances: bool = False,
+                    path: str = "auto", device: int = 0):
+    """search_range() for int8 point sets (numpy int8; nns_search_i8_range)."""
+    return _search_range(to_i8(query_points), to_i8(reference_points), radius2, 3, return_distances, path, device, False)
+
+
 # ---------------------------------------------------------------------------
 # device-resident API (torch tensors are only the owners of device memory)
 # ---------------------------------------------------------------------------
@@ -616,11 +668,12 @@ class Index:
         range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA).
         topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA)."""
         import torch
-        if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16) or refs.dim() != 2 \
+        if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int8) or refs.dim() != 2 \
                 or not refs.is_contiguous() or not refs.is_cuda:
-            raise ValueError("refs must be a contiguous fp32, bf16 or fp16 [n][k] tensor on a HIP device")
+            raise ValueError("refs must be a contiguous fp32, bf16, fp16 or int8 [n][k] tensor on a HIP device")
         self.bf16 = refs.dtype == torch.bfloat16
         self.f16 = refs.dtype == torch.float16
+        self.i8 = refs.dtype == torch.int8
         self.refs = refs  # keep alive: the index reads the original values
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
         self.device = refs.device.index or 0
@@ -630,7 +683,8 @@ class Index:
             | (NNS_TOPK_MFMA if topk_mfma else 0)
         self.flags = flags
         h = ctypes.c_void_p()
-        create = lib.nns_index_create_f16 if self.f16 else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
+        create = lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
+            else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
         self._h = h
@@ -648,7 +702,8 @@ class Index:
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
-        fn = lib.nns_index_search_f16 if self.f16 else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
+        fn = lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
+            else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
         _check(fn(self._h, m, queries.data_ptr(), keys.data_ptr(), _stream_ptr(stream)), "nns_index_search")
         return keys
 
@@ -759,11 +814,12 @@ class Index:
         _check(lib.nns_index_stats(self._h, ctypes.byref(st)), "nns_index_stats")
         d = st.asdict()
         # the filter's operand form the index uses: "split" (split-bf16, fp32 points by default), "fp32"
-        # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16), "f16" (fp16 points);
+        # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16), "f16" (fp16 points),
+        # "i8" (int8 points);
         # None: exact path
         form = ctypes.c_int(-1)
         _check(lib.nns_index_filter_form(self._h, ctypes.byref(form)), "nns_index_filter_form")
-        d["filter_form"] = {-1: None, 0: "fp32", 1: "bf16", 2: "bf16", 3: "split", 4: "f16"}[form.value]
+        d["filter_form"] = {-1: None, 0: "fp32", 1: "bf16", 2: "bf16", 3: "split", 4: "f16", 5: "i8"}[form.value]
         return d
 
     def near_ties(self) -> np.ndarray:
