@@ -315,11 +315,44 @@ int nns_search_i8_ex(int k, int m, int n, const int8_t *s_points,
                      const int8_t *r_points, int *idx_out, float *dist_out,
                      int num_shards, unsigned flags, int device);
 
+/* Binary points ("b1": ORB / BRIEF descriptors, 1-bit quantised embeddings) under Hamming distance.  dtype code 4 (the
+ * bf16_points argument of nns_plan_topk / nns_plan_range).
+ * Storage: a point of k bits is k / 32 consecutive uint32_t words, 4-byte aligned; bit t of a point is
+ * (word[t / 32] >> (t % 32)) & 1 — on a little-endian host numpy.packbits(..., bitorder="little").  Layout
+ * [points][k / 32], row-major.  k is the number of BITS in every entry point and plan call.
+ * Limits: k % 32 != 0: NNS_ERR_UNSUPPORTED (pad both sets with zero bits: no distance changes).  k / 32 > 16384:
+ * NNS_ERR_UNSUPPORTED (the exact path's own limit, applied to words).  A point set that is not 4-byte aligned:
+ * NNS_ERR_INVALID.
+ * Semantics: the int8 contract with one word changed — V0's arithmetic on the bits widened to 0.0 / 1.0.  Every term
+ * fl(fl(q - r)^2) is then 0 or 1 and every partial sum an integer <= k <= 2^19 < 2^24, so V0's distance IS
+ * popcount(q xor r), the Hamming distance, as fp32: indices bit-exact, distances bit-equal, lowest index wins ties, index
+ * 0 when nothing is selectable.  nns_stats.nonfinite is always 0; there is NO void or guard condition.  An index and
+ * its queries must have the same dtype: any mix with the fp32 / bf16 / fp16 / int8 entry points returns
+ * NNS_ERR_INVALID, in both directions.  The dtype-agnostic entry points (nns_index_search_indices,
+ * nns_index_search_topk, nns_index_range_count / nns_index_range_fill, nns_index_refresh, nns_index_stats,
+ * nns_index_near_ties — count 0 —, nns_index_topk_info / nns_index_range_info) serve a b1 index like any other, q_dev
+ * in the index's dtype.
+ * Path: there is no MFMA filter: always NNS_PATH_EXACT, nns_index_filter_form reports -1.  The lane-per-ref scans
+ * (K1b, K6, K7) run one xor and one accumulating popcount per 32-bit word.
+ * Flags: NNS_PATH_AUTO / NNS_PATH_EXACT, NNS_PROFILE.  NNS_PATH_MFMA, NNS_RANGE_MFMA, NNS_TOPK_MFMA, NNS_REFS_SOA and
+ * NNS_RECORDS_PER_REF: NNS_ERR_UNSUPPORTED.  NNS_FILTER_BF16, NNS_FILTER_F32 and NNS_FILTER_SPLIT_EAGER:
+ * NNS_ERR_INVALID.  All of these, like the limits on k and the alignment, are answered before the device is looked up.
+ * nns_search_*_multi is not extended to binary points.
+ * Times (tools/probe_b1.py, profiles/b1_probe.json): see README. */
+int nns_index_create_b1(nns_index **out, int device, int k, int n,
+                        const uint32_t *r_dev, int64_t index_base,
+                        unsigned flags, void *stream);
+int nns_index_search_b1(nns_index *ix, int m, const uint32_t *q_dev,
+                        nns_key *keys_dev, void *stream);
+int nns_search_b1_ex(int k, int m, int n, const uint32_t *s_points,
+                     const uint32_t *r_points, int *idx_out, float *dist_out,
+                     int num_shards, unsigned flags, int device);
+
 /* nns_index_search + nns_keys_unpack in one call for the single-shard case (what the reference's
  * cudaCall hands back is indices): keys_dev[m] as above AND idx_dev[m] = index of each key (0 for
  * NNS_KEY_NONE, as V0), dist_dev (optional) = its fp32 distance.  The low-dimensional exact kernel
  * writes all three in its one launch; the other paths append the unpack kernel.  q_dev has the
- * index's dtype (fp32, bf16 / fp16 bit patterns, or int8). */
+ * index's dtype (fp32, bf16 / fp16 bit patterns, int8, or packed bits). */
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev,
                              int *idx_dev, float *dist_dev, void *stream);
 
@@ -379,10 +412,15 @@ int nns_search_f16_topk(int k, int m, int n, const uint16_t *s_points, const uin
 /* int8 points: the same call; NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_i8_topk(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int kn,
                        int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
+/* binary points (k in bits, packed words): the same call; every flag but the auto / exact path and NNS_PROFILE:
+ * see nns_index_create_b1. */
+int nns_search_b1_topk(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the top-K launch geometry for a k-D search of m queries over n refs.
  * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
  * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points (the narrow types share
- * one geometry: their refs are widened as they are read). */
+ * one geometry: their refs are widened as they are read), 4 binary points: k is in bits, and the LDS and workspace fields
+ * follow k / 32 words of 4 bytes (k % 32 != 0 or k / 32 > 16384: NNS_ERR_UNSUPPORTED). */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
 
 /* ---- top-K on the matrix cores (NNS_TOPK_MFMA, K6m) -------------------------------
@@ -465,9 +503,13 @@ int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const ui
 /* int8 points: the same call; NNS_RANGE_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, float radius2,
                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+/* binary points (k in bits, packed words; radius2 is compared with the Hamming distance as fp32): the same call. */
+int nns_search_b1_range(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the range search's launch geometry for a k-D search of m queries over n
  * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
- * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points. */
+ * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points, 4 binary points (k in bits; the
+ * fields follow k / 32 words, as in nns_plan_topk). */
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
 
 /* ---- range search on the matrix cores (NNS_RANGE_MFMA, K7m) ------------------------
@@ -561,7 +603,8 @@ int nns_filter_lazy_tile(void);
  * bf16_points: 0 fp32, 1 bf16, 2 fp16 points.  fp16 points plan as bf16 points do, field for field, at 32 <= k <= 256;
  * k > 256, NNS_RANGE_MFMA or NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED; the operand flags: NNS_ERR_INVALID.
  * 3 int8 points: kt = 256 for every k <= 256, every other field the bf16 plan's at a 128-deep tile (k <= 128) — the
- * int8 block has that tile's bytes and fragments; rejections as for fp16 points, NNS_REFS_SOA with them. */
+ * int8 block has that tile's bytes and fragments; rejections as for fp16 points, NNS_REFS_SOA with them.
+ * 4 binary points: NNS_ERR_UNSUPPORTED (no filter is built for them). */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f
@@ -620,7 +663,8 @@ const char *nns_last_error(void); /* thread-local detail of the last failure */
 int nns_version(void);            /* major * 1000 + minor */
 /* Explicit replacement for the reference's hidden WarmUP static (ten V9 calls before main(),
  * core.cu:1900-1933): runs one tiny search through every kernel family (exact lane-per-query and
- * lane-per-ref, every fp32, bf16 and fp16 tile depth of the MFMA filter and the int8 tile) on `device`, so that
+ * lane-per-ref, every fp32, bf16 and fp16 tile depth of the MFMA filter, the int8 tile and the Hamming scan of binary
+ * points) on `device`, so that
  * code-object loading, the filter's LDS opt-in and the first pool allocations are paid here and
  * not inside a timed call.  Optional: every entry point works without it. */
 int nns_warmup(int device);

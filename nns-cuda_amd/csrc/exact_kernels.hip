@@ -1109,12 +1109,12 @@ __global__ __launch_bounds__(256) void exact_lane_ref_kernel(
         for (int e = tid; e < QT * k; e += 256) {
             const int u = e / k, t = e - u * k;
             const int qslot = g * QT + u;
-            float v = 0.0f;
+            tile_word_t<T> v = 0;   // (b1_t: the raw word, moved as unsigned)
             if (qslot < nq) {
                 const int qi = qlist ? qlist[qslot] : qslot;
                 v = pt_ld1(q + (size_t)qi * k + t);
             }
-            sq[e] = v;
+            reinterpret_cast<tile_word_t<T> *>(sq)[e] = v;
         }
         __syncthreads();
 
@@ -1222,12 +1222,12 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
         for (int e = tid; e < QT * k; e += 256) {
             const int u = e / k, t = e - u * k;
             const int qslot = g * QT + u;
-            float v = 0.0f;
+            tile_word_t<T> v = 0;   // (b1_t: the raw word, moved as unsigned)
             if (qslot < nq) {
                 const int qi = qlist ? qlist[qslot] : qslot;
                 v = pt_ld1(q + (size_t)qi * k + t);
             }
-            sq[e] = v;
+            reinterpret_cast<tile_word_t<T> *>(sq)[e] = v;
         }
         __syncthreads();
 
@@ -1242,9 +1242,9 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
         const int wave_global = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
         for (int64_t row0l = (int64_t)wave_global * 64; row0l < n; row0l += (int64_t)nwaves * 64) {   // (64-bit: see above)
             const int row0 = (int)row0l;
-            float sum[QT];
+            tile_word_t<T> sum[QT];   // (b1_t: the integer Hamming count, converted once at the end)
 #pragma unroll
-            for (int u = 0; u < QT; ++u) sum[u] = 0.0f;
+            for (int u = 0; u < QT; ++u) sum[u] = 0;
             const int j = row0 + lane;
             // load mapping: cpr chunks per row per step (8, or fewer for short rows); instruction i
             // covers rows rpi*i .. rpi*i + rpi-1, lane -> (row rpi*i + lane/cpr, chunk lane%cpr), so a
@@ -1273,6 +1273,16 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
                 __builtin_amdgcn_wave_barrier();
                 const int nc = (kc - c0) < cpr ? (kc - c0) : cpr;
                 for (int ch = 0; ch < nc; ++ch) {
+                    if constexpr (std::is_same_v<T, b1_t>) {   // 4 words: xor + popcount per word (v0_lane_chains' b1_t form)
+                        const uint4 rw = *reinterpret_cast<const uint4 *>(mytile + lane * ROWB + ch * 16);
+                        const unsigned *sw = reinterpret_cast<const unsigned *>(sq);
+#pragma unroll
+                        for (int u = 0; u < QT; ++u) {
+                            const uint4 qv = *reinterpret_cast<const uint4 *>(&sw[u * k + (c0 + ch) * 4]);   // broadcast
+                            sum[u] = popc_add(qv.w ^ rw.w, popc_add(qv.z ^ rw.z, popc_add(qv.y ^ rw.y, popc_add(qv.x ^ rw.x, sum[u]))));
+                        }
+                        continue;
+                    }
                     const float4 raw = *reinterpret_cast<const float4 *>(mytile + lane * ROWB + ch * 16);
                     float rv[EPC];
                     if constexpr (EPC == 4) widen4(raw, nullptr, reinterpret_cast<float (&)[4]>(rv));
@@ -1299,11 +1309,13 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
             }
             if (j < n) {
 #pragma unroll
-                for (int u = 0; u < QT; ++u)
-                    if (best[u] > sum[u]) {   // strict: first (lowest j) minimum of this lane
-                        best[u] = sum[u];
+                for (int u = 0; u < QT; ++u) {
+                    const float d = (float)sum[u];   // (b1_t: exact, the count is below 2^24)
+                    if (best[u] > d) {   // strict: first (lowest j) minimum of this lane
+                        best[u] = d;
                         bidx[u] = j;
                     }
+                }
             }
         }
 #pragma unroll
@@ -1750,7 +1762,9 @@ int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, 
         return launch_k1c(p, k, m, n, (const float *)q, (const float *)r, index_base, keys, ws, ws_fresh, idx_out,
                           dist_out, st);
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    if (bf16 == DT_I8)
+    if (bf16 == DT_B1)
+        NNS_TRY(launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, nullptr, nullptr, m, index_base, keys, st));
+    else if (bf16 == DT_I8)
         NNS_TRY(launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, nullptr, nullptr, m, index_base, keys, st));
     else if (bf16 == DT_F16)
         NNS_TRY(launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, nullptr, nullptr, m, index_base, keys, st));
@@ -1773,6 +1787,7 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
     // batch both keep ~2048 workgroups busy.
     ExactPlan p{};
     k1b_plan(k, n, max_listed, 8, &p);
+    if (bf16 == DT_B1) return launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16 == DT_I8) return launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16 == DT_F16) return launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);

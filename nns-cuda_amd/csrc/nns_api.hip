@@ -75,10 +75,10 @@ struct nns_index {
     int64_t base = 0;
     unsigned flags = 0;
     int path = NNS_PATH_EXACT;
-    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k], or int8 [n][k]
+    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k], or int8 [n][k], or packed bits [n][k] (k words)
     const void *r_soa = nullptr;   // NNS_REFS_SOA: the caller's [k][n] array; r_dev is then r_own
     void *r_own = nullptr;         // owned point-major copy of r_soa
-    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8
+    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8, DT_B1 (k then counts 32-bit words)
     bool profile = false;
     bool refs_bad = false;
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
@@ -327,6 +327,39 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     return NNS_OK;
 }
 
+// Binary points: the entry points take k in bits; below them the dimension is kw = k / 32 words of 4 bytes (DT_B1).
+// What binary points do not take, answered before the device is looked up: a bit count that is not whole words or is
+// beyond the exact path's tile (in words), a point set that is not word-aligned, every flag but the auto / exact path
+// and profiling.  k <= 0 passes through (*kw = k): the callee's own argument check answers it.
+static int b1_enter(const char *where, int k, unsigned flags, const void *p0, const void *p1, int *kw)
+{
+    *kw = k;
+    if (k <= 0) return NNS_OK;
+    if (k % 32 != 0) {
+        set_error("%s: binary points hold whole 32-bit words: k = %d bits is not a multiple of 32 (pad both sets with zeros)", where, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    *kw = k / 32;
+    if (*kw > 16384) {
+        set_error("%s: k = %d bits exceeds the LDS query tile (k / 32 <= 16384 words)", where, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if (((uintptr_t)p0 | (uintptr_t)p1) & 3) {
+        set_error("%s: binary point sets must be 4-byte aligned", where);
+        return NNS_ERR_INVALID;
+    }
+    if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
+        set_error("%s: the operand flags apply to fp32 points (flags 0x%x)", where, flags);
+        return NNS_ERR_INVALID;
+    }
+    if ((flags & NNS_PATH_MASK) == NNS_PATH_MFMA ||
+        (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA | NNS_REFS_SOA | NNS_RECORDS_PER_REF))) {
+        set_error("%s: no MFMA filter, flag pass or dimension-major form is built for binary points (flags 0x%x)", where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
 static int index_create_impl(nns_index **out, int device, int k, int n, const void *r_dev, int bf16,
                              int64_t index_base, unsigned flags, void *stream)
 {
@@ -407,6 +440,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     // are at least 128 deep, so they only pay from k = 32
     const int kmin = bf16 ? 32 : 8;
     if (path == NNS_PATH_AUTO) path = (k >= (ix->mixed ? 32 : kmin) && k <= kmax) ? NNS_PATH_MFMA : NNS_PATH_EXACT;
+    if (bf16 == DT_B1) path = NNS_PATH_EXACT;   // (no filter for binary points; b1_enter has refused NNS_PATH_MFMA)
     if (path == NNS_PATH_MFMA && k > kmax) {
         set_error("NNS_PATH_MFMA: k = %d > %d is not tiled (use NNS_PATH_AUTO/EXACT)", k, kmax);
         delete ix;   // nothing allocated or enqueued yet
@@ -508,6 +542,15 @@ int nns_index_create_i8(nns_index **out, int device, int k, int n, const int8_t 
     return index_create_impl(out, device, k, n, r_dev, DT_I8, index_base, flags & ~kCreateNoSync, stream);
 }
 
+int nns_index_create_b1(nns_index **out, int device, int k, int n, const uint32_t *r_dev,
+                        int64_t index_base, unsigned flags, void *stream)
+{
+    int kw = 0;
+    NNS_TRY(b1_enter("nns_index_create_b1", k, flags & ~kCreateNoSync, r_dev, nullptr, &kw));
+    DeviceScope keep_device;
+    return index_create_impl(out, device, kw, n, r_dev, DT_B1, index_base, flags & ~kCreateNoSync, stream);
+}
+
 int nns_index_refresh(nns_index *ix, void *stream)
 {
     if (!ix) return NNS_ERR_INVALID;
@@ -596,6 +639,16 @@ static void end_pass(nns_index *ix, int m, int path, int first, hipStream_t st)
     if (ix->ev_count < kEvRing) ++ix->ev_count;
 }
 
+// the queries of a binary-point index are words: 4-byte aligned, like its refs (nns_index_create_b1)
+static int check_b1_queries(const char *where, const nns_index *ix, const void *q_dev)
+{
+    if (ix && ix->bf16 == DT_B1 && ((uintptr_t)q_dev & 3)) {
+        set_error("%s: the queries of a binary-point index must be 4-byte aligned", where);
+        return NNS_ERR_INVALID;
+    }
+    return NNS_OK;
+}
+
 extern "C++" {
 // grow an index-owned workspace to `need` elements (the old block may still be read by an earlier pass of this index:
 // back to the pool behind an event); false: the allocation failed, the index holds no workspace
@@ -629,7 +682,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
 {
     if (ix && ix->bf16 != bf16) {
         set_error("nns_index_search: query dtype does not match the index (%s index)",
-                  ix->bf16 == DT_I8 ? "int8" : ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
+                  ix->bf16 == DT_B1 ? "binary" : ix->bf16 == DT_I8 ? "int8" : ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
         return NNS_ERR_INVALID;
     }
     if (!ix || !q_dev || !keys_dev || m <= 0) {
@@ -640,6 +693,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
         set_error("nns_index_search: m = %d exceeds NNS_MAX_POINTS (%d)", m, kMaxPoints);
         return NNS_ERR_INVALID;
     }
+    NNS_TRY(check_b1_queries("nns_index_search", ix, q_dev));
     NNS_TRY(ensure_device_ok(ix->device));
     hipStream_t st = (hipStream_t)stream;
     const bool prof = ix->profile;
@@ -732,6 +786,12 @@ int nns_index_search_i8(nns_index *ix, int m, const int8_t *q_dev, nns_key *keys
     return index_search_impl(ix, m, q_dev, DT_I8, keys_dev, stream);
 }
 
+int nns_index_search_b1(nns_index *ix, int m, const uint32_t *q_dev, nns_key *keys_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_search_impl(ix, m, q_dev, DT_B1, keys_dev, stream);
+}
+
 int nns_index_search_indices(nns_index *ix, int m, const void *q_dev, nns_key *keys_dev, int *idx_dev,
                              float *dist_dev, void *stream)
 {
@@ -819,6 +879,7 @@ static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int k
         set_error("nns_index_search_topk: m = %d exceeds NNS_MAX_POINTS (%d)", m, kMaxPoints);
         return NNS_ERR_INVALID;
     }
+    NNS_TRY(check_b1_queries("nns_index_search_topk", ix, q_dev));
     TopkPlan p{};
     NNS_TRY(topk_plan(ix->k, m, ix->n, kn, &p));
     NNS_TRY(ensure_device_ok(ix->device));
@@ -869,8 +930,10 @@ int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, f
 
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read)
+    // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read; binary points (4): k bits are
+    //  k / 32 words of 4 bytes)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    if (bf16_points == DT_B1) NNS_TRY(b1_enter("nns_plan_topk", k, 0, nullptr, nullptr, &k));
     NNS_TRY(topk_check_kn("nns_plan_topk", kn));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
     TopkPlan p{};
@@ -951,7 +1014,7 @@ static int range_check_split(const char *where, nns_index *ix, int m, const void
         set_error("%s: m = %d exceeds NNS_MAX_POINTS (%d)", where, m, kMaxPoints);
         return NNS_ERR_INVALID;
     }
-    return NNS_OK;
+    return check_b1_queries(where, ix, q_dev);
 }
 
 // ---- K7m: the filtered passes of an NNS_RANGE_MFMA index ---------------------------------------------------------
@@ -1118,8 +1181,10 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
 {
-    (void)bf16_points;   // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read)
+    // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read; binary points (4): k bits are
+    //  k / 32 words of 4 bytes)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
+    if (bf16_points == DT_B1) NNS_TRY(b1_enter("nns_plan_range", k, 0, nullptr, nullptr, &k));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
     RangePlan p{};
     NNS_TRY(range_plan(k, m, n, &p));
@@ -1544,6 +1609,10 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
         set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags are not built for fp16 points (flags 0x%x)", flags);
         return NNS_ERR_UNSUPPORTED;
     }
+    if (bf16_points == DT_B1) {
+        set_error("nns_plan_filter: no MFMA filter is built for binary points");
+        return NNS_ERR_UNSUPPORTED;
+    }
     if (bf16_points == DT_I8 && (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA | NNS_REFS_SOA))) {
         set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points (flags 0x%x)", flags);
         return NNS_ERR_UNSUPPORTED;
@@ -1662,6 +1731,7 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
 {
     if (flags & (NNS_REFS_SOA | NNS_PROFILE)) return false;
     if (rbytes < kChunkMinBytes || n < 4096 || m < kTinyM) return false;
+    if (bf16 == DT_B1) return false;   // (binary points: the rates below are not theirs; the plain path)
     const unsigned path = flags & NNS_PATH_MASK;
     const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > ((bf16 == DT_F16 || bf16 == DT_I8) ? 256 : kMaxFilterK);
     double est_s;
@@ -1895,7 +1965,7 @@ static int check_exact_only_flags(const char *where, const char *what, unsigned 
 static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
                                  int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
-    const char *where = bf16 == DT_I8 ? "nns_search_i8_topk" : bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
+    const char *where = bf16 == DT_B1 ? "nns_search_b1_topk" : bf16 == DT_I8 ? "nns_search_i8_topk" : bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, idx_out));
     NNS_TRY(check_i8_flags(where, bf16, flags));
     NNS_TRY(topk_check_kn(where, kn));
@@ -1975,7 +2045,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
                                   float radius2, int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags,
                                   int device)
 {
-    const char *where = bf16 == DT_I8 ? "nns_search_i8_range" : bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
+    const char *where = bf16 == DT_B1 ? "nns_search_b1_range" : bf16 == DT_I8 ? "nns_search_i8_range" : bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
     if (idx_out) *idx_out = nullptr;
     if (dist_out) *dist_out = nullptr;
     if (!idx_out) {
@@ -2033,6 +2103,32 @@ int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_
     return search_range_host_impl(k, m, n, s_points, r_points, DT_I8, radius2, lims_out, idx_out, dist_out, flags, device);
 }
 
+int nns_search_b1_range(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    if (idx_out) *idx_out = nullptr;
+    if (dist_out) *dist_out = nullptr;
+    int kw = 0;
+    NNS_TRY(b1_enter("nns_search_b1_range", k, flags, s_points, r_points, &kw));
+    return search_range_host_impl(kw, m, n, s_points, r_points, DT_B1, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_b1_ex(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, int *idx_out,
+                     float *dist_out, int num_shards, unsigned flags, int device)
+{
+    int kw = 0;
+    NNS_TRY(b1_enter("nns_search_b1_ex", k, flags, s_points, r_points, &kw));
+    return search_host_impl(kw, m, n, s_points, r_points, DT_B1, idx_out, dist_out, num_shards, flags, device);
+}
+
+int nns_search_b1_topk(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    int kw = 0;
+    NNS_TRY(b1_enter("nns_search_b1_topk", k, flags, s_points, r_points, &kw));
+    return search_topk_host_impl(kw, m, n, s_points, r_points, DT_B1, kn, idx_out, dist_out, num_shards, flags, device);
+}
+
 int nns_search_i8_ex(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int *idx_out,
                      float *dist_out, int num_shards, unsigned flags, int device)
 {
@@ -2088,7 +2184,8 @@ int nns_warmup(int device)
     // (k, m, n, bf16, path): K1a (3-D and 16-D), K1b, the fp32 tile depths 16 / 32 / 64 / 128 / 256 (forced onto the
     // filter: AUTO keeps a 64 x 512 x 16 problem on the exact kernel), the bf16-operand tiles for fp32 points (512 /
     // 384 / 512 / 640 / 768 / 1024: AUTO), the bf16 tiles 128 / 256 / 384 / 512 / 640 / 768 / 1024, the fp16 tiles 128 / 256
-    // (dtype 2), the int8 tile (dtype 3: v_mfma_i32_16x16x64_i8, 256-deep)
+    // (dtype 2), the int8 tile (dtype 3: v_mfma_i32_16x16x64_i8, 256-deep), binary points (dtype 4: k = 8 words, K1b's
+    // Hamming scan)
     static const int shapes[][5] = {{3, 64, 512, 0, NNS_PATH_AUTO},    {16, 64, 512, 0, NNS_PATH_AUTO},  {16, 1, 512, 0, NNS_PATH_AUTO},
                                     {16, 64, 512, 0, NNS_PATH_MFMA},   {24, 64, 512, 0, NNS_PATH_MFMA},  {40, 64, 512, 0, NNS_PATH_MFMA},
                                     {100, 64, 512, 0, NNS_PATH_MFMA},  {200, 64, 512, 0, NNS_PATH_MFMA}, {300, 64, 512, 0, NNS_PATH_AUTO},
@@ -2097,7 +2194,7 @@ int nns_warmup(int device)
                                     {64, 64, 512, 1, NNS_PATH_MFMA},   {200, 64, 512, 1, NNS_PATH_MFMA}, {300, 64, 512, 1, NNS_PATH_MFMA},
                                     {600, 64, 512, 1, NNS_PATH_MFMA},  {700, 64, 512, 1, NNS_PATH_MFMA}, {800, 64, 512, 1, NNS_PATH_MFMA},
                                     {64, 64, 512, 2, NNS_PATH_MFMA},   {200, 64, 512, 2, NNS_PATH_MFMA},
-                                    {64, 64, 512, DT_I8, NNS_PATH_MFMA}};
+                                    {64, 64, 512, DT_I8, NNS_PATH_MFMA}, {8, 64, 512, DT_B1, NNS_PATH_AUTO}};
     const int kmax = 800, mmax = 64, nmax = 512;
     float *q = (float *)malloc(sizeof(float) * kmax * mmax), *r = (float *)malloc(sizeof(float) * kmax * nmax);
     int *idx = (int *)malloc(sizeof(int) * mmax);
@@ -2112,7 +2209,10 @@ int nns_warmup(int device)
     for (int i = 0; i < kmax * nmax; ++i) r[i] = (float)((x = x * 1664525u + 1013904223u) >> 8) * (1.0f / 16777216.0f);
     int rc = NNS_OK;
     for (const auto &sh : shapes) {
-        if (sh[3] == DT_I8) {
+        if (sh[3] == DT_B1) {
+            // the same numbers' fp32 bit patterns as words (q and r hold at least sh[0] * sh[1] and sh[0] * sh[2] floats)
+            rc = search_host_impl(sh[0], sh[1], sh[2], q, r, DT_B1, idx, nullptr, 1, (unsigned)sh[4], device);
+        } else if (sh[3] == DT_I8) {
             // the same numbers (in [0, 1)) as int8 values -128 .. 127
             int8_t *qb = (int8_t *)malloc((size_t)sh[0] * sh[1]);
             int8_t *rb = (int8_t *)malloc((size_t)sh[0] * sh[2]);

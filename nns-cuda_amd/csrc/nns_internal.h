@@ -67,7 +67,8 @@ struct DeviceScope {
 int order_after_default_stream(hipStream_t st);
 void stager_release();         // free the small whole calls' pinned scratch (nns_api.hip)
 // the overlapped upload of a contiguous host ref range (nns_api.hip), shared with nns_search_*_multi's shards
-// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16, DT_F16 or DT_I8)
+// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8 or DT_B1; for DT_B1
+//  `k` is in 32-bit words everywhere below the C-ABI entry points)
 bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes);
 int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
                             int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp);
@@ -200,9 +201,10 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
 
 // ---- point element types ------------------------------------------------------------------------------------------
 // The dtype of an index and of its queries, the `int bf16` argument of the launchers: fp32, bf16 bit patterns, IEEE
-// binary16 (fp16) bit patterns, int8 values.  Element size: dt_size(dtype).
-enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3 };
-inline size_t dt_size(int dt) { return dt == DT_I8 ? 1 : dt ? 2 : 4; }
+// binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word, the dimension counts words).
+// Element size: dt_size(dtype).
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4 };
+inline size_t dt_size(int dt) { return dt == DT_I8 ? 1 : dt == DT_B1 ? 4 : dt ? 2 : 4; }
 // uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
 struct f16_t {
     uint16_t bits;
@@ -260,6 +262,20 @@ __device__ __forceinline__ float4 pt_ld4(const f16_t *p)
     return o;
 }
 
+// binary points travel as b1_t: one raw word of 32 bits, bit t of a point = (word[t / 32] >> (t % 32)) & 1.  A word is
+// never widened: the scans move it as `unsigned` (tile_word_t, v0_lane_chains' b1_t overload)
+struct b1_t {
+    uint32_t w;
+};
+static_assert(sizeof(b1_t) == 4 && alignof(b1_t) == 4, "b1_t is the raw 32-bit word");
+
+__device__ __forceinline__ unsigned pt_ld1(const b1_t *p) { return p->w; }
+// The element type of the LDS query tile of a lane-per-ref scan: the widened fp32 value, or for b1_t the raw word.  The
+// tile is declared float for every point type; a b1_t tile is written and read as unsigned only (a float move may
+// canonicalise a word that happens to be a NaN pattern)
+template <typename T>
+using tile_word_t = std::conditional_t<std::is_same_v<T, b1_t>, unsigned, float>;
+
 // ---- the lane-per-ref scan core (K1b, K6, K7) ----------------------------------------------------------------------
 // One lane holds one ref row rj; the fp32 query tile sq[QT][k] sits in LDS and is read by broadcast.  sum[u] = V0's
 // distance of query u to the ref: one t-ascending v0_step chain per query (VEC 4: a float4 of the row per step, k % 4 == 0
@@ -293,18 +309,65 @@ __device__ __forceinline__ void v0_lane_chains(int k, const float *sq, const T *
     }
 }
 
+// The same scan for binary points (b1_t): k counts 32-bit words, sq holds the QT query rows as raw words.  V0's distance
+// of 0 / 1 values is the Hamming distance (every term fl(fl(q - r)^2) is 0 or 1, every partial sum an integer below
+// 2^24: k <= 16384 words = 2^19 bits), so per word one xor and one popcount that adds into an integer accumulator
+// (v_xor_b32 + v_bcnt_u32_b32), and one exact v_cvt_f32_u32 per (query, ref) at the end.  VEC 4: 16 bytes of the ref
+// row per step (k % 4 == 0, rows 16-byte aligned), the query words by one broadcast ds_read_b128; VEC 1: one word.
+// acc + popcount(x) in the one instruction that does both.  Spelled as asm: from `acc += __popc(x)` the compiler (ROCm 7.2)
+// reassociates the sums of a step into popcounts onto 0 plus v_add3_u32, 2.5 instead of 2 instructions per word.
+__device__ __forceinline__ unsigned popc_add(unsigned x, unsigned acc)
+{
+    unsigned out;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(out) : "v"(x), "v"(acc));
+    return out;
+}
+
+template <int QT, int VEC, int UNROLL>
+__device__ __forceinline__ void v0_lane_chains(int k, const float *sq, const b1_t *rj, float (&sum)[QT])
+{
+    const unsigned *sw = reinterpret_cast<const unsigned *>(sq);
+    unsigned acc[QT];
+#pragma unroll
+    for (int u = 0; u < QT; ++u) acc[u] = 0u;
+    if (VEC == 4) {
+        for (int t = 0; t < k; t += 4) {
+            const uint4 rv = *reinterpret_cast<const uint4 *>(rj + t);
+#pragma unroll
+            for (int u = 0; u < QT; ++u) {
+                const uint4 qv = *reinterpret_cast<const uint4 *>(&sw[u * k + t]);   // broadcast
+                unsigned a = acc[u];
+                a = popc_add(qv.x ^ rv.x, a);
+                a = popc_add(qv.y ^ rv.y, a);
+                a = popc_add(qv.z ^ rv.z, a);
+                a = popc_add(qv.w ^ rv.w, a);
+                acc[u] = a;
+            }
+        }
+    } else {
+#pragma unroll UNROLL
+        for (int t = 0; t < k; ++t) {
+            const unsigned rv = rj[t].w;
+#pragma unroll
+            for (int u = 0; u < QT; ++u) acc[u] += __popc(sw[u * k + t] ^ rv);   // (plain C: an asm statement keeps the loop from unrolling)
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < QT; ++u) sum[u] = (float)acc[u];
+}
+
 // K6 / K7's VEC 1 unroll: what the compiler chose for their loops before they shared v0_lane_chains (through the
 // helper it left QT = 16 rolled, 10 % slower at k = 3).  K1b's grid-stride scan passes 1: it was never unrolled.
 template <int QT>
 constexpr int kLaneScanUnroll = QT >= 8 ? 2 : QT == 4 ? 4 : 8;
 
-// the query tile of K6 / K7: queries q0 .. q0 + QT - 1 widened to fp32 into sq[QT][k], zeros past m
+// the query tile of K6 / K7: queries q0 .. q0 + QT - 1 widened to fp32 into sq[QT][k] (b1_t: the raw words), zeros past m
 template <int QT, int THREADS, typename T>
 __device__ __forceinline__ void load_query_tile(float *sq, const T *q, int q0, int m, int k)
 {
     for (int e = threadIdx.x; e < QT * k; e += THREADS) {
         const int u = e / k, t = e - u * k;
-        sq[e] = q0 + u < m ? pt_ld1(q + (size_t)(q0 + u) * k + t) : 0.0f;
+        reinterpret_cast<tile_word_t<T> *>(sq)[e] = q0 + u < m ? pt_ld1(q + (size_t)(q0 + u) * k + t) : tile_word_t<T>(0);
     }
 }
 

@@ -188,7 +188,9 @@ int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const voi
                        int64_t base, nns_key *keys, nns_key *ws, hipStream_t st, int bstride)
 {
     nns_key *scan_out = p.splits > 1 ? ws : keys;
-    if (bf16 == DT_I8)
+    if (bf16 == DT_B1)
+        NNS_TRY(launch_topk_scan<b1_t>(p, k, m, n, kn, bstride, (const b1_t *)q, (const b1_t *)r, base, scan_out, st));
+    else if (bf16 == DT_I8)
         NNS_TRY(launch_topk_scan<i8_t>(p, k, m, n, kn, bstride, (const i8_t *)q, (const i8_t *)r, base, scan_out, st));
     else if (bf16 == DT_F16)
         NNS_TRY(launch_topk_scan<f16_t>(p, k, m, n, kn, bstride, (const f16_t *)q, (const f16_t *)r, base, scan_out, st));

@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     "nns_plan_range_mfma_bf16", "nns_plan_topk_mfma_bf16", "nns_range_threshold_bf16",
     "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk", "nns_search_f16_range",
     "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk", "nns_search_i8_range",
+    "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk", "nns_search_b1_range",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
@@ -70,7 +71,9 @@ OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
                     "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk",
                     "nns_search_f16_range",
                     "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk",
-                    "nns_search_i8_range")
+                    "nns_search_i8_range",
+                    "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk",
+                    "nns_search_b1_range")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -180,7 +183,12 @@ def _load() -> ctypes.CDLL:
                 "nns_index_search_i8": lib.nns_index_search.argtypes,
                 "nns_search_i8_ex": lib.nns_search_f32_ex.argtypes,
                 "nns_search_i8_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_i8_range": lib.nns_search_f32_range.argtypes}
+                "nns_search_i8_range": lib.nns_search_f32_range.argtypes,
+                "nns_index_create_b1": lib.nns_index_create.argtypes,
+                "nns_index_search_b1": lib.nns_index_search.argtypes,
+                "nns_search_b1_ex": lib.nns_search_f32_ex.argtypes,
+                "nns_search_b1_topk": lib.nns_search_f32_topk.argtypes,
+                "nns_search_b1_range": lib.nns_search_f32_range.argtypes}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -261,7 +269,7 @@ def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
 
 def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0, schedule: bool = False) -> dict:
     """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  bf16: False / True, 2 for fp16 or 3
-    for int8 points (here and in plan_topk / plan_range).  "split": 1 when fp32 points
+    for int8 points (here and in plan_topk / plan_range; those two also take 4, binary points, with k in bits).  "split": 1 when fp32 points
     take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0).  schedule=True asks for the
     16th field too, "lazy": 1 when the split operands run the lazy schedule (0 with NNS_FILTER_SPLIT_EAGER)."""
     nf = 16 if schedule else 15
@@ -528,14 +536,67 @@ def search_i8(query_points, reference_points, *, return_distances: bool = False,
     return (idx, dist) if return_distances else idx
 
 
+def pack_bits(a) -> np.ndarray:
+    """A [n][k] array of bool / 0-1 values as packed binary points: uint8 [n][4 * ceil(k / 32)], bit t of a point at
+    (byte[t // 8] >> (t % 8)) & 1 (= bit t % 32 of little-endian word t // 32), zero-padded to whole 32-bit words.
+    Padding both sets the same way changes no Hamming distance."""
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("pack_bits takes a 2-D array of 0 / 1 values")
+    if a.dtype != np.bool_:
+        if ((a != 0) & (a != 1)).any():
+            raise ValueError("pack_bits takes bool or 0 / 1 values")
+        a = a.astype(np.bool_)
+    n, k = a.shape
+    out = np.zeros((n, 4 * ((k + 31) // 32)), dtype=np.uint8)
+    out[:, :(k + 7) // 8] = np.packbits(a, axis=1, bitorder="little")
+    return out
+
+
+def to_b1(a) -> np.ndarray:
+    """Packed binary points, numpy uint8 [.][kb] with kb % 4 == 0 or uint32 [.][kw], as a contiguous uint8 [.][4 * kw]
+    array (anything else, a buffer that is not 4-byte aligned included, is refused)."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.uint32):
+        raise ValueError("binary point sets must be 2-D numpy uint8 or uint32 arrays of packed bits (see pack_bits)")
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.uint8)
+    if a.shape[1] % 4 != 0:
+        raise ValueError("binary point sets hold whole 32-bit words: the byte count per point must be a multiple of 4")
+    if a.ctypes.data % 4 != 0:   # (a view into a byte buffer: the library reads words)
+        raise ValueError("binary point sets must be 4-byte aligned")
+    return a
+
+
+def search_b1(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
+              path: str = "auto", device: int = 0):
+    """search() for packed binary points (see to_b1 / pack_bits) under Hamming distance (nns_search_b1_ex): the distances
+    are the Hamming distances as fp32, V0's arithmetic on the bits widened to 0.0 / 1.0."""
+    q = to_b1(query_points)
+    r = to_b1(reference_points)
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("query and reference dimensionality differ")
+    m, kb = q.shape
+    n = r.shape[0]
+    idx = np.empty(m, dtype=np.int32)
+    dist = np.empty(m, dtype=np.float32) if return_distances else None
+    _check(lib.nns_search_b1_ex(8 * kb, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
+                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
+           "nns_search_b1_ex")
+    return (idx, dist) if return_distances else idx
+
+
 def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa, topk_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
     m, k = q.shape
+    if bf16 == 4:
+        k *= 8   # (packed binary points: uint8 columns, k in bits)
     n = r.shape[1] if refs_soa else r.shape[0]
     idx = np.empty((m, max(kn, 0)), dtype=np.int32)
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
-    fn = lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
+    fn = lib.nns_search_b1_topk if bf16 == 4 else lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
         else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
               shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
@@ -578,15 +639,23 @@ def search_topk_i8(query_points, reference_points, kn: int, *, return_distances:
     return _search_topk(to_i8(query_points), to_i8(reference_points), kn, 3, return_distances, shards, path, device, False)
 
 
+def search_topk_b1(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
+                   path: str = "auto", device: int = 0):
+    """search_topk() for packed binary points (see to_b1 / pack_bits; nns_search_b1_topk)."""
+    return _search_topk(to_b1(query_points), to_b1(reference_points), kn, 4, return_distances, shards, path, device, False)
+
+
 def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
     m, k = q.shape
+    if bf16 == 4:
+        k *= 8   # (packed binary points: uint8 columns, k in bits)
     n = r.shape[1] if refs_soa else r.shape[0]
     lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
     pidx = ctypes.POINTER(ctypes.c_int)()
     pdist = ctypes.POINTER(ctypes.c_float)()
-    fn = lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
+    fn = lib.nns_search_b1_range if bf16 == 4 else lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
         else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
               ctypes.byref(pdist) if return_distances else None,
@@ -640,6 +709,13 @@ def search_range_i8(query_points, reference_points, radius2: float, *, return_di
     return _search_range(to_i8(query_points), to_i8(reference_points), radius2, 3, return_distances, path, device, False)
 
 
+def search_range_b1(query_points, reference_points, radius2: float, *, return_distances: bool = False,
+                    path: str = "auto", device: int = 0):
+    """search_range() for packed binary points (see to_b1 / pack_bits; nns_search_b1_range): radius2 is compared with the
+    Hamming distance."""
+    return _search_range(to_b1(query_points), to_b1(reference_points), radius2, 4, return_distances, path, device, False)
+
+
 # ---------------------------------------------------------------------------
 # device-resident API (torch tensors are only the owners of device memory)
 # ---------------------------------------------------------------------------
@@ -666,16 +742,24 @@ class Index:
         filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
         filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER).
         range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA).
-        topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA)."""
+        topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA).
+        A torch.uint8 [n][kb] tensor is a set of packed binary points (pack_bits' layout; kb % 4 == 0, 4-byte aligned):
+        Hamming distance, self.k = 8 * kb bits, self.b1 is true, queries are uint8 [m][kb] likewise."""
         import torch
-        if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int8) or refs.dim() != 2 \
+        if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int8, torch.uint8) or refs.dim() != 2 \
                 or not refs.is_contiguous() or not refs.is_cuda:
-            raise ValueError("refs must be a contiguous fp32, bf16, fp16 or int8 [n][k] tensor on a HIP device")
+            raise ValueError("refs must be a contiguous fp32, bf16, fp16, int8 or uint8 (packed bits) [n][k] tensor on a HIP device")
         self.bf16 = refs.dtype == torch.bfloat16
         self.f16 = refs.dtype == torch.float16
         self.i8 = refs.dtype == torch.int8
+        self.b1 = refs.dtype == torch.uint8
+        if self.b1 and (refs.shape[1] % 4 != 0 or refs.data_ptr() % 4 != 0):
+            raise ValueError("packed binary refs hold whole 32-bit words: kb % 4 == 0 and a 4-byte aligned data_ptr()")
         self.refs = refs  # keep alive: the index reads the original values
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
+        self.cols = self.k   # columns of a query tensor
+        if self.b1:
+            self.k *= 8      # bits
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
             | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
@@ -683,7 +767,7 @@ class Index:
             | (NNS_TOPK_MFMA if topk_mfma else 0)
         self.flags = flags
         h = ctypes.c_void_p()
-        create = lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
+        create = lib.nns_index_create_b1 if self.b1 else lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
             else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
@@ -697,12 +781,13 @@ class Index:
         import torch
         if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous():
             raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
-        if queries.shape[1] != self.k:
+        if queries.shape[1] != self.cols:
             raise ValueError("query dimensionality differs from the index")
+        self._check_aligned(queries)
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
-        fn = lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
+        fn = lib.nns_index_search_b1 if self.b1 else lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
             else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
         _check(fn(self._h, m, queries.data_ptr(), keys.data_ptr(), _stream_ptr(stream)), "nns_index_search")
         return keys
@@ -716,8 +801,9 @@ class Index:
         distances) of a single-shard search in as few launches as the path allows."""
         import torch
         if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
-                or queries.shape[1] != self.k:
+                or queries.shape[1] != self.cols:
             raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
+        self._check_aligned(queries)
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
@@ -732,8 +818,9 @@ class Index:
         """[m][kn] packed (V0 distance, global index) int64 keys, ascending; NNS_KEY_NONE pads short rows."""
         import torch
         if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
-                or queries.shape[1] != self.k:
+                or queries.shape[1] != self.cols:
             raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
+        self._check_aligned(queries)
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty((m, max(kn, 0)), dtype=torch.int64, device=queries.device)
@@ -753,10 +840,15 @@ class Index:
         _check(lib.nns_index_topk_info(self._h, out.ctypes.data, 4), "nns_index_topk_info")
         return dict(zip(("path", "flagged", "examined", "filled"), (int(v) for v in out)))
 
+    def _check_aligned(self, queries):
+        if self.b1 and queries.data_ptr() % 4 != 0:
+            raise ValueError("packed binary queries must be 4-byte aligned")
+
     def _check_queries(self, queries):
         if queries.dtype != self.refs.dtype or queries.dim() != 2 or not queries.is_contiguous() \
-                or queries.shape[1] != self.k:
+                or queries.shape[1] != self.cols:
             raise ValueError("queries must be a contiguous [m][k] tensor of the index's dtype")
+        self._check_aligned(queries)
 
     def range_count(self, queries, radius2: float, lims=None, stream=None):
         """Count pass of the range search: int64 lims [m + 1] (device); the fill's per-chunk offsets stay in the
