@@ -1,6 +1,7 @@
 """GPU tests of fp16 points (IEEE binary16): the f16 MFMA's error model behind tau mode 4, 1-NN through the f16 filter
 (v_mfma_f32_16x16x32_f16 at KT = 128 / 256) and through the exact kernels, near ties, special values and the 32752 guard,
-subnormal operands, top-K, range search, the whole calls and the same-dtype rule.  Every comparison is exact: indices
+subnormal operands, top-K, range search, the whole calls, the resident index's lifecycle (index_base, caller streams,
+changing m, shard merges, refresh and its stale-flag window) and the same-dtype rule.  Every comparison is exact: indices
 equal and distance bits equal to the V0 oracle on the values widened to fp32 (numpy's float16 does the widening)."""
 import ctypes
 import os
@@ -13,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_gpu_parity import _bf16_model_cases  # noqa: E402
 from test_range_cpu import range_oracle, v0_all  # noqa: E402
+from test_topk_cpu import topk_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -313,6 +315,126 @@ def test_whole_calls(pkg, orc):
     assert np.array_equal(lims, wl) and np.array_equal(idx, wi) and np.array_equal(_bits(dist), _bits(wd))
     with pytest.raises(ValueError):
         pkg.search_f16(q.astype(np.float32), r)
+
+
+# ---- the resident index's lifecycle ---------------------------------------------------------------------------------
+def _keys_of(d, sel, base=0):
+    """packed keys of the entries sel [m][kn] of the distance matrix d"""
+    dv = np.take_along_axis(d, sel, 1)
+    return (dv.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (sel + base).astype(np.uint64)
+
+
+def lifecycle_common(pkg, orc, q, r, q_many, r_new, form, plan_dtype):
+    """What test_b1_gpu.test_split_api_manners checks, for an index that runs an MFMA filter (also the body of
+    test_i8_gpu's lifecycle test).  q, r, q_many, r_new: points in the index's own numpy dtype, (130, 5003, 100) with 700
+    queries in q_many; form: stats()["filter_form"]; plan_dtype: plan_filter's bf16 argument.  One index with
+    index_base 10^6 serves 1-NN, top-5, a range search and search_indices on a caller's stream, then m = 40 (below 64
+    queries: the exact kernels), 700 (m_pad beyond 512: the query workspace and the lists grow) and 130 again; two half
+    indices merge to a whole one's keys; a refresh() follows refs rewritten in place.  Every answer is the V0 oracle's,
+    bit for bit.  Returns (ix, rd, qd, base), the index still open on r_new."""
+    f = lambda a: a.astype(np.float32)                  # noqa: E731
+    m, n, k = q.shape[0], r.shape[0], r.shape[1]
+    want = orc.v0_search(f(q), f(r))
+    d = v0_all(f(q), f(r))
+    base = 10 ** 6
+    rd, qd = _dev(r), _dev(q)
+    before = torch.cuda.current_device()
+    ix = pkg.Index(rd, index_base=base, profile=True)
+    torch.cuda.synchronize()
+    radius2 = float(np.sort(d, axis=None)[10 * m])      # about 10 hits per query
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        keys = ix.search_keys(qd, stream=st)
+        tk = ix.search_topk_keys(qd, 5, stream=st)
+        lims, ridx, rdist = ix.search_range(qd, radius2, return_distances=True, stream=st)
+        idx = ix.search_indices(qd, stream=st)
+    st.synchronize()
+    assert np.array_equal(keys.cpu().numpy().view(np.uint64), _keys_of(d, want[0][:, None].astype(np.int64), base)[:, 0])
+    oi, _ = topk_oracle(f(q), f(r), 5)
+    assert np.array_equal(tk.cpu().numpy().view(np.uint64), _keys_of(d, oi.astype(np.int64), base))
+    wl, wi, wd = range_oracle(f(q), f(r), radius2, index_base=base)
+    assert 5 * m <= wl[-1] <= 20 * m
+    assert np.array_equal(lims.cpu().numpy(), wl) and np.array_equal(ridx.cpu().numpy(), wi)
+    assert np.array_equal(_bits(rdist.cpu().numpy()), _bits(wd))
+    assert np.array_equal(idx.cpu().numpy(), want[0] + base)
+    s = ix.stats()
+    assert s["path"] == MFMA and s["filter_form"] == form and s["nonfinite"] == 0, s
+    assert torch.cuda.current_device() == before
+
+    def check(qq, path, what):
+        i, dd = ix.search(_dev(qq), return_distances=True)
+        torch.cuda.synchronize()
+        _same(i.cpu().numpy() - base, dd.cpu().numpy(), *orc.v0_search(f(qq), f(r)), what)
+        s = ix.stats()
+        assert s["path"] == path and s["nonfinite"] == 0, (what, s)
+
+    # one index, changing m
+    pads = [pkg.plan_filter(k, mm, n, bf16=plan_dtype)["m_pad"] for mm in (m, q_many.shape[0])]
+    assert pads[0] <= 512 < pads[1], pads
+    check(q[:40], EXACT, "m = 40")
+    check(q_many, MFMA, "m = 700")
+    check(q, MFMA, "m = 130 again")
+    # shards: two half indices over an odd n, merged, against a whole index with base 0
+    whole = pkg.Index(rd)
+    wk, wtk = whole.search_keys(qd), whole.search_topk_keys(qd, 5)
+    torch.cuda.synchronize()
+    whole.close()
+    assert np.array_equal(wk.cpu().numpy().view(np.uint64), _keys_of(d, want[0][:, None].astype(np.int64))[:, 0])
+    assert np.array_equal(wtk.cpu().numpy().view(np.uint64), _keys_of(d, oi.astype(np.int64)))
+    h = n // 2
+    assert n % 2 == 1
+    lo, hi = pkg.Index(rd[:h]), pkg.Index(rd[h:], index_base=h)
+    a, b = lo.search_keys(qd), hi.search_keys(qd)
+    pkg.keys_min(a, b)
+    torch.cuda.synchronize()
+    assert lo.stats()["path"] == MFMA and hi.stats()["path"] == MFMA      # (of the 1-NN searches: both halves filtered)
+    ta, tb = lo.search_topk_keys(qd, 5), hi.search_topk_keys(qd, 5)
+    pkg.keys_topk_merge(ta, tb)
+    torch.cuda.synchronize()
+    lo.close()
+    hi.close()
+    assert torch.equal(a, wk) and torch.equal(ta, wtk)
+    # refresh() after rewriting the refs in place
+    rd.copy_(torch.from_numpy(r_new))
+    ix.refresh()
+    i2, d2 = ix.search(qd, return_distances=True)
+    torch.cuda.synchronize()
+    _same(i2.cpu().numpy() - base, d2.cpu().numpy(), *orc.v0_search(f(q), f(r_new)), "after refresh")
+    s = ix.stats()
+    assert s["path"] == MFMA and s["filter_form"] == form and s["nonfinite"] == 0, s
+    return ix, rd, qd, base
+
+
+def test_resident_index_lifecycle(pkg, orc):
+    """lifecycle_common for fp16 points, then the stale-flag window of a refresh (test_refresh_relatches_nonfinite_refs
+    for fp16): refs rewritten to hold one 40000.0 — finite, but -2 v is not in binary16 — are caught on the device by K5
+    while the host still believes the image clean; stats() re-latches, and a clean refresh brings the filter back."""
+    m, n, k = 130, 5003, 100
+    q, r, r_new = _u16(91, m, k), _u16(92, n, k), _u16(94, n, k)
+    ix, rd, qd, base = lifecycle_common(pkg, orc, q, r, _u16(93, 700, k), r_new, "f16", 2)
+    r_big = r_new.copy()
+    r_big[1234, 7] = 40000.0
+    assert np.isfinite(r_big.astype(np.float32)).all() and float(r_big[1234, 7]) == 40000.0
+    want_big = _oracle(orc, q, r_big)
+    rd.copy_(torch.from_numpy(r_big))
+    ix.refresh()                                        # no stats() from here to the search: the host flag is stale
+    i, d = ix.search(qd, return_distances=True)
+    torch.cuda.synchronize()
+    _same(i.cpu().numpy() - base, d.cpu().numpy(), *want_big, "stale flag")
+    s = ix.stats()
+    assert s["nonfinite"] == 1 and s["ambiguous"] == m, s           # the device-side check sent every query to the scan
+    i, d = ix.search(qd, return_distances=True)
+    torch.cuda.synchronize()
+    _same(i.cpu().numpy() - base, d.cpu().numpy(), *want_big, "re-latched")
+    assert ix.stats()["path"] == EXACT                  # re-latched by stats(): straight to the exact kernels now
+    rd.copy_(torch.from_numpy(r))
+    ix.refresh()
+    i, d = ix.search(qd, return_distances=True)
+    torch.cuda.synchronize()
+    _same(i.cpu().numpy() - base, d.cpu().numpy(), *_oracle(orc, q, r), "clean again")
+    s = ix.stats()
+    assert s["path"] == MFMA and s["nonfinite"] == 0 and s["filter_form"] == "f16", s
+    ix.close()
 
 
 def test_dtype_mismatch(pkg):

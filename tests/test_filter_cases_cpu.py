@@ -14,11 +14,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LONG_TILES = 2048                   # kShareThrMaxTiles and NNS_F_TILEREC_MAX (filter_mfma.hip)
 ORACLE_BUDGET = 8e10                # checked queries x n x k per case (the CPU oracle does ~1e10 of these a second)
-ORACLE_TOTAL = 3.5e12               # the same over the whole table
+ORACLE_TOTAL = 3.7e12               # the same over the whole table
 HOST_BYTES = 4 << 30                # peak host memory of one case
 
-# dtype: "f32" (fp32 points and operands, tau mode 0), "bf16" (bf16 points, mode 1) or "mixed" (fp32 points through
-# bf16 operands, NNS_FILTER_BF16: mode 2).  per_ref: NNS_RECORDS_PER_REF (path "mfma_perref").  key: filter_key() of
+# dtype: "f32" (fp32 points and operands, tau mode 0), "bf16" (bf16 points, mode 1), "mixed" (fp32 points through
+# bf16 operands, NNS_FILTER_BF16: mode 2), "f16" (fp16 points, filter_f16_kernel: tau mode 4) or "i8" (int8 points,
+# filter_i8_kernel: 5, the form nns_index_filter_form reports; the planner reports bf16 = 1 for both, so their mode
+# comes from the dtype).  per_ref: NNS_RECORDS_PER_REF (path "mfma_perref").  key: filter_key() of
 # the plan, i.e. (kt, mode, share_thr, tile_rec, k5_form, long).  Long streams take the cheapest (m, n) of each K5
 # form: splits = 1 needs >= 256 query groups, 2-3 and 4 splits need the ref count to grow with them.  k is below kt
 # (ragged) in most cases, n is never a multiple of 32.
@@ -157,6 +159,27 @@ FILTER_CASES = [
     FilterCase("mixed", 1000, 250, 63, False, (1024, 2, 1, 0, 'rows2-3', False)),
     FilterCase("mixed", 769, 250, 100, True, (1024, 2, 1, 0, 'wave', False)),
     FilterCase("mixed", 1024, 250, 100, False, (1024, 2, 1, 2, 'wave', False)),
+    FilterCase("f16", 100, 131072, 65537, False, (128, 4, 0, 0, 'rows1', True)),
+    FilterCase("f16", 100, 65536, 140001, False, (128, 4, 0, 0, 'rows2-3', True)),
+    FilterCase("f16", 100, 32768, 300001, False, (128, 4, 0, 0, 'wave', True)),
+    FilterCase("f16", 100, 250, 31, False, (128, 4, 1, 0, 'rows1', False)),
+    FilterCase("f16", 128, 250, 140, False, (128, 4, 1, 0, 'rows2-3', False)),
+    FilterCase("f16", 33, 250, 777, True, (128, 4, 1, 0, 'wave', False)),
+    FilterCase("f16", 100, 250, 777, False, (128, 4, 1, 1, 'wave', False)),
+    FilterCase("f16", 129, 131072, 65537, False, (256, 4, 0, 0, 'rows1', True)),
+    FilterCase("f16", 129, 65536, 140001, False, (256, 4, 0, 0, 'rows2-3', True)),
+    FilterCase("f16", 129, 32768, 300001, False, (256, 4, 0, 0, 'wave', True)),
+    FilterCase("f16", 256, 250, 31, False, (256, 4, 1, 0, 'rows1', False)),
+    FilterCase("f16", 255, 250, 100, False, (256, 4, 1, 0, 'rows2-3', False)),
+    FilterCase("f16", 129, 250, 300, True, (256, 4, 1, 0, 'wave', False)),
+    FilterCase("f16", 256, 250, 300, False, (256, 4, 1, 1, 'wave', False)),
+    FilterCase("i8", 100, 131072, 65537, False, (256, 5, 0, 0, 'rows1', True)),
+    FilterCase("i8", 129, 65536, 140001, False, (256, 5, 0, 0, 'rows2-3', True)),
+    FilterCase("i8", 200, 32768, 300001, False, (256, 5, 0, 0, 'wave', True)),
+    FilterCase("i8", 256, 250, 31, False, (256, 5, 1, 0, 'rows1', False)),
+    FilterCase("i8", 33, 250, 140, False, (256, 5, 1, 0, 'rows2-3', False)),
+    FilterCase("i8", 129, 250, 777, True, (256, 5, 1, 0, 'wave', False)),
+    FilterCase("i8", 100, 250, 777, False, (256, 5, 1, 1, 'wave', False)),
 ]
 
 
@@ -164,9 +187,16 @@ def filter_case_id(c):
     return f"{c.dtype}-k{c.k}-m{c.m}-n{c.n}" + ("-perref" if c.per_ref else "")
 
 
+PLAN_DTYPE = {"bf16": 1, "f16": 2, "i8": 3}         # nns_plan_filter's bf16 argument
+KEY_MODE = {"f16": 4, "i8": 5}                      # the key's mode field where the plan's bf16 / mixed do not tell
+
+
 def plan_case(pkg, c):
+    """The case's plan (plan_filter's fields) plus "dtype", the case's."""
     flags = (pkg.NNS_RECORDS_PER_REF if c.per_ref else 0) | (pkg.NNS_FILTER_BF16 if c.dtype == "mixed" else 0)
-    return pkg.plan_filter(c.k, c.m, c.n, bf16=c.dtype == "bf16", flags=flags)
+    p = pkg.plan_filter(c.k, c.m, c.n, bf16=PLAN_DTYPE.get(c.dtype, 0), flags=flags)
+    p["dtype"] = c.dtype
+    return p
 
 
 def stream_tiles(p):
@@ -184,7 +214,9 @@ def stream_tiles(p):
 
 def refs_per_split(p):
     """Refs of one ref-range split: slots_per_split / slots_per_block super-periods of pad_pts refs (filter_plan)."""
-    spb = p["kt"] // 16 if p["bf16"] else p["kt"] // 8          # k-steps per block (mixed plans with bf16 = 1)
+    # k-steps per block (mixed plans with bf16 = 1; an int8 fragment holds 64 dims of bytes, so OpI8 at kt 256 has
+    # OpBF16K128's 8 steps).  p: plan_case's, or plan_filter's own for fp32 / bf16 points
+    spb = p["kt"] // 32 if p.get("dtype") == "i8" else (p["kt"] // 16 if p["bf16"] else p["kt"] // 8)
     deep = 32 % spb != 0
     gcd = 32 if spb % 32 == 0 else (16 if spb % 16 == 0 else 8)
     slots_per_block = spb // gcd if deep else 1
@@ -193,7 +225,8 @@ def refs_per_split(p):
 
 
 def filter_key(p):
-    mode = 2 if p["mixed"] else p["bf16"]
+    mode = KEY_MODE.get(p.get("dtype"), 2 if p["mixed"] else p["bf16"])
+    assert p["bf16"] == 1 or p.get("dtype") not in KEY_MODE, p
     s = p["splits"]
     k5 = "rows1" if s == 1 else ("rows2-3" if s <= 3 else "wave")
     return (p["kt"], mode, p["share_thr"], p["tile_rec"], k5, stream_tiles(p) > LONG_TILES)
@@ -238,12 +271,13 @@ def test_case_plans_to_its_key(pkg, c):
 
 def test_cases_are_distinct_and_ragged():
     keys = [c.key for c in FILTER_CASES]
-    assert len(set(keys)) == len(keys) == 133
+    assert len(set(keys)) == len(keys) == 154
     kt = {c: c.key[0] for c in FILTER_CASES}
     assert sum(c.k != kt[c] for c in FILTER_CASES) * 2 >= len(FILTER_CASES)
     # every record / threshold form with private thresholds is reached at every depth that has it
     assert {(c.key[0], c.key[1]) for c in FILTER_CASES if c.key[2] == 0} == \
-        {(kt_, 0) for kt_ in (16, 32, 64, 128, 256)} | {(kt_, 1) for kt_ in (128, 256, 384, 512, 640, 768, 1024)}
+        {(kt_, 0) for kt_ in (16, 32, 64, 128, 256)} | {(kt_, 1) for kt_ in (128, 256, 384, 512, 640, 768, 1024)} | \
+        {(128, 4), (256, 4), (256, 5)}
 
 
 def _sweep_keys(pkg):
@@ -252,7 +286,8 @@ def _sweep_keys(pkg):
     ms = [1, 63, 64, 512, 4096, 8192, 16384, 32768, 65536, 131072, 300000]
     ns = [1, 63, 1000, 65537, 140001, 300001, 1048576, 8388608]
     found = {}
-    for dtype, ks in (("f32", ks_f), ("bf16", ks_b), ("mixed", ks_b)):
+    for dtype, ks in (("f32", ks_f), ("bf16", ks_b), ("mixed", ks_b), ("f16", [32, 33, 128, 129, 256]),
+                      ("i8", [32, 128, 129, 256])):
         for k in ks:
             for m in ms:
                 for n in ns:

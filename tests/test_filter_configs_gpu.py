@@ -3,7 +3,8 @@ the configuration that ran is tied to the table through the index's stats, every
 on the returned ref, planted copies, split-edge refs, cross-split duplicates and near-ties plus a random sample are
 checked against the oracle over all refs, and on long streams two half indices merged with keys_min reproduce every
 key.  The long-stream adversarial tests run the ring-wrap and true-overflow inputs of test_gpu_parity.py on every
-tile operator and tau mode whose long streams keep private thresholds (or, mixed, share them)."""
+tile operator and tau mode whose long streams keep private thresholds (or, mixed, share them).  fp16 ("f16") and
+int8 ("i8") cases run filter_f16_kernel / filter_i8_kernel: the index's filter_form ties the run to them."""
 import os
 import sys
 
@@ -34,22 +35,31 @@ def v0_rows(q, r):
 
 
 def make_points(pkg, c, seed):
-    """Uniform [0, 1) queries and refs (fill_uniform, the oracle's RNG bit for bit) as host fp32 arrays; bf16 cases
-    hold the values the search sees (rounded to bf16, widened)."""
+    """Uniform [0, 1) queries and refs (fill_uniform, the oracle's RNG bit for bit) as host fp32 arrays; bf16 and fp16
+    cases hold the values the search sees (rounded to the type, widened), int8 cases the integers floor(256 u) - 128
+    (uniform over -128 .. 127; at k <= 256 every V0 distance of theirs is an exact integer below 2^24)."""
     q = torch.empty((c.m, c.k), dtype=torch.float32, device="cuda")
     r = torch.empty((c.n, c.k), dtype=torch.float32, device="cuda")
     pkg.fill_uniform(q, seed, 0)
     pkg.fill_uniform(r, seed, c.m * c.k)
     if c.dtype == "bf16":
         q, r = q.to(torch.bfloat16).float(), r.to(torch.bfloat16).float()
+    elif c.dtype == "f16":
+        q, r = q.to(torch.float16).float(), r.to(torch.float16).float()
+    elif c.dtype == "i8":
+        q, r = torch.floor(q * 256.0) - 128.0, torch.floor(r * 256.0) - 128.0
     out = q.cpu().numpy(), r.cpu().numpy()
     del q, r
     return out
 
 
+DEVICE_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16, "i8": torch.int8}
+FILTER_FORM = {"f16": "f16", "i8": "i8"}      # stats()["filter_form"] of the dtypes with a filter kernel of their own
+
+
 def to_device(c, a):
     t = torch.from_numpy(a).cuda()
-    return t.to(torch.bfloat16) if c.dtype == "bf16" else t
+    return t.to(DEVICE_DTYPE[c.dtype]) if c.dtype in DEVICE_DTYPE else t
 
 
 def open_index(pkg, c, refs_dev, index_base=0):
@@ -58,7 +68,15 @@ def open_index(pkg, c, refs_dev, index_base=0):
 
 
 def ulp_step(c, v, u):
-    """v moved up by u units in the last place of the points' type (bf16 ulps in bf16 cases)."""
+    """v moved up by u units in the last place of the points' type (bf16 ulps in bf16 cases; fp16: u steps of the
+    binary16 bit pattern, so a subnormal moves by one fp16 ulp too; int8: by u, towards zero where v + u leaves the
+    type's range)."""
+    if c.dtype == "f16":
+        h = np.array([v], np.float16)
+        assert h[0] == v
+        return (h.view(np.uint16) + np.uint16(u)).view(np.float16).astype(np.float32)[0]
+    if c.dtype == "i8":
+        return np.float32(v + u if v + u <= 127 else v - u)
     b = np.array([v], np.float32).view(np.uint32)
     b = b + np.uint32(u << 16 if c.dtype == "bf16" else u)
     return b.view(np.float32)[0]
@@ -169,6 +187,8 @@ def test_filter_configuration_vs_oracle(pkg, orc, c):
     ix.close()
     # the configuration that ran is the case's
     assert st["path"] == 2 and st["k_tile"] == p["kt"] and st["splits"] == p["splits"], (st, p)
+    if c.dtype in FILTER_FORM:
+        assert st["filter_form"] == FILTER_FORM[c.dtype], st
     assert st["nonfinite"] == 0, st
     # the filter decided: the exact scan answered at most 5 % of the queries (none when m < 20)
     assert st["ambiguous"] <= c.m // 20, st
@@ -214,6 +234,8 @@ def _adversarial(pkg, orc, c, q, r, group):
     st = ix.stats()
     ix.close()
     assert st["path"] == 2 and st["k_tile"] == p["kt"] and st["splits"] == p["splits"] and st["nonfinite"] == 0, st
+    if c.dtype in FILTER_FORM:
+        assert st["filter_form"] == FILTER_FORM[c.dtype], st
     idx_h, dist_h = idx.cpu().numpy(), dist.cpu().numpy()
     assert idx_h.min() >= 0 and idx_h.max() < c.n
     assert np.array_equal(_bits(v0_rows(q, r[idx_h])), _bits(dist_h))
@@ -225,7 +247,71 @@ def _adversarial(pkg, orc, c, q, r, group):
 
 
 def _as_points(c, orc, a):
+    if c.dtype == "f16":
+        return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
     return orc.round_bf16(a) if c.dtype == "bf16" else np.ascontiguousarray(a, np.float32)
+
+
+def _four_squares(limit):
+    """[limit][4]: row v holds four integers whose squares sum to v (Lagrange)."""
+    s = int(np.sqrt(limit)) + 1
+    a, b, cc, d = np.meshgrid(*[np.arange(s)] * 4, indexing="ij")
+    tot = (a * a + b * b + cc * cc + d * d).ravel()
+    out = np.zeros((limit, 4), np.int64)
+    vals, first = np.unique(tot, return_index=True)
+    keep = vals < limit
+    assert keep.sum() == limit
+    out[vals[keep]] = np.stack([x.ravel()[first[keep]] for x in (a, b, cc, d)], axis=1)
+    return out
+
+
+def _i8_line(pkg, c, p, q, r, G, rng):
+    """The ring-wrap input for int8 points, written into q and r; returns the group's query rows.  L = 8192 refs at the
+    head of the stream whose squared distances D_j to an integer centre fall strictly from 3e5 to 1e3 (a random ref
+    lies at ~1e4 k): D_j = 1e3 + 2.99e5 sqrt(1 - j / (L - 1)), steps of ~18 at the far end and thousands at the near
+    end, so that only the last few line refs lie within 2 tau (tau ~ 10^2) of the final minimum.  Ref j is the
+    centre plus offsets of magnitude b or b + 1 in k - 8 coordinates (b^2 (k - 8) <= D_j) and, in four more, the
+    four squares that make up the rest: D_j exactly, signs at random.  The last four coordinates stay at the centre's
+    values: the group's queries are the centre with +-1 noise there, so every query sees D_j plus a constant.  The
+    centre is small (|v| <= 16), the line's norms stay below the cloud's largest (checked) and tau does not grow."""
+    L, d_hi, d_lo, k = 8192, 300000, 1000, c.k
+    perm = rng.permutation(k)
+    still, four, free = perm[:4], perm[4:8], perm[8:]
+    kf = free.size
+    centre = rng.integers(-16, 17, k).astype(np.float32)
+    target = d_lo + np.rint((d_hi - d_lo) * np.sqrt(np.linspace(1.0, 0.0, L))).astype(np.int64)
+    assert (np.diff(target) < 0).all()
+    b = np.floor(np.sqrt(target // kf)).astype(np.int64)
+    assert (b * b * kf <= target).all() and ((b + 1) ** 2 * kf > target).all()
+    rem = target - kf * b * b
+    nb = rem // (2 * b + 1)                     # coordinates at b + 1 (< kf), rotated from ref to ref
+    rem = rem - nb * (2 * b + 1)                # 0 .. 2 b: the four squares
+    off = np.zeros((L, k), np.int64)
+    off[:, free] = b[:, None] + ((np.arange(kf)[None, :] + np.arange(L)[:, None]) % kf < nb[:, None])
+    off[:, four] = _four_squares(int(rem.max()) + 1)[rem]
+    assert np.array_equal((off * off).sum(axis=1), target) and not off[:, still].any()
+    line = centre + np.where(rng.random((L, k)) < 0.5, -1, 1) * off
+    assert line.min() >= -128 and line.max() <= 127
+    r[:L] = line
+    norm2 = (r.astype(np.float64) ** 2).sum(axis=1)
+    assert norm2[:L].max() <= norm2[L:].max()
+    group = rng.choice(c.m, G, replace=False)
+    noise = np.zeros((G, k), np.float32)
+    noise[:, still] = rng.integers(-1, 2, (G, 4))
+    q[group] = centre + noise
+    r64 = r.astype(np.float64)
+    for g in group:
+        d = v0_rows(np.repeat(q[g][None, :], L, axis=0), r[:L])
+        assert (np.diff(d) <= 0).all(), "a line ref is not a record for the group"
+        assert (np.diff(d) < 0).mean() > 0.9
+        # fewer than half a ring of line refs within 2 tau of the query's final minimum (tau mode 1, OpI8's): the rings
+        # hold what the margin keeps, and wrap on the records
+        x = q[g].astype(np.float64)
+        dall = norm2 - 2.0 * (r64 @ x) + x @ x
+        c0, c1, x2 = pkg.tau_consts(p["kt"], float(x @ x), float(norm2.max()), 1)
+        tau = c0 + c1 * max(dall.min() - x @ x + x2, 0.0)
+        assert (dall[:L] <= dall.min() + 2.0 * tau).sum() < 32, tau
+    return group
 
 
 @pytest.mark.timeout(300)
@@ -239,12 +325,18 @@ def test_long_stream_ring_lists_wrap(pkg, orc, c):
     hold most of such a line: there 2048 refs start at the cloud's centre and run from 0.9 to 0.45 of its centred ref
     norm, so the line does not raise the largest norm and the records within tau of the minimum stay below a ring per
     list.  The line comes first in the split's stream, and the host checks that each of its refs is at least as near
-    to every group query as all before it: each is a record whatever lane or list it falls to."""
+    to every group query as all before it: each is a record whatever lane or list it falls to.  fp16 points take the
+    bf16 line rounded to binary16; int8 points an integer line of their own (_i8_line)."""
     p = plan_case(pkg, c)
     assert p["splits"] == 1
     rng = np.random.default_rng(c.k + 13)
     q, r = make_points(pkg, c, 600 + c.k)
     G = 32
+    if c.dtype == "i8":
+        group = _i8_line(pkg, c, p, q, r, G, rng)
+        _, st = _adversarial(pkg, orc, c, q, r, group)
+        assert st["ambiguous"] < G, st
+        return
     if c.dtype == "mixed":      # (the margin's norms are taken about the refs' centre, ~0.5 in every coordinate)
         L, R = 2048, np.sqrt(c.k / 12.0)
         s_hi, s_lo, centre = 0.9 * R, 0.45 * R, 0.5
@@ -255,7 +347,10 @@ def test_long_stream_ring_lists_wrap(pkg, orc, c):
     line[np.arange(L), np.arange(L) % c.k] += np.linspace(s_hi, s_lo, L, dtype=np.float32)
     r[:L] = _as_points(c, orc, line)
     group = rng.choice(c.m, G, replace=False)
-    q[group] = _as_points(c, orc, base + rng.normal(0, 1e-5, (G, c.k)))
+    # (bf16 rounds the noise away: the group is 32 copies of the centre.  binary16's grid is 2^-14 just below 0.125, where
+    #  noise of 1e-5 would now and then move a coordinate by 6e-5 and break a tie between equal steps the wrong way
+    #  round; a tenth of it leaves fp16 groups at the centre too)
+    q[group] = _as_points(c, orc, base + rng.normal(0, 1e-6 if c.dtype == "f16" else 1e-5, (G, c.k)))
     for g in group:
         d = v0_rows(np.repeat(q[g][None, :], L, axis=0), r[:L])
         assert (np.diff(d) <= 0).all(), "a line ref is not a record for the group"
@@ -313,15 +408,27 @@ def test_long_stream_mixed_margin_covers_coherent_rounding(pkg, orc, c):
 def test_long_stream_true_overflow_falls_back(pkg, orc, c):
     """8192 exact copies of the nearest ref inside one long stream: every lane list holds more than 64 live
     candidates, the overflow bit sends the group's queries to the exact scan, and the answer is the lowest copy
-    (test_filter_true_list_overflow_falls_back on a long stream)."""
+    (test_filter_true_list_overflow_falls_back on a long stream).  The group's queries are the hot ref plus noise of a
+    few units in the last place: 1e-3 rounded to binary16 for fp16 points, +-1 in up to four coordinates for int8."""
     rng = np.random.default_rng(c.k + 17)
     q, r = make_points(pkg, c, 700 + c.k)
     D, G = 8192, 24
-    hot = _as_points(c, orc, rng.random((1, c.k)))
     j0 = c.n // 3 + 5
+    if c.dtype == "i8":
+        hot = rng.integers(-128, 128, (1, c.k)).astype(np.float32)
+    else:
+        hot = _as_points(c, orc, rng.random((1, c.k)))
     r[j0:j0 + D] = hot
     group = rng.choice(c.m, G, replace=False)
-    q[group] = _as_points(c, orc, hot + rng.normal(0, 1e-2 if c.dtype == "bf16" else 1e-4, (G, c.k)))
+    if c.dtype == "i8":         # the group: the hot ref moved by 1 in up to four coordinates, towards zero
+        near = np.repeat(hot, G, axis=0)
+        for g in range(G):
+            t = rng.choice(c.k, 4, replace=False)
+            near[g, t] -= np.sign(near[g, t]) * rng.integers(0, 2, 4)
+        q[group] = near
+    else:
+        noise = {"bf16": 1e-2, "f16": 1e-3}.get(c.dtype, 1e-4)
+        q[group] = _as_points(c, orc, hot + rng.normal(0, noise, (G, c.k)))
     idx_h, st = _adversarial(pkg, orc, c, q, r, group)
     assert (idx_h[group] == j0).all(), idx_h[group]
     assert st["ambiguous"] >= G, st

@@ -1,6 +1,6 @@
 """GPU tests of int8 points: the operand lane map of v_mfma_i32_16x16x64_i8 (selftest mode 6), 1-NN through the int8 filter
 (both record forms) and through the exact kernels, the extreme values, ties, top-K, range search, the whole calls, the
-same-dtype rule and the agreement with a bf16 index built from the same values.  Every comparison is exact: indices equal
+resident index's lifecycle, the same-dtype rule and the agreement with a bf16 index built from the same values.  Every comparison is exact: indices equal
 and distance bits equal to the V0 oracle on the values widened to fp32."""
 import os
 import sys
@@ -10,6 +10,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_f16_gpu import lifecycle_common  # noqa: E402
 from test_range_cpu import range_oracle, v0_all  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +228,29 @@ def test_whole_calls(pkg, orc):
     assert np.array_equal(lims, wl) and np.array_equal(idx, wi) and np.array_equal(_bits(dist), _bits(wd))
     with pytest.raises(ValueError):
         pkg.search_i8(q.astype(np.float32), r)
+
+
+# ---- the resident index's lifecycle ---------------------------------------------------------------------------------
+def test_resident_index_lifecycle(pkg, orc):
+    """test_f16_gpu.lifecycle_common for int8 points (index_base, a caller's stream, search_indices, changing m, shard
+    merges, refresh), then a refresh to refs that hold rows of all -128 and all 127: the filter keeps running (no int8
+    value is out of its range) and finds them."""
+    m, n, k = 130, 5003, 100
+    q, r, r_new = _i8(91, m, k), _i8(92, n, k), _i8(94, n, k)
+    ix, rd, qd, base = lifecycle_common(pkg, orc, q, r, _i8(93, 700, k), r_new, "i8", I8)
+    r_ext, q_ext = r_new.copy(), q.copy()
+    r_ext[5], r_ext[4000] = -128, 127
+    q_ext[0], q_ext[1] = -128, 127
+    rd.copy_(torch.from_numpy(r_ext))
+    ix.refresh()
+    i, d = ix.search(_dev(q_ext), return_distances=True)
+    torch.cuda.synchronize()
+    i, d = i.cpu().numpy() - base, d.cpu().numpy()
+    _same(i, d, *_oracle(orc, q_ext, r_ext), "extreme rows after refresh")
+    assert i[0] == 5 and i[1] == 4000 and d[0] == 0 and d[1] == 0
+    s = ix.stats()
+    assert s["path"] == MFMA and s["nonfinite"] == 0 and s["filter_form"] == "i8", s
+    ix.close()
 
 
 def test_dtype_mismatch(pkg):
