@@ -131,6 +131,17 @@ enum {
                           * fp32 points whose filter form is the split one, 8 <= k <= 256, or bf16 points, 32 <= k <= 256
                           * (the ref image is then the bf16 filter's); with NNS_FILTER_F32, NNS_FILTER_BF16 or another k:
                           * NNS_ERR_UNSUPPORTED.  Also accepted by nns_search_f32_topk / nns_search_bf16_topk */
+    NNS_FILTER_I8PRE_OFF = 16384, /* MFMA filter, fp32 points in the 128-deep lazy layout (64 < k <= 128 on split-bf16
+                          * operands, default schedule): do not keep the int8 pre-pass's operands; every search runs the
+                          * lazy 16x16x32 kernel.  Without the flag such an index also holds an int8 image of the centred
+                          * refs under one scale and one i32 seed per ref (128 + 4 bytes per ref more), and each long-stream
+                          * search chooses ON THE DEVICE between the int8 pre-pass kernel (first pass on
+                          * v_mfma_i32_16x16x64_i8, half the MFMA cycles; flagged tiles refined with the lazy kernel's own
+                          * chain) and the lazy kernel: the pre-pass runs when the refs' scale is valid and at most m / 64
+                          * queries have an int8 bound above 1.5 x the lazy bound.  Same keys either way.  No effect at
+                          * other depths or schedules; NNS_ERR_INVALID with other point types or with the force flag */
+    NNS_FILTER_I8PRE_FORCE = 32768, /* ... run the pre-pass whenever the scale is valid, whatever the count says (the bound
+                          * holds for any data: answers stay exact, an ill-suited cloud only refines more tiles) */
     NNS_MULTI_FORCE_COLLECTIVE = 256 /* nns_search_*_multi, for tests: no single-GPU shortcut — even ONE shard runs the
                           * thread-per-GPU body, ncclCommInitAll and the grouped ncclAllReduce (core.cu:965-1057's
                           * shape), so that branch can be executed on a one-GPU box (a 1-rank all-reduce) */
@@ -588,6 +599,10 @@ int nns_selftest_mfma_lazy(int kt, const float *a, const float *b, const float *
  * order (as K2 writes them) through the kernel's own gather.  out_hh[ref][query] = the accumulator, seeded with c0[ref],
  * after the four hi.hi MFMAs; out[ref][query] = after rh.ql and rl.qh of every 32-dim step on top.  [32][64] each. */
 int nns_selftest_mfma_lazy16(const float *q, const float *r, const float *c0, float *out, float *out_hh);
+/* Diagnostic: the int8 pre-pass's operands and chain on one wave (host pointers; q [64][128], r [32][128] int8, seeds
+ * [32]): the images are written in K2's lane map at depth 128, the refs negated, and the kernel's two
+ * v_mfma_i32_16x16x64_i8 per tile run with the seeds as srcC.  out [32 refs][64 queries] = seeds[ref] - q.r, exact. */
+int nns_selftest_mfma_i8pre(const int8_t *q, const int8_t *r, const int *seeds, int *out);
 /* Diagnostic (host only): the MFMA tile of the lazy split kernel this build launches — 16 (v_mfma_f32_16x16x32_bf16, the
  * default) or 32 (v_mfma_f32_32x32x16_bf16, a build with -DNNS_F_LAZY_T16=0).  Plans, images and lists are the same. */
 int nns_filter_lazy_tile(void);
@@ -634,6 +649,12 @@ int nns_split_lazy_bound(int kt, float qnorm2, float ymax2, float *out1);
  * points, 5 int8 points (exact integer scores on v_mfma_i32_16x16x64_i8; 5 is not a tau mode: the margin formula is
  * nns_tau_consts mode 1's); -1 on the exact path.  Host only. */
 int nns_index_filter_form(nns_index *ix, int *form_out);
+/* *ran_out = 1 when the filter of the index's last search was the int8 pre-pass kernel (0: the lazy kernel, another
+ * schedule or path, or no search yet).  A stream-ordered read: waits for the stream the index last worked on. */
+int nns_index_filter_pre(nns_index *ix, int *ran_out);
+/* B8 of the int8 pre-pass for one query: s the shared scale, ex2 = |e_x|^2 and q82 = |q8|^2 the
+ * query's quantisation sums, r8max2 / eymax2 the refs' maxima, c0 = nns_tau_consts(128, ., ., 3)[0].  Host arithmetic. */
+int nns_i8pre_bound(float s, float ex2, float q82, float r8max2, float eymax2, float c0, float *out1);
 
 /* ---- the exchange of the one-process-per-GPU form ----------------------------
  * What V8/V9's gather + host re-rank (core.cu:821-852, 1025-1056) becomes when every GPU

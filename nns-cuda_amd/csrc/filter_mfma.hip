@@ -141,6 +141,7 @@ struct OpBase {
     static constexpr bool kI8 = false;        // int8 points (OpI8): i32 accumulators, launched as filter_i8_kernel
     static constexpr bool kSplit = false;     // split-bf16 operands of fp32 points streamed hi, lo per k-step (OpSplitT)
     static constexpr bool kLazy = false;      // the lazy schedule of the split operands (OpLazySplitT)
+    static constexpr bool kPre = false;       // the int8 pre-pass of the lazy schedule (OpI8Pre), launched as filter_i8pre_kernel
     static constexpr int kSlotSteps = 32;     // fragment steps (1 KiB each) of a ring slot
     static constexpr int kRingDepth = 4;      // ring slots
     static constexpr bool kDmaBurst = false;  // a slot's ring DMA pieces one per step (true: back to back, see the interval)
@@ -164,7 +165,7 @@ constexpr int F_D = OP::kRingDepth;
 template <class OP>
 constexpr int F_SLOT_COORD = OP::kSlotSteps * 1024;
 template <class OP>
-constexpr int F_SLOT_NORM = OP::kLazy ? 1024 : 2048;
+constexpr int F_SLOT_NORM = OP::kPre ? 256 : OP::kLazy ? 1024 : 2048;
 template <class OP>
 constexpr int F_SLOT_BYTES = F_SLOT_COORD<OP> + F_SLOT_NORM<OP>;
 template <class OP>
@@ -429,6 +430,42 @@ struct OpLazySplit16 : OpBF16T<8> {
     static constexpr int kLPQ = 2;
 };
 
+// The int8 pre-pass of the lazy schedule (KT = 128; DESIGN section 4, "int8 pre-pass"): the first-pass question — can any
+// pair of this 16 x 16 tile be within the lane's threshold? — asked of v_mfma_i32_16x16x64_i8 on K2's int8 image of the
+// same centred points (r8, q8 under one scale s; the image holds -r8 and the accumulator is seeded with N_j =
+// floor(|y'_j|^2 / (2 s^2)), so it ends as A = N_j - q8.r8 with 2 s^2 A <= score + B8_i).  Half the MFMA cycles and half
+// the ring bytes of the hi-hi pass: a 32-ref block is 2 ref tiles x 2 k-steps of 64 dims = 4 fragments, a 64-ref slot 8
+// fragment steps (one DMA piece per wave) + the slot's 64 seeds, and the ring is 16 slots deep so that a piece keeps its
+// landing time at half the interval.  The threshold lives in the integer domain (thrw8, updated where thr is): the
+// hot loop spends v_min3_i32 + v_min_i32 + v_cmp per (tile, state).  A tile has only two k-steps, so the retiring tile's
+// minima and masks are taken at k-step 1 of the other tile and tested one step later, at its own seed step; a flagged
+// (tile, state) is refined on a FRESH accumulator with lazy16's chain in lazy16's order (norms, four rh.qh, then rh.ql and
+// rl.qh per k-step), every operand loaded from global memory inside the branch.  Lists, plan and K5 are OpLazySplit16's.
+struct OpI8Pre : OpBF16T<4> {
+    static constexpr int kSlotSteps = 8;
+    static constexpr int kRingDepth = 16;
+    static constexpr bool kPre = true;
+    static constexpr int kLPQ = 2;
+    // (the builtin, as OpI8: 32 resident operand registers leave the allocator room, and it keeps the read hazards)
+    __device__ static __forceinline__ void mma16(const float4 &a, const float4 &b, f32x4 &acc)
+    {
+        acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b),
+                                                                             __builtin_bit_cast(i32x4, acc), 0, 0, 0));
+    }
+    // first MFMA of a tile: srcC = the refs' integer seeds
+    __device__ static __forceinline__ void mma16_seed(const float4 &a, const float4 &b, f32x4 &acc, const f32x4 &c)
+    {
+        acc = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b),
+                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
+    }
+    __device__ static __forceinline__ void mma16_tail_fence(AccSet16 &) {}
+    // the refinement's bf16 MFMAs (builtin too)
+    __device__ static __forceinline__ f32x4 mma16_bf16(const float4 &a, const float4 &b, const f32x4 &acc)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    }
+};
+
 // min over the lanes that carry the same query: l ^ 32 (32x32 tiles), and l ^ 16 too (16x16 tiles).  Row
 // swaps (v_permlane32_swap / v_permlane16_swap, gfx950), not ds_bpermute: no LDS round trip on the slow
 // path.  swap(t, t) returns {old t with its upper rows replaced by the partner's, and vice versa}: the min of
@@ -464,6 +501,7 @@ struct FilterArgs {
     int share_thr;          // short streams: a query's lanes adopt the smallest of their thresholds
     int tile_rec;           // short streams: ONE record per (lane, ref tile) — (tile minimum, first ref of the lane's
                             // rows) — instead of one per score within the threshold; K5 re-ranks the lane's rows
+    FilterPreArgs pre;      // OpI8Pre: K2's int8 operands beside the lazy image
 #ifdef NNS_DIAG
     unsigned long long *stamps;   // diagnostic (NNS_FILTER_CLOCK): per-workgroup s_memtime / s_memrealtime
 #endif
@@ -485,7 +523,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // everywhere else SPS = 32, F_D = 4.
     constexpr bool LAZY = OP::kLazy;
     constexpr int SPS = OP::kSlotSteps;
-    static_assert(F_LDS_BYTES<OP> == 4 * (32768 + 2048), "every operator's ring takes the same LDS: one workgroup per CU");
+    static_assert(F_LDS_BYTES<OP> == 4 * (32768 + 2048) || (OP::kPre && F_LDS_BYTES<OP> <= 4 * (32768 + 2048)),
+                  "every operator's ring takes the same LDS: one workgroup per CU");
     constexpr bool DEEP = SPS % SPB != 0;
     static_assert(SPS == 32 || !DEEP, "blocks straddling slots: 32-step slots only");
     constexpr int SUP_SLOTS = DEEP ? SPB / SUP_GCD : 1;
@@ -519,7 +558,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #define NNS_F_LAZY_SHARE 1
 #endif
     constexpr bool kLazyShare = NNS_F_LAZY_SHARE != 0;
-    constexpr int AHEAD = LAZY ? NNS_F_LAZY_AHEAD : OP::kLag ? 2 : 3;
+    // The pre-pass ring of sixteen: an interval is half the lazy one, so twice as many slots ahead keep a piece's landing time
+#ifndef NNS_F_PRE_AHEAD
+#define NNS_F_PRE_AHEAD 8
+#endif
+    constexpr bool PRE = OP::kPre;
+    constexpr int AHEAD = PRE ? NNS_F_PRE_AHEAD : LAZY ? NNS_F_LAZY_AHEAD : OP::kLag ? 2 : 3;
     static_assert(AHEAD >= 2 && AHEAD <= F_D<OP> - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
     // DMA pieces per wave and slot that the counted vmcnt waits may leave in flight: with the norms issued by one wave
     // per slot, a wave's youngest slot has F_PPW or F_PPW + F_NP pieces — counting F_PPW is safe for both
@@ -539,12 +583,17 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     constexpr bool T16 = OP::kTile16;
     constexpr int NS = T16 ? 2 * QB : QB;
     constexpr int QPS = T16 ? 16 : 32;          // queries per state
-    constexpr int QFB = LAZY ? 2 * SPB : SPB;   // query fragments per 32-query block (lazy: qh and ql of each hi step)
-    constexpr int NBQ = T16 ? SPB / 2 : QFB;    // resident operand fragments per state
+    // query fragments per 32-query block of the fp32 points' image (lazy: qh and ql of each hi step; the pre-pass refines
+    // out of the same image: 16 at KT = 128)
+    constexpr int QFB = PRE ? 16 : LAZY ? 2 * SPB : SPB;
+    constexpr int NBQ = T16 ? SPB / 2 : QFB;    // resident operand fragments per state (the pre-pass: q8's two k-steps)
     // the lazy schedule on 16x16 tiles (OpLazySplit16): gathered operands, two lists per query
     constexpr bool L16 = LAZY && T16;
     static_assert(!L16 || (OP::kLPQ == 2 && QB == 2 && SPB == 8), "OpLazySplit16: KT = 128, four states, two lists per query");
-    static_assert(L16 || OP::kLPQ == (T16 ? 4 : 2), "list lanes per query: the lanes a query sits on");
+    // the pre-pass keeps OpLazySplit16's lists: two per query, owned by the lanes with even g
+    constexpr bool Q2 = L16 || PRE;
+    static_assert(!PRE || (T16 && !LAZY && OP::kLPQ == 2 && QB == 2 && SPB == 4), "OpI8Pre: KT = 128, four states, two lists per query");
+    static_assert(Q2 || OP::kLPQ == (T16 ? 4 : 2), "list lanes per query: the lanes a query sits on");
     const int g16 = lane >> 4, i16 = lane & 15;   // (16x16 tiles: the lane's row quarter and query column)
 
     // ---- resident B operands: this wave's QB x 32 queries, all of K (128 VGPRs at QB = 2) ----
@@ -561,6 +610,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             for (int b = 0; b < NBQ; ++b) {
                 // (L16: qh of query tile st, k-step b, gathered out of query block st / 2's interleaved qh | ql fragments)
                 if constexpr (L16) bq[st][b] = a.qimg[(size_t)(qblk0 + (st >> 1)) * (QFB * 64) + lazy16_gather(lane, st & 1, b, 2, 0)];
+                else if constexpr (PRE) bq[st][b] = a.pre.q8[((size_t)(qblk0 * 2 + st) * 2 + b) * 64 + lane];   // q8 of query tile st, k-step b
                 else bq[st][b] = src[(st * NBQ + b) * 64];
             }
             // (record form 2 keeps no thresholds: skip the margin's double-precision arithmetic, ~1 us of a short stream)
@@ -572,7 +622,14 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             if constexpr (LAZY)
                 bnd[st] = split_lazy_bound(a.kt, a.qnorm[qblk0 * 32 + st * QPS + (lane & (QPS - 1))],
                                            __uint_as_float(a.scal->ymax2_bits));
+            if constexpr (PRE) bnd[st] = a.pre.qb8[qblk0 * 32 + st * QPS + (lane & (QPS - 1))];   // B8 of the lane's query
         }
+    }
+    // (pre-pass) score units per integer unit: 1 / (2 s^2), s = cmax / 127 as K2 forms it
+    float inv2s2 = 0.0f;
+    if constexpr (PRE) {
+        const float s8 = __uint_as_float(a.scal->i8_cmax_bits) / 127.0f;
+        inv2s2 = 1.0f / (2.0f * s8 * s8);
     }
     // Pin the loads here: hipcc must wait for them BEFORE the ring starts, not with a
     // vmcnt(0) at their first use inside the loop (it cannot see the asm DMAs).
@@ -582,7 +639,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         for (int b = 0; b < NBQ; ++b)
             asm volatile("" : "+v"(bq[st][b].x), "+v"(bq[st][b].y), "+v"(bq[st][b].z), "+v"(bq[st][b].w));
         asm volatile("" : "+v"(tc[st].c0), "+v"(tc[st].c1), "+v"(tc[st].x2));
-        if constexpr (LAZY) asm volatile("" : "+v"(bnd[st]));
+        if constexpr (LAZY || PRE) asm volatile("" : "+v"(bnd[st]));
     }
     // The tau constants of the lane's states live in LDS behind the ring (2 KiB per wave, read only on
     // the slow path) instead of 3 registers per state; c1 depends on the tile depth alone and is
@@ -614,6 +671,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     auto issue_piece = [&](int s, int p) __attribute__((always_inline)) {
         const size_t gslot = (size_t)(slot0 + s);
         const unsigned dst = lds_base + (s & (F_D<OP> - 1)) * F_SLOT_BYTES<OP>;
+        if constexpr (PRE) {
+            // the int8 region's slot (one 1 KiB piece per wave), and the slot's 64 seeds (one wave's business, as the norms)
+            if (p < F_PPW) dma16(a.pre.rimg8 + gslot * F_SLOT_COORD<OP> + wave * 1024 + lane * 16, dst + wave * 1024);
+            else if (((int)gslot & (F_NW - 1)) == wave) dma4(a.pre.rseed + gslot * SLOT_REFS + lane, dst + F_SLOT_COORD<OP>);
+            return;
+        }
         if (p < F_PPW) {
             const int piece = wave * F_PPW + p;
             if constexpr (OP::kSplit) {
@@ -648,20 +711,23 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // ---- per-lane record state ---------------------------------------------------------
     float thr[NS];
     float thrw[NS];   // lazy split: fl(thr + B), what a tile's hi-hi minimum is tested against
+    int thrw8[NS];    // pre-pass: (thr + B8) / (2 s^2) rounded up, what a tile's integer minimum is tested against
     int cnt[NS];
     // candidate lists are stored [split][state unit][entry][lane] (unit = the 64 lanes' lists of
     // one query block / query tile) so that both the appends of a wave and K5's per-query reads
     // touch consecutive 8-byte words
     // (L16: units of 32 queries as on 32x32 tiles; the owner of state st, quarter g, query i — g even — keeps list lane
     //  32 (g >> 1) + 16 (st & 1) + i of unit st >> 1)
-    constexpr int LQPS = L16 ? 32 : QPS;
+    constexpr int LQPS = Q2 ? 32 : QPS;
     const size_t lblk0 = (size_t)blockIdx.y * (a.m_pad / LQPS) + (size_t)qblk0 * (32 / LQPS);
-    const bool owner = !L16 || (g16 & 1) == 0;
+    const bool owner = !Q2 || (g16 & 1) == 0;
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
         thr[st] = thrw[st] = __builtin_inff();
+        thrw8[st] = kI8PreThrMax;
 #if defined(NNS_DIAG) && defined(NNS_F_THR_NEGINF)   // timing experiment: the fast path alone (results are wrong)
         thr[st] = thrw[st] = -__builtin_inff();
+        thrw8[st] = -kI8PreThrMax;
 #endif
         cnt[st] = 0;
     }
@@ -676,10 +742,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         const unsigned lb_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)lb);
         lbase = (char *)(((uintptr_t)lb_hi << 32) | (uintptr_t)lb_lo);
     }
-    const unsigned loff = (L16 ? 32 * (g16 >> 1) + i16 : lane) * (unsigned)sizeof(CandEntry);
+    const unsigned loff = (Q2 ? 32 * (g16 >> 1) + i16 : lane) * (unsigned)sizeof(CandEntry);
     // byte offset of state st's list behind lbase + loff
     auto list_off = [](int st) __attribute__((always_inline)) -> unsigned {
-        if constexpr (L16) return (unsigned)((st >> 1) * (kCandCap * 64) + (st & 1) * 16) * (unsigned)sizeof(CandEntry);
+        if constexpr (Q2) return (unsigned)((st >> 1) * (kCandCap * 64) + (st & 1) * 16) * (unsigned)sizeof(CandEntry);
         else return (unsigned)(st * (kCandCap * 64 * (int)sizeof(CandEntry)));
     };
     f32x4 nseed0 = {0.0f, 0.0f, 0.0f, 0.0f}, nseed1 = nseed0;   // 16x16 tiles: the two ref tiles' norms
@@ -777,10 +843,20 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         // instructions, and one record process over a query's n refs flags 43 % fewer tiles than two private ones over
         // n / 2 each (C3: 3.40 % -> 1.93 % of the retirements, filter 13.70 -> 13.05 ms; DESIGN, "Where the lazy
         // kernel's time goes").  Lists only get shorter; every entry K5 needs is still <= every threshold the lane holds.
-        if (a.share_thr || (LAZY && kLazyShare)) t = share_min<T16>(t);
+        // (the pre-pass always: its two lists per query rely on the four lanes holding one threshold)
+        if (a.share_thr || (LAZY && kLazyShare) || PRE) t = share_min<T16>(t);
         // (a finite threshold: "x <= thr" then also excludes the +INF scores of padding refs)
         thr[st] = fminf(t, 3.4028234663852886e38f);
         if constexpr (LAZY) thrw[st] = thr[st] + bnd[st];
+        if constexpr (PRE) {
+            // A pair with a three-product score <= thr has 2 s^2 A <= thr + B8, A an integer: A <= floor((thr + B8) / (2 s^2)).
+            // The fp32 sum, the product and inv2s2 itself are each within 2^-23 relative: 2^-20 of the magnitude and
+            // one unit on top keep the rounding on the safe side (B8 carries two units for it).  Clamped below the
+            // padding seeds, and far enough above INT_MIN for the conversion.
+            const float w = (thr[st] + bnd[st]) * inv2s2;
+            const float wu = w + fabsf(w) * 0x1p-20f + 1.0f;
+            thrw8[st] = (int)fminf(fmaxf(floorf(wu), -(float)kI8PreThrMax), (float)kI8PreThrMax);
+        }
     };
     // Slow path, step 2: one finished score x of ref j: append to the state's candidate ring (thr is finite
     // here — tighten clamps it — so "x <= thr" also excludes the +INF scores of padding refs).  `roomy`
@@ -1031,10 +1107,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // ---- 16x16 tiles: one step, with the other ref tile's record collection folded in --------
     constexpr int NT16 = T16 ? NS : 4;
     float tmh[NT16];   // minima of the retiring ref tile, one per state
+    int tmi[NT16];     // (pre-pass: the integer minima)
     unsigned long long hm[NT16];
 #pragma unroll
     for (int i = 0; i < NT16; ++i) {
         tmh[i] = 0.0f;
+        tmi[i] = 0;
         hm[i] = 0ull;
     }
     // threshold test of the retiring ref tile ot of block oblk: ONE wave-uniform branch for the
@@ -1050,7 +1128,71 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #ifdef NNS_DIAG
             diag_tiles += NT16;
 #endif
-            if constexpr (L16) {
+            if constexpr (PRE) {
+                // PRE-PASS: a flagged (ref tile, state) — some lane's integer minimum within thrw8 — gets the three-product
+                // scores of its 16 x 16 pairs on a fresh accumulator: lazy16's chain in lazy16's order (the norms as srcC of
+                // the first rh.qh MFMA, the other three, then rh.ql and rl.qh per k-step), so a refined score has the bits
+                // lazy16 gives it.  Nothing of it is in the ring: rh, rl out of the image's hi and lo regions, qh, ql out
+                // of the query image (all through lazy16_gather), the four norms out of rnorm.
+                // (the very first tests of a stream see the start accumulators / no masks: nothing there)
+                const bool refine = (any != 0ull) & (oblk >= slot0 * BPS);
+                if (__builtin_expect(refine, 0)) {   // cold: laid out off the MFMA stream
+                    constexpr int NK = 4;   // k-steps of 32 dims of the bf16 chain at KT = 128
+                    const float4 *hi = reinterpret_cast<const float4 *>(a.rimg) + (size_t)oblk * (2 * NK * 64);
+                    const float4 *lo = reinterpret_cast<const float4 *>(a.rimg_lo) + (size_t)oblk * (2 * NK * 64);
+                    const int jbase = oblk * 32 + 16 * ot + 4 * g16;
+                    static_for<NT16>([&](auto st_c) __attribute__((always_inline)) {
+                        constexpr int st = decltype(st_c)::value;
+                        if (hm[st] != 0ull) {
+#ifdef NNS_DIAG
+                            ++diag_slow;
+                            const unsigned long long diag_f0 = __builtin_amdgcn_s_memtime();
+#endif
+                            const float4 *qs = a.qimg + (size_t)(qblk0 + (st >> 1)) * (QFB * 64);
+                            // (every load is issued AND consumed inside the state's branch, all of them in flight before
+                            //  the first is used: see the lazy16 refinement below)
+                            float4 rh[NK], rl[NK], qh[NK], ql[NK];
+                            const float4 nv = *reinterpret_cast<const float4 *>(a.rnorm + jbase);
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) rh[ks] = hi[lazy16_gather(lane, ot, ks)];
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) qh[ks] = qs[lazy16_gather(lane, st & 1, ks, 2, 0)];
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) rl[ks] = lo[lazy16_gather(lane, ot, ks)];
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) ql[ks] = qs[lazy16_gather(lane, st & 1, ks, 2, 1)];
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) {
+                                asm volatile("" : "+v"(rh[ks].x), "+v"(rh[ks].y), "+v"(rh[ks].z), "+v"(rh[ks].w));
+                                asm volatile("" : "+v"(qh[ks].x), "+v"(qh[ks].y), "+v"(qh[ks].z), "+v"(qh[ks].w));
+                                asm volatile("" : "+v"(rl[ks].x), "+v"(rl[ks].y), "+v"(rl[ks].z), "+v"(rl[ks].w));
+                                asm volatile("" : "+v"(ql[ks].x), "+v"(ql[ks].y), "+v"(ql[ks].z), "+v"(ql[ks].w));
+                            }
+                            f32x4 o = {nv.x, nv.y, nv.z, nv.w};
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) o = OP::mma16_bf16(rh[ks], qh[ks], o);
+#pragma unroll
+                            for (int ks = 0; ks < NK; ++ks) {
+                                o = OP::mma16_bf16(rh[ks], ql[ks], o);
+                                o = OP::mma16_bf16(rl[ks], qh[ks], o);
+                            }
+                            tighten(st_c, fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]));
+                            // (two lists per query, the lanes with even g own them: the hand-over of the lazy16 refinement)
+                            const bool roomy = __builtin_amdgcn_ballot_w64((cnt[st] & kCandCountMask) + 8 > kCandCap) == 0ull;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const unsigned ob = __float_as_uint(o[r]);
+                                const auto sw = __builtin_amdgcn_permlane16_swap(ob, ob, false, false);
+                                record(st_c, owner ? o[r] : __builtin_inff(), jbase + r, roomy);
+                                record(st_c, owner ? __uint_as_float(sw[1]) : __builtin_inff(), jbase + 4 + r, roomy);
+                            }
+#ifdef NNS_DIAG
+                            diag_cyc += __builtin_amdgcn_s_memtime() - diag_f0;
+#endif
+                        }
+                    });
+                }
+            } else if constexpr (L16) {
                 // LAZY: a flagged (ref tile, state) — some lane's hi-hi minimum within fl(thr + B) — gets its cross products
                 // now, on the same accumulator: rh x ql and rl x qh per k-step, rh out of the ring, rl and ql plain global
                 // loads through the gather (rl: the lo region of the image; ql: the query image, 16 KiB per wave, L2).
@@ -1140,7 +1282,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // SGPR pairs, computed a step before the branch that reads them)
     auto t16_masks = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int st = 0; st < NT16; ++st) hm[st] = __builtin_amdgcn_ballot_w64(tmh[st] <= (LAZY ? thrw[st] : thr[st]));
+        for (int st = 0; st < NT16; ++st) {
+            if constexpr (PRE) hm[st] = __builtin_amdgcn_ballot_w64(tmi[st] <= thrw8[st]);
+            else hm[st] = __builtin_amdgcn_ballot_w64(tmh[st] <= (LAZY ? thrw[st] : thr[st]));
+        }
     };
     // step b = 8 rt + ks of the block blk_global: the 4 MFMAs of ref tile rt's k-step ks; at
     // ks = 1 the other tile's four accumulators (finished at its k-step 7, >= 5 MFMAs ago) are
@@ -1153,7 +1298,9 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             // (with two query tiles per wave a step is two MFMAs: retire one k-step later, so that the reads of the other
             //  tile's accumulators still sit >= 5 MFMAs behind the MFMAs that finished them)
             constexpr int RET = NT16 >= 4 ? 1 : 2;
-            static_assert(NKS >= RET + 2, "the other tile is retired at k-steps RET and RET + 1");
+            // (the pre-pass refines on a fresh accumulator: the retiring tile may be tested while it is seeded again, at
+            //  its own k-step 0, a step behind its minima and masks)
+            static_assert(NKS >= RET + 2 || (PRE && NKS == RET + 1), "the other tile is retired at k-steps RET and RET + 1");
             constexpr int rt = b / NKS, ks = b % NKS, ot = 1 - rt;
             static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
                 constexpr int qt = decltype(qc)::value;
@@ -1170,11 +1317,19 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                     if constexpr (OP::kI8) OP::retire(acc.template at<ot, qt>(), ot == 0 ? nseed0 : nseed1);
                     const f32x4 o = acc.template at<ot, qt>();
                     if constexpr ((kAblate & 2) != 0) asm volatile("" ::"v"(o));
+                    else if constexpr (PRE) {
+                        const i32x4 oi = __builtin_bit_cast(i32x4, o);
+                        tmi[qt] = min(min(min(oi[0], oi[1]), oi[2]), oi[3]);
+                    }
                     else tmh[qt] = fminf(fminf(fminf(o[0], o[1]), o[2]), o[3]);
                     __builtin_amdgcn_sched_barrier(0);   // keep the pair right behind its MFMA
                 }
             });
             if constexpr (ks == RET && (kAblate & 2) == 0) t16_masks();
+            if constexpr (PRE) {
+                // (k-step 0 of tile rt: the masks of the step before are tile rt's own, of the block before this one)
+                if constexpr (ks == 0 && (kAblate & 2) == 0) t16_test(acc, blk_global - 1, std::integral_constant<int, rt>{}, oslot, oin);
+            } else
             if constexpr (ks == RET + 1 && (kAblate & 2) == 0) t16_test(acc, rt == 0 ? blk_global - 1 : blk_global, std::integral_constant<int, ot>{}, oslot, oin);
         }
     };
@@ -1196,7 +1351,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     typename OP::Acc acc;
     if constexpr (T16) {
         // (OpI8: i32 zeros, retired under the norm +INF — see nseed1)
-        const float inf0 = OP::kI8 ? 0.0f : __builtin_inff();
+        // (OpI8Pre: the padding seed's bits, an integer above every threshold)
+        const float inf0 = OP::kI8 ? 0.0f : PRE ? __int_as_float(kI8PrePadSeed) : __builtin_inff();
         const f32x4 inf4 = {inf0, inf0, inf0, inf0};
         static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
             acc.template at<0, decltype(qc)::value>() = inf4;
@@ -1394,6 +1550,16 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     }
     if constexpr (T16) {   // ref tile 1 of the last block is still to be retired
         OP::mma16_tail_fence(acc);
+        if constexpr (PRE && (kAblate & 2) == 0) {
+            // the last block's tile 0 has its masks (k-step 1 of tile 1) and no seed step to be tested at; then tile 1
+            t16_test(acc, (slot0 + ns) * BPS - 1, std::integral_constant<int, 0>{}, ring(ns - 1), BPS - 1);
+            static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
+                const i32x4 oi = __builtin_bit_cast(i32x4, acc.template at<1, decltype(qc)::value>());
+                tmi[decltype(qc)::value] = min(min(min(oi[0], oi[1]), oi[2]), oi[3]);
+            });
+            t16_masks();
+            t16_test(acc, (slot0 + ns) * BPS - 1, std::integral_constant<int, 1>{}, ring(ns - 1), BPS - 1);
+        } else
         if constexpr ((kAblate & 2) == 0) {
             static_for<NT16>([&](auto qc) __attribute__((always_inline)) {
                 if constexpr (OP::kI8) OP::retire(acc.template at<1, decltype(qc)::value>(), nseed1);
@@ -1435,7 +1601,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     }
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
-        if constexpr (L16) {
+        if constexpr (Q2) {
             if (owner) a.counts[(lblk0 + (st >> 1)) * 64 + 32 * (g16 >> 1) + 16 * (st & 1) + i16] = cnt[st];
         } else {
             a.counts[(lblk0 + st) * 64 + lane] = cnt[st];
@@ -1478,9 +1644,12 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_lazy_kernel(const FilterA
 }
 
 // the lazy schedule on 16x16x32 tiles (OpLazySplit16)
+// (a search of an index that keeps the int8 pre-pass's operands enqueues this kernel AND filter_i8pre_kernel; both read
+//  the selection words K2 left and the one they do not name returns at once: no host read, the search stays asynchronous)
 template <class OP>
 __global__ __launch_bounds__(OP::kNW * 64) void filter_lazy16_kernel(const FilterArgs a)
 {
+    if (a.pre.q8 && i8pre_selected(a.scal->i8_cmax_bits, a.scal->i8_odd_count, a.pre.m, a.pre.force != 0)) return;
     filter_main<OP>(a);
 }
 // fp16 points (OpF16T)
@@ -1493,6 +1662,14 @@ __global__ __launch_bounds__(OP::kNW * 64) void filter_f16_kernel(const FilterAr
 template <class OP>
 __global__ __launch_bounds__(OP::kNW * 64) void filter_i8_kernel(const FilterArgs a)
 {
+    filter_main<OP>(a);
+}
+// the int8 pre-pass of the lazy schedule (OpI8Pre)
+template <class OP>
+__global__ __launch_bounds__(OP::kNW * 64) void filter_i8pre_kernel(const FilterArgs a)
+{
+    if (!i8pre_selected(a.scal->i8_cmax_bits, a.scal->i8_odd_count, a.pre.m, a.pre.force != 0)) return;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) const_cast<DevScalars *>(a.scal)->i8_ran = 1;
     filter_main<OP>(a);
 }
 // (the 32x32x16 lazy kernel stays in every build, launched or not: the ISA checks of the two read one compilation)
@@ -1698,6 +1875,55 @@ __global__ __launch_bounds__(64) void mfma_lazy16_selftest_kernel(const float *_
 int launch_mfma_lazy16_selftest(const float *q, const float *r, const float *c0, float *out, float *out_hh, hipStream_t st)
 {
     hipLaunchKernelGGL(mfma_lazy16_selftest_kernel, dim3(1), dim3(64), 0, st, q, r, c0, out, out_hh);
+    NNS_HIP(hipGetLastError());
+    return NNS_OK;
+}
+
+// ---- self-test of OpI8Pre's operands and chain: one wave, 32 refs x 64 queries at KT = 128 --------------------------------
+// q [64][128], r [32][128] int8, seeds [32] i32: the wave writes the two int8 images as K2 writes them (fragment 2 t + ks:
+// lane l holds dims 64 ks + 16 (l >> 4) .. + 15 of point 16 t + (l & 15); the refs NEGATED), then runs the kernel's chain
+// through the operator's own MFMAs: the seed MFMA of k-step 0 with the lane's four seeds as srcC, then k-step 1.
+// out [ref][query] = seeds[ref] - q.r, exact integers.
+__global__ __launch_bounds__(64) void mfma_i8pre_selftest_kernel(const int8_t *__restrict__ q, const int8_t *__restrict__ r,
+                                                                 const int *__restrict__ seeds, int *__restrict__ out)
+{
+    __shared__ uint4 rimg[4 * 64], qimg[8 * 64];   // [fragment 2 t + ks][lane]
+    const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+    auto pack = [&](const int8_t *row, bool neg) {
+        unsigned w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            w[e] = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int v = row[4 * e + b];
+                w[e] |= (unsigned)(unsigned char)(int8_t)(neg ? -v : v) << (8 * b);
+            }
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    };
+    for (int f = 0; f < 8; ++f) {
+        const int t = f >> 1, ks = f & 1;
+        qimg[f * 64 + lane] = pack(q + (16 * t + i) * 128 + 64 * ks + 16 * g, false);
+        if (f < 4) rimg[f * 64 + lane] = pack(r + (16 * t + i) * 128 + 64 * ks + 16 * g, true);
+    }
+    __syncthreads();
+    for (int rt = 0; rt < 2; ++rt)
+        for (int st = 0; st < 4; ++st) {
+            const int4 sd = *reinterpret_cast<const int4 *>(seeds + 16 * rt + 4 * g);
+            const f32x4 c = __builtin_bit_cast(f32x4, i32x4{sd.x, sd.y, sd.z, sd.w});
+            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+            OpI8Pre::mma16_seed(__builtin_bit_cast(float4, rimg[(2 * rt) * 64 + lane]), __builtin_bit_cast(float4, qimg[(2 * st) * 64 + lane]), acc, c);
+            OpI8Pre::mma16(__builtin_bit_cast(float4, rimg[(2 * rt + 1) * 64 + lane]), __builtin_bit_cast(float4, qimg[(2 * st + 1) * 64 + lane]), acc);
+            const i32x4 o = __builtin_bit_cast(i32x4, acc);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[(16 * rt + 4 * g + e) * 64 + 16 * st + i] = o[e];
+        }
+}
+
+int launch_mfma_i8pre_selftest(const int8_t *q, const int8_t *r, const int *seeds, int *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(mfma_i8pre_selftest_kernel, dim3(1), dim3(64), 0, st, q, r, seeds, out);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
@@ -1917,7 +2143,8 @@ template <class OP>
 static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStream_t st)
 {
     auto kern = [] {   // (one kernel per operator: a plain conditional would instantiate both names)
-        if constexpr (OP::kI8) return filter_i8_kernel<OP>;
+        if constexpr (OP::kPre) return filter_i8pre_kernel<OP>;
+        else if constexpr (OP::kI8) return filter_i8_kernel<OP>;
         else if constexpr (OP::kF16) return filter_f16_kernel<OP>;
         else if constexpr (OP::kLazy && OP::kTile16) return filter_lazy16_kernel<OP>;
         else if constexpr (OP::kLazy) return filter_lazy_kernel<OP>;
@@ -1941,9 +2168,10 @@ static int launch_filter_t(const FilterGeom &g, const FilterArgs &args, hipStrea
 
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
-                  hipStream_t st)
+                  hipStream_t st, const FilterPreArgs *pre)
 {
     FilterArgs a;
+    a.pre = pre ? *pre : FilterPreArgs{};
     a.qimg = reinterpret_cast<const float4 *>(qimg);
     a.rimg = reinterpret_cast<const char *>(rimg);
     a.rimg_lo = g.lazy_img ? a.rimg + (size_t)g.n_pad * g.kt * 2 : nullptr;   // (split operands only)
@@ -1968,7 +2196,14 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
         NNS_HIP(hipMemsetAsync(a.stamps, 0, (nwg * 4 + 8) * sizeof(unsigned long long), st));
     }
 #endif
-    const int rc = with_filter_op(g, [&](auto op) { return launch_filter_t<decltype(op)>(g, a, st); });
+    if (pre && !(g.lazy && g.kt == 128 && LazyOp128::kTile16)) {
+        set_error("MFMA filter: the int8 pre-pass serves the lazy 16x16 kernel at kt = 128 (kt = %d, lazy %d)", g.kt, g.lazy);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    int rc = with_filter_op(g, [&](auto op) { return launch_filter_t<decltype(op)>(g, a, st); });
+    // (diagnostic builds: the two launches share a.stamps — the kernel the rule does not name returns before it touches
+    //  them, so the stamps and totals read below are the running kernel's alone)
+    if (rc == NNS_OK && pre) rc = launch_filter_t<OpI8Pre>(g, a, st);
 #ifdef NNS_DIAG
     if (a.stamps) {   // diagnostic: synchronous read-out, median clock over workgroups
         std::vector<unsigned long long> h(nwg * 4 + 8);

@@ -37,6 +37,11 @@ static size_t img_row_bytes(const FilterGeom &g) { return (size_t)g.kt * (g.i8 ?
 // bounds branch: images and norm arrays carry that much padding (+ the over-read of a 128-norm piece)
 static size_t img_bytes(const FilterGeom &g, int pts_pad) { return (size_t)pts_pad * img_row_bytes(g) + 3 * 32768 + 4096; }
 static size_t norm_bytes(const FilterGeom &g, int pts_pad) { return ((size_t)pts_pad + 3 * g.slot_pts + 256) * sizeof(float); }
+// The int8 pre-pass's operands sit behind the image they go with, in the same allocation.  Refs: the int8 region (128
+// bytes per ref; its ring runs up to 16 slots of 8 KiB past the end) and one i32 seed per ref (+ 16 slots of 64).
+// Queries: the q8 image (128 bytes per query) and one bound per query.
+static size_t i8pre_ref_bytes(int n_pad) { return (size_t)n_pad * 128 + 16 * 8192 + ((size_t)n_pad + 16 * 64) * sizeof(int); }
+static size_t i8pre_query_bytes(int m_pad) { return (size_t)m_pad * (128 + sizeof(float)); }
 // below this many queries the AUTO path skips the MFMA filter (and, in the whole-call
 // entry points, its ref pre-pass too)
 static const int kTinyM = 64;
@@ -84,6 +89,8 @@ struct nns_index {
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
     bool split = false;            // fp32 points without NNS_FILTER_BF16 / NNS_FILTER_F32: split-bf16 operands where
                                    // filter_plan enables them (geom.split)
+
+    bool i8pre = false;            // a 128-deep lazy 1-NN index that also keeps the int8 pre-pass's operands
 
     // MFMA path, ref side
     FilterGeom geom{};
@@ -212,8 +219,12 @@ int order_after_default_stream(hipStream_t st)
 // exclude each other.
 static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
 {
-    if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) && bf16) {
-        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split) apply to fp32 points (bf16, fp16 and int8 points use their own filter)");
+    if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE)) && bf16) {
+        set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split, int8 pre-pass) apply to fp32 points (bf16, fp16 and int8 points use their own filter)");
+        return NNS_ERR_INVALID;
+    }
+    if ((flags & NNS_FILTER_I8PRE_OFF) && (flags & NNS_FILTER_I8PRE_FORCE)) {
+        set_error("the int8 pre-pass flags (off, force) exclude each other");
         return NNS_ERR_INVALID;
     }
     if ((flags & NNS_FILTER_BF16) && (flags & NNS_FILTER_F32)) {
@@ -254,11 +265,18 @@ static int prep_refs(nns_index *ix, hipStream_t st)
                                        &ix->scal->r_maxabs_bits, st, ix->bf16 == DT_F16));
         return NNS_OK;
     }
+    I8PreArgs pre{};
+    if (ix->i8pre) {
+        char *const r8 = (char *)ix->rimg + img_bytes(g, g.n_pad);
+        pre.img8 = (uint4 *)r8;
+        pre.seeds = (int *)(r8 + (size_t)g.n_pad * 128 + 16 * 8192);
+        pre.scal = ix->scal;
+    }
     NNS_TRY(launch_prep_mean(ix->k, g.kt, ix->n, (const float *)ix->r_dev, ix->mean_ws, ix->mean,
-                             &ix->scal->r_maxabs_bits, st));
+                             &ix->scal->r_maxabs_bits, st, ix->i8pre ? &ix->scal->i8_cmax_bits : nullptr));
     NNS_TRY(launch_prep_image(ix->k, g.kt, ix->n, g.n_pad, (const float *)ix->r_dev, ix->mean, -2.0f,
                               INFINITY, (float *)ix->rimg, ix->rnorm, &ix->scal->ymax2_bits, nullptr, st,
-                              g.lazy_img ? 3 : g.split ? 2 : ix->mixed ? 1 : 0));
+                              g.lazy_img ? 3 : g.split ? 2 : ix->mixed ? 1 : 0, ix->i8pre ? &pre : nullptr));
     return NNS_OK;
 }
 
@@ -485,7 +503,9 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             const FilterGeom &g = ix->geom;
             size_t ws = 0;
             prep_workspace_bytes(g.kt, &ws);
-            if (pool_alloc(&ix->rimg, img_bytes(g, g.n_pad)) != hipSuccess ||
+            // the int8 pre-pass: a 1-NN index in the 128-deep lazy layout keeps its operands unless told not to
+            ix->i8pre = path == NNS_PATH_MFMA && g.lazy_img && g.kt == 128 && filter_lazy_tile() == 16 && !(flags & NNS_FILTER_I8PRE_OFF);
+            if (pool_alloc(&ix->rimg, img_bytes(g, g.n_pad) + (ix->i8pre ? i8pre_ref_bytes(g.n_pad) : 0)) != hipSuccess ||
                 pool_alloc(&ix->rnorm, norm_bytes(g, g.n_pad)) != hipSuccess ||
                 pool_alloc(&ix->mean, (size_t)g.kt * sizeof(float)) != hipSuccess ||
                 pool_alloc(&ix->mean_ws, ws) != hipSuccess ||
@@ -594,7 +614,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
         ix->amb_list = nullptr;
         ix->multi_list = nullptr;
         ix->m_cap = 0;
-        if (pool_alloc(&ix->qimg, img_bytes(gq, gq.m_pad)) != hipSuccess ||
+        if (pool_alloc(&ix->qimg, img_bytes(gq, gq.m_pad) + (ix->i8pre ? i8pre_query_bytes(gq.m_pad) : 0)) != hipSuccess ||
             pool_alloc(&ix->qnorm, (size_t)gq.m_pad * sizeof(float)) != hipSuccess ||
             pool_alloc(&ix->amb_list, (size_t)gq.m_pad * sizeof(int)) != hipSuccess ||
             pool_alloc(&ix->multi_list, (size_t)gq.m_pad * sizeof(int)) != hipSuccess) {
@@ -726,20 +746,43 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_BEGIN], st);
     // reset the per-search scalars (q max-abs, ambiguous count); keep the ref-side ones
     static_assert(offsetof(DevScalars, amb_count) == offsetof(DevScalars, q_maxabs_bits) + sizeof(unsigned) &&
-                      offsetof(DevScalars, multi_count) == offsetof(DevScalars, amb_count) + sizeof(int),
+                      offsetof(DevScalars, multi_count) == offsetof(DevScalars, amb_count) + sizeof(int) &&
+                      offsetof(DevScalars, i8_odd_count) == offsetof(DevScalars, multi_count) + sizeof(int) &&
+                      offsetof(DevScalars, i8_ran) == offsetof(DevScalars, i8_odd_count) + sizeof(int),
                   "per-search scalars must be adjacent");
-    NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
+    NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 4 * sizeof(int), st));
+    // the int8 pre-pass serves the lazy kernel's searches (long-stream record form) of an index that keeps its operands
+    const bool use_pre = ix->i8pre && g.lazy && g.kt == 128;
+    FilterPreArgs fpre{};
+    if (use_pre) {
+        const char *const r8 = (const char *)ix->rimg + img_bytes(g, g.n_pad);
+        const char *const q8 = (const char *)ix->qimg + img_bytes(g, g.m_pad);
+        fpre.rimg8 = r8;
+        fpre.rseed = (const int *)(r8 + (size_t)g.n_pad * 128 + 16 * 8192);
+        fpre.q8 = (const float4 *)q8;
+        fpre.qb8 = (const float *)(q8 + (size_t)g.m_pad * 128);
+        fpre.m = m;
+        fpre.force = (ix->flags & NNS_FILTER_I8PRE_FORCE) ? 1 : 0;
+    }
     if (bf16 == DT_I8)
         NNS_TRY(launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st));
     else if (bf16)
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg, ix->qnorm,
                                        nullptr, &ix->scal->q_maxabs_bits, st, bf16 == DT_F16));
-    else
+    else {
+        I8PreArgs qpre{};
+        if (use_pre) {
+            qpre.img8 = (uint4 *)fpre.q8;
+            qpre.bound = (float *)fpre.qb8;
+            qpre.scal = ix->scal;
+        }
         NNS_TRY(launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f,
                                   (float *)ix->qimg, ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st,
-                                  g.split ? 2 : ix->mixed ? 1 : 0));
+                                  g.split ? 2 : ix->mixed ? 1 : 0, use_pre ? &qpre : nullptr));
+    }
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_QPREP], st);
-    NNS_TRY(launch_filter(g, ix->qimg, ix->rimg, ix->rnorm, ix->qnorm, ix->scal, ix->lists, ix->counts, st));
+    NNS_TRY(launch_filter(g, ix->qimg, ix->rimg, ix->rnorm, ix->qnorm, ix->scal, ix->lists, ix->counts, st,
+                          use_pre ? &fpre : nullptr));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_FILTER], st);
 #ifdef NNS_DIAG
     // tuning diagnostic for ablated filter builds (-DNNS_FILTER_ABLATE: empty candidate lists would
@@ -1368,6 +1411,30 @@ int nns_index_near_ties(nns_index *ix, int *ids_out, int cap, int *count_out)
     return NNS_OK;
 }
 
+int nns_index_filter_pre(nns_index *ix, int *ran_out)
+{
+    if (!ix || !ran_out) {
+        set_error("nns_index_filter_pre: bad arguments");
+        return NNS_ERR_INVALID;
+    }
+    *ran_out = 0;
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(ix->device));
+    if (!ix->i8pre || !ix->searched || ix->last_path != NNS_PATH_MFMA) return NNS_OK;
+    DevScalars h{};
+    NNS_HIP(hipMemcpyAsync(&h, ix->scal, sizeof(h), hipMemcpyDeviceToHost, ix->last_stream));
+    NNS_HIP(hipStreamSynchronize(ix->last_stream));
+    *ran_out = h.i8_ran;
+    return NNS_OK;
+}
+
+int nns_i8pre_bound(float s, float ex2, float q82, float r8max2, float eymax2, float c0, float *out1)
+{
+    if (!out1) return NNS_ERR_INVALID;
+    *out1 = i8pre_bound(s, ex2, q82, r8max2, eymax2, c0);
+    return NNS_OK;
+}
+
 int nns_index_filter_form(nns_index *ix, int *form_out)
 {
     if (!ix || !form_out) return NNS_ERR_INVALID;
@@ -1433,6 +1500,27 @@ int nns_selftest_mfma_lazy16(const float *q, const float *r, const float *c0, fl
                          hipMemcpy(out_hh, o + no, no * 4, hipMemcpyDeviceToHost) != hipSuccess))
         rc = NNS_ERR_HIP;
     if (rc == NNS_ERR_HIP) set_error("nns_selftest_mfma_lazy16: %s", hipGetErrorString(hipGetLastError()));
+    pool_free(d);
+    return rc;
+}
+
+int nns_selftest_mfma_i8pre(const int8_t *q, const int8_t *r, const int *seeds, int *out)
+{
+    if (!q || !r || !seeds || !out) return NNS_ERR_INVALID;
+    DeviceScope keep_device;
+    NNS_TRY(ensure_device_ok(0));
+    constexpr size_t nq = 64 * 128, nr = 32 * 128, no = 32 * 64;   // (bytes, bytes, ints; every offset 16-byte aligned)
+    char *d = nullptr;
+    NNS_HIP(pool_alloc(&d, nq + nr + 32 * sizeof(int) + no * sizeof(int)));
+    int rc = NNS_OK;
+    if (hipMemcpy(d, q, nq, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + nq, r, nr, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nq + nr, seeds, 32 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        rc = NNS_ERR_HIP;
+    int *o = reinterpret_cast<int *>(d + nq + nr + 32 * sizeof(int));
+    if (rc == NNS_OK)
+        rc = launch_mfma_i8pre_selftest((const int8_t *)d, (const int8_t *)(d + nq), (const int *)(d + nq + nr), o, nullptr);
+    if (rc == NNS_OK && hipMemcpy(out, o, no * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = NNS_ERR_HIP;
+    if (rc == NNS_ERR_HIP) set_error("nns_selftest_mfma_i8pre: %s", hipGetErrorString(hipGetLastError()));
     pool_free(d);
     return rc;
 }

@@ -742,12 +742,60 @@ __host__ __device__ inline bool refs_void(unsigned r_maxabs_bits, bool f16)
 struct DevScalars {
     unsigned r_maxabs_bits;  // max |r| bits (NaN/INF/huge detection)
     unsigned ymax2_bits;     // max centred squared norm over refs
-    // the three per-search words are adjacent: one 12-byte memset resets them
+    // the five per-search words are adjacent: one 20-byte memset resets them
     unsigned q_maxabs_bits;  // max |q| bits
     int amb_count;           // number of ambiguous queries (sent to the exact scan)
     int multi_count;         // number of queries K5 decided among MORE THAN ONE candidate within tau
-    unsigned pad[3];
+    int i8_odd_count;        // int8 pre-pass: real queries whose bound B8_i exceeds 1.5 B_i (K2 on the queries)
+    int i8_ran;              // int8 pre-pass: 1 when this search's filter was the pre-pass kernel (nns_index_filter_pre)
+    // the int8 pre-pass of a 128-deep lazy index (K2 on the refs; fp32 bits, uint-ordered like the norms):
+    unsigned i8_cmax_bits;   // largest centred |ref coordinate|, rounded up: the shared scale is s = cmax / 127
+    unsigned i8_r8max2_bits; // max |r8|^2 over the refs, r8 = clamp(rint(y' / s), +-127)
+    unsigned i8_eymax2_bits; // max |e_y|^2 over the refs, e_y = y' / s - r8
 };
+
+// What K2 adds for the int8 pre-pass (image_kernel<128, BF, I8>).  Refs (I8 = 1): img8 = -r8 in image_i8_kernel's lane
+// map at depth 128 (1 KiB fragment 2 t + ks: point tile t, k-step ks of 64 dims; 4 KiB per 32-ref block), seeds[j] =
+// floor(|y'_j|^2 / (2 s^2)) (padding refs: kI8PrePadSeed), and the two maxima above.  Queries (I8 = 2): img8 = q8 in the
+// same map, bound[i] = B8_i (i8pre_bound).
+struct I8PreArgs {
+    uint4 *img8;
+    int *seeds;
+    float *bound;
+    DevScalars *scal;
+};
+// The selection rule of the pre-pass, evaluated on the device by both filter kernels of a search (the one it does not
+// name returns at once): the scale is valid — cmax finite, not huge, and not so small that 1 / (2 s^2) leaves fp32 — and,
+// unless forced, at most m / 64 queries have a bound above 1.5 B (the factor and the share are conditions, not
+// measurements: they cap the pre-pass's flags near lazy16's for all but a sliver of the queries).
+__host__ __device__ inline bool i8pre_scale_valid(unsigned cmax_bits)
+{
+    const float cmax = __builtin_bit_cast(float, cmax_bits);
+    return cmax >= 1e-15f && cmax < kHuge;   // (NaN: false)
+}
+__host__ __device__ inline bool i8pre_selected(unsigned cmax_bits, int odd_count, int m, bool force)
+{
+    return i8pre_scale_valid(cmax_bits) && (force || (long long)odd_count * 64 <= (long long)m);
+}
+// Seed of a padding ref and start value of the accumulators: above every integer threshold (<= kI8PreThrMax), and adding
+// a dot product of two int8 rows (|q8.r8| <= 128 * 127^2 < 2^21) cannot overflow it.
+constexpr int kI8PrePadSeed = 0x3FFFFFFF;
+constexpr int kI8PreThrMax = 1 << 29;
+
+// B8 of the int8 pre-pass: how far 2 s^2 (N_j - q8_i.r8_j) can lie ABOVE the three-product score of the pair, in score
+// units.  With x' = s (q8 + e_x), y' = s (r8 + e_y):  |y'|^2 - 2 x'.y' = 2 s^2 (|y'|^2 / (2 s^2) - q8.r8) - 2 s^2 (q8.e_y +
+// e_x.r8 + e_x.e_y), and Cauchy-Schwarz on the three cross terms with the refs' maxima gives
+//   2 s^2 (N_j - q8.r8) <= score + 2 s^2 (|e_x| R8 + |q8| EY + |e_x| EY)        (N_j <= |y'|^2 / (2 s^2): the floor helps).
+// ex2 = |e_x|^2 and q82 = |q8|^2 are the query's ACTUAL sums (a clipped coordinate is in e_x), r8max2 / eymax2 the refs'.
+// c0 (tau_consts mode 3, >= 2 e3) covers the three-product score against the exact one; the factor covers the fp32
+// evaluation of e_x and of the sums; two integer units (2 * 2 s^2) cover the kernel's rounding of the threshold.
+__host__ __device__ inline float i8pre_bound(float s, float ex2, float q82, float r8max2, float eymax2, float c0)
+{
+    const double s2 = 2.0 * (double)s * (double)s;
+    const double ex = sqrt((double)ex2), q8 = sqrt((double)q82), r8 = sqrt((double)r8max2), ey = sqrt((double)eymax2);
+    const double b = s2 * (ex * r8 + q8 * ey + ex * ey) * (1.0 + 0x1p-10) + (double)c0 + 2.0 * s2;
+    return (float)(b * (1.0 + 1e-6));
+}
 
 // ---- launchers (each .hip file owns its kernels) --------------------------------
 // exact_kernels.hip
@@ -784,12 +832,14 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
 
 // prep_kernels.hip (K2)
 int prep_workspace_bytes(int kt, size_t *bytes);
+// cmax_bits (optional; the int8 pre-pass): also reduce the per-dimension minimum and maximum and leave the largest
+// centred |coordinate|, rounded up, in that word (uint-ordered max: zero it first)
 int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws,
-                     float *mean, unsigned *maxabs_bits, hipStream_t st);
+                     float *mean, unsigned *maxabs_bits, hipStream_t st, unsigned *cmax_bits = nullptr);
 int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts,
                       const float *mean, float scale, float pad_norm,
                       float *img, float *norms, unsigned *max_norm_bits,
-                      unsigned *maxabs_bits, hipStream_t st, int form = 0);
+                      unsigned *maxabs_bits, hipStream_t st, int form = 0, const I8PreArgs *i8 = nullptr);
 
 // form: 0 fp32 image, 1 bf16-rounded operands, 2 split-bf16 operands (hi, lo fragment per k-step), 3 the same values in
 // the lazy layout: the hi fragments of all blocks ([npts_pad / 32][kt / 16] KiB), then the lo fragments likewise
@@ -812,6 +862,16 @@ int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pt
                          float *norms, unsigned *max_norm_bits, hipStream_t st);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
+// the int8 pre-pass's operands beside the lazy image (K2, I8PreArgs): given to launch_filter, a lazy search at kt = 128
+// runs filter_i8pre_kernel instead of filter_lazy16_kernel
+struct FilterPreArgs {
+    const char *rimg8;    // [n_pad / 32][4 KiB] + ring over-read
+    const int *rseed;     // [n_pad] + ring over-read
+    const float4 *q8;     // [m_pad / 16][2][64 lanes]
+    const float *qb8;     // [m_pad]
+    int m;                // real queries of the search
+    int force;            // NNS_FILTER_I8PRE_FORCE: run the pre-pass whatever the count says
+};
 // split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth
 // f16 (with bf16 = true): fp16 points — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
 // i8 (with bf16 = true): int8 points — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of
@@ -821,7 +881,8 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = fals
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
-                  hipStream_t st);
+                  hipStream_t st, const FilterPreArgs *pre = nullptr);
+int launch_mfma_i8pre_selftest(const int8_t *q, const int8_t *r, const int *seeds, int *out, hipStream_t st);
 int launch_mfma_lazy16_selftest(const float *q, const float *r, const float *c0, float *out, float *out_hh, hipStream_t st);
 int filter_lazy_tile();   // MFMA tile (16 or 32) of the lazy split kernel this build launches (NNS_F_LAZY_T16)
 int launch_mfma_selftest(int kt, int bf16, const float *a, const float *b, const float *c0, float *out,

@@ -36,20 +36,24 @@ __device__ __forceinline__ void max_word(unsigned *word, unsigned v)
 
 int prep_workspace_bytes(int kt, size_t *bytes)
 {
-    *bytes = (size_t)PREP_MEAN_BLOCKS * kt * sizeof(double);
+    // (+ two floats per block and dimension: the minima and maxima the int8 pre-pass's scale comes from)
+    *bytes = (size_t)PREP_MEAN_BLOCKS * kt * (sizeof(double) + 2 * sizeof(float));
     return NNS_OK;
 }
 
 // stage 1: per-block column sums.  Thread (rl, c4): c4 walks the dims four at a time (one
 // 16-byte load per lane when k % 4 == 0), rl walks the rows, so a wave reads consecutive
 // bytes.  Sums are fp64 in a fixed order -> the mean is deterministic.
-template <int VEC>
+// MM: also the block's per-dimension minimum and maximum -> minmax[blk][0 | 1][kt] (a dimension the block read nothing
+// of: +INF, -INF)
+template <int VEC, bool MM = false>
 __global__ __launch_bounds__(256) void colsum_kernel(int k, int kt, int n, int rows_per_block,
                                                      const float *__restrict__ r,
                                                      double *__restrict__ partial,
-                                                     unsigned *__restrict__ maxabs_bits)
+                                                     unsigned *__restrict__ maxabs_bits,
+                                                     float *__restrict__ minmax = nullptr)
 {
-    extern __shared__ double ssum[];   // [rl_count][kt]
+    extern __shared__ double ssum[];   // [rl_count][kt] (MM: + [2][rl_count][kt] floats)
     const int cgroups = kt / VEC;                       // column groups per row
     const int cw = cgroups < 256 ? cgroups : 256;
     const int rl_count = 256 / cw;
@@ -61,8 +65,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(int k, int kt, int n, int r
     unsigned mx = 0;
     for (int g = g0; g < cgroups; g += cw) {
         double acc[VEC];
+        float lo[VEC], hi[VEC];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[e] = 0.0;
+        for (int e = 0; e < VEC; ++e) {
+            acc[e] = 0.0;
+            lo[e] = INFINITY;
+            hi[e] = -INFINITY;
+        }
         const int c = g * VEC;
         if (c < k && rl < rl_count)
             for (int j = row0 + rl; j < row1; j += rl_count) {
@@ -81,17 +90,38 @@ __global__ __launch_bounds__(256) void colsum_kernel(int k, int kt, int n, int r
                     acc[e] += (double)v[e];
                     const unsigned b = __float_as_uint(v[e]) & 0x7FFFFFFFu;
                     mx = b > mx ? b : mx;
+                    if constexpr (MM) {
+                        lo[e] = fminf(lo[e], v[e]);
+                        hi[e] = fmaxf(hi[e], v[e]);
+                    }
                 }
             }
         if (rl < rl_count)
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) ssum[rl * kt + c + e] = acc[e];
+            for (int e = 0; e < VEC; ++e) {
+                ssum[rl * kt + c + e] = acc[e];
+                if constexpr (MM) {
+                    float *smm = reinterpret_cast<float *>(ssum + rl_count * kt);
+                    smm[rl * kt + c + e] = lo[e];
+                    smm[(rl_count + rl) * kt + c + e] = hi[e];
+                }
+            }
     }
     __syncthreads();
     for (int c = threadIdx.x; c < kt; c += 256) {
         double acc = 0.0;
         for (int i = 0; i < rl_count; ++i) acc += ssum[i * kt + c];   // fixed order
         partial[(size_t)blockIdx.x * kt + c] = acc;
+        if constexpr (MM) {
+            const float *smm = reinterpret_cast<const float *>(ssum + rl_count * kt);
+            float lo = INFINITY, hi = -INFINITY;
+            for (int i = 0; i < rl_count; ++i) {
+                lo = fminf(lo, smm[i * kt + c]);
+                hi = fmaxf(hi, smm[(rl_count + i) * kt + c]);
+            }
+            minmax[((size_t)blockIdx.x * 2) * kt + c] = lo;
+            minmax[((size_t)blockIdx.x * 2 + 1) * kt + c] = hi;
+        }
     }
     // wave max then one atomic per wave
 #pragma unroll
@@ -103,8 +133,11 @@ __global__ __launch_bounds__(256) void colsum_kernel(int k, int kt, int n, int r
 }
 
 // stage 2: one workgroup per dimension, fixed-shape tree over the partials -> fp32 mean
+// minmax / cmax_bits (the int8 pre-pass, both or neither): the dimension's extremes over the blocks, and the largest
+// centred |coordinate| over the dimensions, max_t max(max_t - c_t, c_t - min_t) rounded up, as a uint-ordered max word
 __global__ __launch_bounds__(256) void mean_kernel(int kt, int nblocks, int n, const double *__restrict__ partial,
-                                                   float *__restrict__ mean)
+                                                   float *__restrict__ mean, const float *__restrict__ minmax = nullptr,
+                                                   unsigned *__restrict__ cmax_bits = nullptr)
 {
     __shared__ double red[256];
     const int c = blockIdx.x;
@@ -116,11 +149,37 @@ __global__ __launch_bounds__(256) void mean_kernel(int kt, int nblocks, int n, c
         if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
         __syncthreads();
     }
-    if (threadIdx.x == 0) mean[c] = (float)(red[0] / (double)n);
+    const float mc = (float)(red[0] / (double)n);
+    if (threadIdx.x == 0) mean[c] = mc;
+    if (minmax) {
+        __shared__ float rlo[256], rhi[256];
+        float lo = INFINITY, hi = -INFINITY;
+        for (int b = threadIdx.x; b < nblocks; b += 256) {
+            lo = fminf(lo, minmax[((size_t)b * 2) * kt + c]);
+            hi = fmaxf(hi, minmax[((size_t)b * 2 + 1) * kt + c]);
+        }
+        rlo[threadIdx.x] = lo;
+        rhi[threadIdx.x] = hi;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (threadIdx.x < off) {
+                rlo[threadIdx.x] = fminf(rlo[threadIdx.x], rlo[threadIdx.x + off]);
+                rhi[threadIdx.x] = fmaxf(rhi[threadIdx.x], rhi[threadIdx.x + off]);
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && rlo[0] <= rhi[0]) {   // (a padding dimension has no values: centred 0)
+            // the largest |y'| = |fl(y - c)| itself (the same subtraction), a few ulps up
+            float d = fmaxf(__fsub_rn(rhi[0], mc), __fsub_rn(mc, rlo[0]));
+            d = d * (1.0f + 0x1p-22f);
+            if (!(d >= 0.0f)) d = INFINITY;   // (NaN coordinates: the scale is invalid)
+            max_word(cmax_bits, __float_as_uint(d));
+        }
+    }
 }
 
 int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws, float *mean,
-                     unsigned *maxabs_bits, hipStream_t st)
+                     unsigned *maxabs_bits, hipStream_t st, unsigned *cmax_bits)
 {
     int nblocks = PREP_MEAN_BLOCKS;
     int rows = divup(n, nblocks);
@@ -129,15 +188,30 @@ int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws, f
     const bool vec = (k % 4 == 0) && (((uintptr_t)r & 15) == 0);
     const int cgroups = vec ? kt / 4 : kt;
     const int cw = cgroups < 256 ? cgroups : 256;
-    const size_t lds = (size_t)(256 / cw) * kt * sizeof(double);
+    size_t lds = (size_t)(256 / cw) * kt * sizeof(double);
+    float *minmax = reinterpret_cast<float *>(partial_ws + (size_t)PREP_MEAN_BLOCKS * kt);   // (behind the sums)
+    if (cmax_bits) {
+        lds += (size_t)(256 / cw) * kt * 2 * sizeof(float);
+        if (vec)
+            hipLaunchKernelGGL((colsum_kernel<4, true>), dim3(nblocks), dim3(256), lds, st, k, kt, n, rows, r, partial_ws,
+                               maxabs_bits, minmax);
+        else
+            hipLaunchKernelGGL((colsum_kernel<1, true>), dim3(nblocks), dim3(256), lds, st, k, kt, n, rows, r, partial_ws,
+                               maxabs_bits, minmax);
+        NNS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(mean_kernel, dim3(kt), dim3(256), 0, st, kt, nblocks, n, partial_ws, mean, minmax, cmax_bits);
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
+    }
     if (vec)
         hipLaunchKernelGGL(colsum_kernel<4>, dim3(nblocks), dim3(256), lds, st, k, kt, n, rows, r, partial_ws,
-                           maxabs_bits);
+                           maxabs_bits, (float *)nullptr);
     else
         hipLaunchKernelGGL(colsum_kernel<1>, dim3(nblocks), dim3(256), lds, st, k, kt, n, rows, r, partial_ws,
-                           maxabs_bits);
+                           maxabs_bits, (float *)nullptr);
     NNS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mean_kernel, dim3(kt), dim3(256), 0, st, kt, nblocks, n, partial_ws, mean);
+    hipLaunchKernelGGL(mean_kernel, dim3(kt), dim3(256), 0, st, kt, nblocks, n, partial_ws, mean, (const float *)nullptr,
+                       (unsigned *)nullptr);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
@@ -150,13 +224,18 @@ int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws, f
 // value v becomes h = rn_bf16(v) and l = rn_bf16(v - h) (v - h is exact in fp32), written as two 1 KiB
 // fragments per 16-dim k-step in the v_mfma_f32_32x32x16_bf16 operand order (lane = 32 hl + i, dims
 // 16 s + 8 hl .. + 7): fragment 2 s = hi, 2 s + 1 = lo.  The block keeps the fp32 image's bytes (KT / 8 fragments).
-template <int KT, int BF = 0>
-__global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float *__restrict__ pts,
-                                                    const float *__restrict__ mean, float scale,
-                                                    float pad_norm, float *__restrict__ img,
-                                                    float *__restrict__ norms,
-                                                    unsigned *__restrict__ max_norm_bits,
-                                                    unsigned *__restrict__ maxabs_bits)
+// I8 (the int8 pre-pass of a 128-deep lazy index, beside the BF = 3 / 2 image; I8PreArgs, nns_internal.h): the centred
+// values once more as int8 under the shared scale s = cmax / 127 — v = y' / s, r8 = clamp(rint(v), +-127), e = v - r8 — in
+// image_i8_kernel's lane map at depth 128 (fragment 2 t + ks: lane l holds dims 64 ks + 16 (l >> 4) .. + 15 of point
+// 16 t + (l & 15)).  1 (refs): the image holds -r8, so that the filter's accumulator, seeded with N_j = floor(|y'_j|^2 /
+// (2 s^2)), ends as N_j - q8.r8; max |r8|^2 and max |e_y|^2 go to their words.  2 (queries): q8 and the bound B8_i.
+template <int KT, int BF, int I8>
+__device__ __forceinline__ void image_body(int k, int npts, const float *__restrict__ pts,
+                                           const float *__restrict__ mean, float scale,
+                                           float pad_norm, float *__restrict__ img,
+                                           float *__restrict__ norms,
+                                           unsigned *__restrict__ max_norm_bits,
+                                           unsigned *__restrict__ maxabs_bits, const I8PreArgs *x)
 {
     constexpr int LD = KT + 4;                  // padded row (floats), keeps float4 alignment
     __shared__ __attribute__((aligned(16))) float tile[32 * LD];
@@ -219,9 +298,11 @@ __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float
         nrm[i][part] = acc;
     }
     __syncthreads();
+    double nsq = 0.0;   // (I8: the row's squared norm once more, for the seed)
     if (tid < 32) {
         double acc = 0.0;
         for (int p = 0; p < 8; ++p) acc += nrm[tid][p];
+        nsq = acc;
         float nv = (float)acc;
         unsigned nb = 0;
         if (p0 + tid >= npts) nv = pad_norm;           // padding never wins (refs: +INF)
@@ -304,6 +385,100 @@ __global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float
         mx = o > mx ? o : mx;
     }
     if ((tid & 63) == 0 && maxabs_bits) max_word(maxabs_bits, mx);
+
+    if constexpr (I8 != 0) {
+        static_assert(KT == 128, "the int8 pre-pass is 128 deep: four fragments per block, one per wave");
+        __shared__ float pe2[32][8];
+        __shared__ int pr2[32][8];
+        const float cmax = __uint_as_float(x->scal->i8_cmax_bits);
+        const bool valid = i8pre_scale_valid(x->scal->i8_cmax_bits);   // (all refs equal, INF / NaN / huge: no scale)
+        const float s = cmax / 127.0f;
+        const float inv = valid ? 127.0f / cmax : 0.0f;
+        const int frag = tid >> 6, lane = tid & 63;
+        const int i = 16 * (frag >> 1) + (lane & 15), d0 = 64 * (frag & 1) + 16 * (lane >> 4);
+        unsigned w[4];
+        float e2 = 0.0f;
+        int r2 = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            w[e] = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const float v = tile[i * LD + d0 + 4 * e + b] * inv;
+                const float r = fminf(fmaxf(rintf(v), -127.0f), 127.0f);   // (NaN -> -127: such inputs never reach the filter's answer)
+                const float d = v - r;
+                e2 += d * d;
+                const int ri = (int)r;
+                r2 += ri * ri;
+                w[e] |= (unsigned)(unsigned char)(int8_t)(I8 == 1 ? -ri : ri) << (8 * b);
+            }
+        }
+        x->img8[(size_t)blk * 256 + tid] = make_uint4(w[0], w[1], w[2], w[3]);
+        pe2[i][4 * (frag & 1) + (lane >> 4)] = e2;
+        pr2[i][4 * (frag & 1) + (lane >> 4)] = r2;
+        __syncthreads();
+        if (tid < 32) {
+            float es = 0.0f;
+            int rs = 0;
+            for (int p = 0; p < 8; ++p) {
+                es += pe2[tid][p];
+                rs += pr2[tid][p];
+            }
+            es *= 1.0f + 0x1p-20f;   // (the fp32 sum of 128 squares, rounded up)
+            const bool live = p0 + tid < npts;
+            if constexpr (I8 == 1) {
+                int seed = kI8PrePadSeed;
+                if (live && valid) {
+                    const double q = nsq / (2.0 * (double)s * (double)s);
+                    seed = q < (double)kI8PreThrMax ? (int)q : kI8PrePadSeed;   // (floor of a value >= 0)
+                }
+                x->seeds[p0 + tid] = seed;
+                unsigned eb = live ? __float_as_uint(es) : 0u, rb = live ? __float_as_uint((float)rs) : 0u;
+#pragma unroll
+                for (int off = 16; off > 0; off >>= 1) {
+                    const unsigned oe = __shfl_xor(eb, off, 64), orr = __shfl_xor(rb, off, 64);
+                    eb = oe > eb ? oe : eb;
+                    rb = orr > rb ? orr : rb;
+                }
+                if (tid == 0) {
+                    max_word(&x->scal->i8_eymax2_bits, eb);
+                    max_word(&x->scal->i8_r8max2_bits, rb);
+                }
+            } else {
+                const float c0 = tau_consts(KT, (float)nsq, __uint_as_float(x->scal->ymax2_bits), 3).c0;
+                const float b8 = valid ? i8pre_bound(s, es, (float)rs, __uint_as_float(x->scal->i8_r8max2_bits),
+                                                     __uint_as_float(x->scal->i8_eymax2_bits), c0)
+                                       : INFINITY;
+                x->bound[p0 + tid] = b8;
+                // the selection rule's count (an integer sum: the same whatever the order)
+                const bool odd = live && !(b8 <= 1.5f * split_lazy_bound(KT, (float)nsq, __uint_as_float(x->scal->ymax2_bits)));
+                const unsigned long long om = __builtin_amdgcn_ballot_w64(odd);
+                if (tid == 0 && om != 0ull) atomicAdd(&x->scal->i8_odd_count, __builtin_popcountll(om));
+            }
+        }
+    }
+}
+
+template <int KT, int BF = 0>
+__global__ __launch_bounds__(256) void image_kernel(int k, int npts, const float *__restrict__ pts,
+                                                    const float *__restrict__ mean, float scale,
+                                                    float pad_norm, float *__restrict__ img,
+                                                    float *__restrict__ norms,
+                                                    unsigned *__restrict__ max_norm_bits,
+                                                    unsigned *__restrict__ maxabs_bits)
+{
+    image_body<KT, BF, 0>(k, npts, pts, mean, scale, pad_norm, img, norms, max_norm_bits, maxabs_bits, nullptr);
+}
+// ... with the int8 pre-pass's operands (I8 = 1 refs beside the lazy image, 2 queries beside the split image)
+template <int BF, int I8>
+__global__ __launch_bounds__(256) void image_i8pre_kernel(int k, int npts, const float *__restrict__ pts,
+                                                          const float *__restrict__ mean, float scale,
+                                                          float pad_norm, float *__restrict__ img,
+                                                          float *__restrict__ norms,
+                                                          unsigned *__restrict__ max_norm_bits,
+                                                          unsigned *__restrict__ maxabs_bits, const I8PreArgs x)
+{
+    image_body<128, BF, I8>(k, npts, pts, mean, scale, pad_norm, img, norms, max_norm_bits, maxabs_bits, &x);
 }
 
 // NNS_FILTER_BF16 at KT = 512 (fp32 points, 256 < k <= 512; operands in the 32x32x16 order 0 of
@@ -465,9 +640,23 @@ __global__ __launch_bounds__(256) void image_deep_kernel(int k, int npts, const 
 
 int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, const float *mean,
                       float scale, float pad_norm, float *img, float *norms,
-                      unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form)
+                      unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form, const I8PreArgs *i8)
 {
     const int blocks = npts_pad / 32;
+    if (i8) {   // refs (form 3) or queries (form 2) of a 128-deep lazy index, with the int8 pre-pass's operands
+        if (kt != 128 || (form != 3 && form != 2)) {
+            set_error("prep: the int8 pre-pass goes with the split image at tile K 128 (kt = %d, form %d)", kt, form);
+            return NNS_ERR_UNSUPPORTED;
+        }
+        if (form == 3)
+            hipLaunchKernelGGL((image_i8pre_kernel<3, 1>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm,
+                               img, norms, max_norm_bits, maxabs_bits, *i8);
+        else
+            hipLaunchKernelGGL((image_i8pre_kernel<2, 2>), dim3(blocks), dim3(256), 0, st, k, npts, pts, mean, scale, pad_norm,
+                               img, norms, max_norm_bits, maxabs_bits, *i8);
+        NNS_HIP(hipGetLastError());
+        return NNS_OK;
+    }
     if (form == 3) {   // split-bf16 operands in the lazy layout (the depths of the lazy kernel)
         if (kt != 128) {
             set_error("prep: the lazy split layout is built at tile K 128 only (kt = %d)", kt);

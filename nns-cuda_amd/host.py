@@ -38,6 +38,10 @@ NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three
 # split-bf16 operands, 8 <= k <= 256; bf16 points on exact operands, 32 <= k <= 256
 NNS_RANGE_MFMA = 4096
 NNS_TOPK_MFMA = 8192
+# the int8 pre-pass of the 128-deep lazy filter: off / force ("auto": neither; the device decides per search)
+NNS_FILTER_I8PRE_OFF = 16384
+NNS_FILTER_I8PRE_FORCE = 32768
+_I8PRE = {"auto": 0, "off": NNS_FILTER_I8PRE_OFF, "force": NNS_FILTER_I8PRE_FORCE}
 # "mfma_perref": the MFMA filter with per-score candidate records forced (the long-stream form) at any size
 _PATHS = {"auto": NNS_PATH_AUTO, "exact": NNS_PATH_EXACT, "mfma": NNS_PATH_MFMA,
           "mfma_perref": NNS_PATH_MFMA | NNS_RECORDS_PER_REF}
@@ -63,6 +67,7 @@ ABI_SYMBOLS = (
     "nns_index_create_f16", "nns_index_search_f16", "nns_search_f16_ex", "nns_search_f16_topk", "nns_search_f16_range",
     "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk", "nns_search_i8_range",
     "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk", "nns_search_b1_range",
+    "nns_index_filter_pre", "nns_i8pre_bound", "nns_selftest_mfma_i8pre",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
@@ -73,7 +78,8 @@ OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
                     "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk",
                     "nns_search_i8_range",
                     "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk",
-                    "nns_search_b1_range")
+                    "nns_search_b1_range",
+                    "nns_index_filter_pre", "nns_i8pre_bound", "nns_selftest_mfma_i8pre")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -188,7 +194,10 @@ def _load() -> ctypes.CDLL:
                 "nns_index_search_b1": lib.nns_index_search.argtypes,
                 "nns_search_b1_ex": lib.nns_search_f32_ex.argtypes,
                 "nns_search_b1_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_b1_range": lib.nns_search_f32_range.argtypes}
+                "nns_search_b1_range": lib.nns_search_f32_range.argtypes,
+                "nns_index_filter_pre": [c_vp, ctypes.POINTER(c_int)],
+                "nns_i8pre_bound": [ctypes.c_float] * 6 + [c_vp],
+                "nns_selftest_mfma_i8pre": [c_vp, c_vp, c_vp, c_vp]}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -255,9 +264,28 @@ def selftest_mfma_lazy16(q: np.ndarray, r: np.ndarray, c0: np.ndarray):
     return out, out_hh
 
 
+def selftest_mfma_i8pre(q: np.ndarray, r: np.ndarray, seeds: np.ndarray) -> np.ndarray:
+    """nns_selftest_mfma_i8pre: [32 refs][64 queries] int32 accumulators seeds[ref] - q.r of the int8 pre-pass's chain.
+    q [64][128], r [32][128] int8, seeds [32] int32."""
+    q = np.ascontiguousarray(q, np.int8)
+    r = np.ascontiguousarray(r, np.int8)
+    seeds = np.ascontiguousarray(seeds, np.int32)
+    assert q.shape == (64, 128) and r.shape == (32, 128) and seeds.shape == (32,)
+    out = np.empty((32, 64), np.int32)
+    _check(lib.nns_selftest_mfma_i8pre(q.ctypes.data, r.ctypes.data, seeds.ctypes.data, out.ctypes.data), "nns_selftest_mfma_i8pre")
+    return out
+
+
 def filter_lazy_tile() -> int:
     """nns_filter_lazy_tile: 16 or 32, the MFMA tile of the lazy split kernel this build launches."""
     return int(lib.nns_filter_lazy_tile())
+
+
+def i8pre_bound(s: float, ex2: float, q82: float, r8max2: float, eymax2: float, c0: float) -> float:
+    """B8 of the int8 pre-pass for one query (nns_i8pre_bound)."""
+    out = np.empty(1, np.float32)
+    _check(lib.nns_i8pre_bound(s, ex2, q82, r8max2, eymax2, c0, out.ctypes.data), "nns_i8pre_bound")
+    return float(out[0])
 
 
 def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
@@ -737,12 +765,14 @@ class Index:
 
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
                  soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False,
-                 filter_split_eager: bool = False, range_mfma: bool = False, topk_mfma: bool = False):
+                 filter_split_eager: bool = False, range_mfma: bool = False, topk_mfma: bool = False,
+                 filter_i8pre: str = "auto"):
         """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
         filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
         filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER).
         range_mfma: range searches of this index go through the MFMA flag pass (NNS_RANGE_MFMA).
         topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA).
+        filter_i8pre: "auto" | "off" | "force" — the int8 pre-pass of the 128-deep lazy filter (NNS_FILTER_I8PRE_*).
         A torch.uint8 [n][kb] tensor is a set of packed binary points (pack_bits' layout; kb % 4 == 0, 4-byte aligned):
         Hamming distance, self.k = 8 * kb bits, self.b1 is true, queries are uint8 [m][kb] likewise."""
         import torch
@@ -764,7 +794,7 @@ class Index:
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
             | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
             | (NNS_FILTER_SPLIT_EAGER if filter_split_eager else 0) | (NNS_RANGE_MFMA if range_mfma else 0) \
-            | (NNS_TOPK_MFMA if topk_mfma else 0)
+            | (NNS_TOPK_MFMA if topk_mfma else 0) | _I8PRE[filter_i8pre]
         self.flags = flags
         h = ctypes.c_void_p()
         create = lib.nns_index_create_b1 if self.b1 else lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
@@ -772,6 +802,12 @@ class Index:
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
         self._h = h
+
+    def filter_pre(self) -> bool:
+        """Did the last search's filter run the int8 pre-pass kernel?  (nns_index_filter_pre: waits for the index's stream)"""
+        ran = ctypes.c_int(0)
+        _check(lib.nns_index_filter_pre(self._h, ctypes.byref(ran)), "nns_index_filter_pre")
+        return bool(ran.value)
 
     def refresh(self, stream=None) -> None:
         _check(lib.nns_index_refresh(self._h, _stream_ptr(stream)), "nns_index_refresh")

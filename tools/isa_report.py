@@ -62,12 +62,12 @@ path = m.compile_isa()
 txt = open(path).read()
 for b in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", txt, flags=re.S):
     name = re.search(r"\.name:\s+(\S+)", b).group(1)
-    if "filter_kernel" not in name:
+    if "filter_kernel" not in name and "filter_i8pre_kernel" not in name:   # (the int8 pre-pass: a kernel name of its own)
         continue
     g = lambda k: re.search(r"\.%s:\s+(\d+)" % k, b).group(1)
     print(name[20:62], "vgpr", g("vgpr_count"), "sgpr", g("sgpr_count"), "spill", g("vgpr_spill_count"), "scratch", g("private_segment_fixed_size"))
 lines = txt.splitlines()
-for sym in [l.split(":")[0] for l in lines if l.startswith("_ZN3nns13filter_kernel") and "@" in l]:
+for sym in [l.split(":")[0] for l in lines if l.startswith(("_ZN3nns13filter_kernel", "_ZN3nns19filter_i8pre_kernel")) and "@" in l]:
     start = next(i for i, l in enumerate(lines) if l.startswith(sym + ":"))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
     body = lines[start:end]
