@@ -146,6 +146,7 @@ struct OpBase {
     static constexpr int kRingDepth = 4;      // ring slots
     static constexpr bool kDmaBurst = false;  // a slot's ring DMA pieces one per step (true: back to back, see the interval)
     static constexpr bool kTile16 = false;    // 32x32 MFMA tiles: a lane owns one query per query block
+    static constexpr int kGroup = 1;          // intervals per workgroup barrier (OpI8Pre: NNS_F_PRE_GROUP, see pre_cadence_ok)
     static constexpr int kLPQ = 2;            // candidate lists (list lanes) per query and split: FilterGeom.lpq
     // the lanes' tau constants (c0, x2 per state) stay in registers: an LDS round trip on the slow path
     // queues behind the whole workgroup's fragment reads (measured: ~900 cycles each under this load)
@@ -443,8 +444,13 @@ struct OpLazySplit16 : OpBF16T<8> {
 // rl.qh per k-step), every operand loaded from global memory inside the branch.  Lists, plan and K5 are OpLazySplit16's.
 struct OpI8Pre : OpBF16T<4> {
     static constexpr int kSlotSteps = 8;
-    static constexpr int kRingDepth = 16;
+    static constexpr int kRingDepth = kI8PreRingDepth;
     static constexpr bool kPre = true;
+    // One barrier per kGroup intervals.  A refinement stalls its wave for longer than an interval; with a barrier at every
+    // interval the seven other waves wait it out, with one per group they run on inside the group and the stalled wave's
+    // SIMD partner has the MFMA pipe to itself meanwhile.  A wave's thresholds depend on its own stream alone, so the lists
+    // are the same whatever the cadence.
+    static constexpr int kGroup = kI8PreGroup;
     static constexpr int kLPQ = 2;
     // (the builtin, as OpI8: 32 resident operand registers leave the allocator room, and it keeps the read hazards)
     __device__ static __forceinline__ void mma16(const float4 &a, const float4 &b, f32x4 &acc)
@@ -559,12 +565,14 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #endif
     constexpr bool kLazyShare = NNS_F_LAZY_SHARE != 0;
     // The pre-pass ring of sixteen: an interval is half the lazy one, so twice as many slots ahead keep a piece's landing time
-#ifndef NNS_F_PRE_AHEAD
-#define NNS_F_PRE_AHEAD 8
-#endif
+    // (NNS_F_PRE_AHEAD, default 8: nns_internal.h)
     constexpr bool PRE = OP::kPre;
-    constexpr int AHEAD = PRE ? NNS_F_PRE_AHEAD : LAZY ? NNS_F_LAZY_AHEAD : OP::kLag ? 2 : 3;
+    constexpr int AHEAD = PRE ? kI8PreAhead : LAZY ? NNS_F_LAZY_AHEAD : OP::kLag ? 2 : 3;
     static_assert(AHEAD >= 2 && AHEAD <= F_D<OP> - (OP::kLag ? 2 : 1), "a slot is refilled only when no wave reads it any more");
+    // Barrier cadence: sync_slot runs at the intervals s with s % G == 0 and confirms the G slots after slot s
+    constexpr int G = OP::kGroup;
+    static_assert(G == 1 || PRE, "a barrier at every interval everywhere but in the pre-pass");
+    static_assert(!PRE || pre_cadence_ok(F_D<OP>, AHEAD, G), "pre-pass ring: G < AHEAD and AHEAD + G <= ring depth");
     // DMA pieces per wave and slot that the counted vmcnt waits may leave in flight: with the norms issued by one wave
     // per slot, a wave's youngest slot has F_PPW or F_PPW + F_NP pieces — counting F_PPW is safe for both
     // (not the 768-deep tile: 252 of its 256 registers are taken, the turn-taking test spills)
@@ -916,6 +924,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 #ifdef NNS_DIAG
     unsigned diag_slow = 0, diag_tiles = 0;   // slow-path executions / retired (tile, state) pairs of this wave
     unsigned long long diag_cyc = 0;   // s_memtime ticks spent inside record_all (lazy: from the flag to the end of record_all)
+    unsigned long long diag_sync = 0;  // s_memtime ticks spent inside sync_slot: the counted wait and the barrier
 #endif
     auto record_all = [&](const typename OP::Acc &acc, int blk_global, auto st_c) __attribute__((always_inline)) {
         constexpr int st = decltype(st_c)::value;
@@ -1134,6 +1143,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                 // the first rh.qh MFMA, the other three, then rh.ql and rl.qh per k-step), so a refined score has the bits
                 // lazy16 gives it.  Nothing of it is in the ring: rh, rl out of the image's hi and lo regions, qh, ql out
                 // of the query image (all through lazy16_gather), the four norms out of rnorm.
+                // oslot / oin MUST STAY UNUSED here: pre_cadence_ok and the kernel's static_assert rest on an interval reading
+                // its own and the next slot only.  A refinement that re-read the retiring tile's slot (s - 1, as lazy16's does)
+                // would need AHEAD + G < ring depth instead of <=: tools/pre_cadence_check.cpp models that too (reads_prev).
+                (void)oslot, (void)oin;
                 // (the very first tests of a stream see the start accumulators / no masks: nothing there)
                 const bool refine = (any != 0ull) & (oblk >= slot0 * BPS);
                 if (__builtin_expect(refine, 0)) {   // cold: laid out off the MFMA stream
@@ -1151,6 +1164,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
                             const float4 *qs = a.qimg + (size_t)(qblk0 + (st >> 1)) * (QFB * 64);
                             // (every load is issued AND consumed inside the state's branch, all of them in flight before
                             //  the first is used: see the lazy16 refinement below)
+                            // (the ref-side loads once per flagged TILE instead, ahead of the states, measured within the
+                            //  run-to-run spread of this form at C3 and was dropped: DESIGN, "Barrier cadence of the pre-pass")
                             float4 rh[NK], rl[NK], qh[NK], ql[NK];
                             const float4 nv = *reinterpret_cast<const float4 *>(a.rnorm + jbase);
 #pragma unroll
@@ -1463,9 +1478,12 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     auto ring = [&](int s) __attribute__((always_inline)) { return smem + ((s + F_D<OP>) & (F_D<OP> - 1)) * F_SLOT_BYTES<OP>; };
     static_assert((F_D<OP> & (F_D<OP> - 1)) == 0, "ring depth must be a power of two");
 
-    // prologue: slots 0 .. AHEAD - 1 in flight; confirm slot 0; start interval 0's first fragments
+    // prologue: slots 0 .. AHEAD - 1 in flight; confirm slot 0 (a cadence of G: slots 0 .. G, what the first group reads);
+    // start interval 0's first fragments
+    // (with G > 1 interval 0's sync_slot then waits on the same count with nothing issued in between: redundant by design —
+    //  only slot 0 is read before it — so that every loop barrier, the first included, finds its G slots confirmed the same way)
     static_for<AHEAD>([&](auto s_c) __attribute__((always_inline)) { issue(decltype(s_c)::value); });
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * F_PPS) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((G == 1 ? AHEAD - 1 : AHEAD - G - 1) * F_PPS) : "memory");
     __builtin_amdgcn_s_barrier();
     if constexpr (T16) seed16(ring(0), 0, I0c{});   // the first block's tile-0 norms
     seed_fetch(ring(0), 0);                          // (shallow lock-step tiles: the first tile's norms)
@@ -1482,16 +1500,25 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
     // The slot loop, one copy per interval variant (the dispatch is wave-uniform and loop-invariant): with
     // the three variants as branches inside ONE loop, hipcc parks the accumulators in different register
     // tuples at the merge and at the loop header and reconciles them with ~48 v_mov at every back-edge.
-    // Every wave executes exactly ns barriers whichever copy it runs.
+    // Every wave executes the same barriers whichever copy it runs: one per interval (OpI8Pre: one per group of G).
     auto slot_loop = [&](auto lag_c, auto dph_c, auto rec_c) __attribute__((always_inline)) {
         auto sync_slot = [&]() __attribute__((always_inline)) {
             if constexpr ((kAblate & 1) == 0) {
+#ifdef NNS_DIAG
+                const unsigned long long diag_s0 = __builtin_amdgcn_s_memtime();
+#endif
                 // my share of slot s+1 has landed.  AHEAD 2: issued an interval ago, the only DMA in flight.  AHEAD 3:
                 // issued two intervals ago; the F_PPS pieces of slot s+2 issued since stay in flight (vmcnt counts
                 // in issue order; a candidate store of the slow path issued in between only makes the wait longer)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 2) * F_PPS) : "memory");
+                // (a cadence of G: my share of slots s+1 .. s+G, the rest of the group and the slot its last interval
+                //  prefetches from; slots s+G+1 .. s+AHEAD-1 stay in flight)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - G - 1) * F_PPS) : "memory");
                 // everyone's share of slot s+1 has landed; everyone is done with slot s-2
+                // (a cadence of G: everyone's share of slots s+1 .. s+G has landed; everyone is done with every slot before s)
                 __builtin_amdgcn_s_barrier();
+#ifdef NNS_DIAG
+                diag_sync += __builtin_amdgcn_s_memtime() - diag_s0;
+#endif
             }
         };
         if constexpr (SPBLK == 2) {
@@ -1514,7 +1541,10 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             }
         } else {
             for (int s = 0; s < ns; ++s) {
-                sync_slot();
+                // (the predicate is a function of s alone: every wave executes the same barriers, ceil(ns / G) of them,
+                //  wherever its refinements fall; the branch is scalar and the loop stays one interval per iteration)
+                if constexpr (G == 1) sync_slot();
+                else if (s % G == 0) sync_slot();
                 interval(lag_c, dph_c, I0{}, rec_c, s, ring(s), ring(s - 1), ring(s + 1));
                 if constexpr (!OP::kLag) {
                     // lock-step partners (staggering only their DMA issue steps, or packing / spreading the
@@ -1613,6 +1643,8 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
         atomicAdd(tot, (unsigned long long)diag_slow);
         atomicAdd(tot + 1, (unsigned long long)diag_tiles);
         atomicAdd(tot + 2, diag_cyc);
+        atomicAdd(tot + 3, diag_sync);
+        atomicAdd(tot + 4, 1ull);   // (waves)
     }
     if (a.stamps && threadIdx.x == 0) {
         unsigned long long *o = a.stamps + 4 * (size_t)(blockIdx.y * gridDim.x + blockIdx.x);
@@ -2225,8 +2257,13 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
                             "workgroup main loop %.1f us median (%.1f .. %.1f), first start to last end %.1f us\n",
                     ghz[ghz.size() / 2], ghz.front(), ghz.back(), ghz.size(), us[us.size() / 2], us.front(), us.back(),
                     (double)(last - first) * 0.01);
-        fprintf(stderr, "[nns] filter slow path: %llu of %llu (tile, state) retirements (fp32 tiles only), %.0f memtime ticks each, share=%d\n",
-                h[nwg * 4], h[nwg * 4 + 1], h[nwg * 4] ? (double)h[nwg * 4 + 2] / (double)h[nwg * 4] : 0.0, a.share_thr);
+        // (the total words behind the stamps: slow-path executions, retirements, ticks inside the slow path, ticks inside
+        //  sync_slot, waves)
+        const double nwaves = h[nwg * 4 + 4] ? (double)h[nwg * 4 + 4] : 1.0;
+        fprintf(stderr, "[nns] filter slow path: %llu of %llu (tile, state) retirements (fp32 tiles only), %.0f memtime ticks each, share=%d, "
+                        "%.0f memtime ticks per wave in the slot wait + barrier\n",
+                h[nwg * 4], h[nwg * 4 + 1], h[nwg * 4] ? (double)h[nwg * 4 + 2] / (double)h[nwg * 4] : 0.0, a.share_thr,
+                (double)h[nwg * 4 + 3] / nwaves);
         (void)hipFree(a.stamps);
     }
 #endif

@@ -514,6 +514,28 @@ __host__ __device__ constexpr int lazy16_gather(int lane, int t, int ks, int par
     return ((2 * ks + (g >> 1)) * parts + part) * 64 + 32 * (g & 1) + 16 * t + i;
 }
 
+// The int8 pre-pass's ring (OpI8Pre, filter_mfma.hip): kI8PreRingDepth slots, a slot's DMA issued kI8PreAhead intervals
+// before the interval that reads it, and a workgroup barrier only at the intervals s with s % kI8PreGroup == 0.
+// Between two barriers a wave is anywhere inside its group g: it reads slots gG .. gG + G (an interval reads its own slot
+// and, for its last fragments' prefetch and the next tile's seeds, the next one) and its DMA writes slots gG + AHEAD ..
+// gG + G - 1 + AHEAD.  The barrier that opens group g confirms slots gG + 1 .. gG + G with the counted wait
+// vmcnt((AHEAD - G - 1) pieces per wave): the youngest of them must have been issued (G < AHEAD), and the leader's
+// youngest write must not reach the laggard's oldest read one ring turn on (AHEAD + G - 1 < depth).
+// (tools/pre_cadence_check.cpp brute-forces the protocol against this closed form.)
+#ifndef NNS_F_PRE_AHEAD
+#define NNS_F_PRE_AHEAD 8
+#endif
+#ifndef NNS_F_PRE_GROUP
+#define NNS_F_PRE_GROUP 4
+#endif
+constexpr int kI8PreRingDepth = 16;
+constexpr int kI8PreAhead = NNS_F_PRE_AHEAD;
+constexpr int kI8PreGroup = NNS_F_PRE_GROUP;
+__host__ __device__ constexpr bool pre_cadence_ok(int depth, int ahead, int group)
+{
+    return group >= 1 && group < ahead && ahead + group <= depth;
+}
+
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
     int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; tau mode 4)
