@@ -326,6 +326,34 @@ int nns_search_i8_ex(int k, int m, int n, const int8_t *s_points,
                      const int8_t *r_points, int *idx_out, float *dist_out,
                      int num_shards, unsigned flags, int device);
 
+/* uint8 points (SIFT / BIGANN descriptors, raw pixels, 8-bit quantisers: values 0 .. 255).  dtype code 5 (the bf16_points
+ * argument of nns_plan_filter / nns_plan_topk / nns_plan_range).  Arrays are const uint8_t *, same [points][k] layout.
+ * Semantics: the int8 contract with one word changed — V0's arithmetic on the values widened exactly to fp32; indices
+ * bit-exact, distances bit-equal, lowest index wins ties, index 0 when nothing is selectable; nns_stats.nonfinite is
+ * always 0 and there is NO void or guard condition.  For k <= 256 the distance is the exact integer squared distance, at
+ * most 256 * 255^2 = 16 646 400 < 2^24; beyond k = 258 V0's chain rounds and the exact kernels run V0's own arithmetic
+ * (k <= 16384).  An index and its queries must have the same dtype: any mix with the other dtypes' entry points returns
+ * NNS_ERR_INVALID, in both directions.  The dtype-agnostic entry points serve a uint8 index like any other.
+ * Bias identity: (q - 128) - (r - 128) = q - r for every coordinate, so every term of V0's chain on the widened uint8
+ * values is the fp32 integer it is on the int8 values q - 128, r - 128.  K2 flips the top bit of each byte (u ^ 0x80 read
+ * as int8 is u - 128) and so builds exactly the int8 operand image: for 32 <= k <= 256 and at least 64 queries the
+ * filter is the int8 one, unchanged (v_mfma_i32_16x16x64_i8 at KT = 256, exact integer scores, |x'.y'| <= 2^22,
+ * |score| < 2^24, the margin nns_tau_consts mode 1's); nns_index_filter_form reports 5.  The padded dimensions hold 0
+ * after the bias in queries and refs alike; the norms are the sums of (u - 128)^2 over the real dimensions.
+ * Flags: NNS_PATH_AUTO / NNS_PATH_EXACT / NNS_PATH_MFMA, NNS_PROFILE, NNS_RECORDS_PER_REF, NNS_RANGE_MFMA and
+ * NNS_TOPK_MFMA (32 <= k <= 256: K7m / K6m on the int8 MFMA, below; other k: NNS_ERR_UNSUPPORTED).  NNS_FILTER_BF16,
+ * NNS_FILTER_F32, NNS_FILTER_SPLIT_EAGER and the int8 pre-pass flags: NNS_ERR_INVALID.  NNS_REFS_SOA, and NNS_PATH_MFMA
+ * with k > 256: NNS_ERR_UNSUPPORTED.  All of these are answered before the device is looked up.  There is no
+ * nns_search_u8_multi.  Times (tools/probe_u8.py, profiles/u8_probe.json): see README. */
+int nns_index_create_u8(nns_index **out, int device, int k, int n,
+                        const uint8_t *r_dev, int64_t index_base,
+                        unsigned flags, void *stream);
+int nns_index_search_u8(nns_index *ix, int m, const uint8_t *q_dev,
+                        nns_key *keys_dev, void *stream);
+int nns_search_u8_ex(int k, int m, int n, const uint8_t *s_points,
+                     const uint8_t *r_points, int *idx_out, float *dist_out,
+                     int num_shards, unsigned flags, int device);
+
 /* Binary points ("b1": ORB / BRIEF descriptors, 1-bit quantised embeddings) under Hamming distance.  dtype code 4 (the
  * bf16_points argument of nns_plan_topk / nns_plan_range).
  * Storage: a point of k bits is k / 32 consecutive uint32_t words, 4-byte aligned; bit t of a point is
@@ -423,14 +451,17 @@ int nns_search_f16_topk(int k, int m, int n, const uint16_t *s_points, const uin
 /* int8 points: the same call; NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_i8_topk(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, int kn,
                        int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
+/* uint8 points: the same call; NNS_TOPK_MFMA at 32 <= k <= 256 runs K6m on the int8 MFMA (other k: NNS_ERR_UNSUPPORTED). */
+int nns_search_u8_topk(int k, int m, int n, const uint8_t *s_points, const uint8_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
 /* binary points (k in bits, packed words): the same call; every flag but the auto / exact path and NNS_PROFILE:
  * see nns_index_create_b1. */
 int nns_search_b1_topk(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, int kn,
                        int *idx_out, float *dist_out, int num_shards, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the top-K launch geometry for a k-D search of m queries over n refs.
  * out[0..5] = {queries per workgroup, ref splits (grid.y), refs per split, workgroups, LDS bytes per workgroup,
- * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points (the narrow types share
- * one geometry: their refs are widened as they are read), 4 binary points: k is in bits, and the LDS and workspace fields
+ * split-workspace keys (0 with one split)}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8, 5 uint8 points (the narrow types
+ * share one geometry: their refs are widened as they are read), 4 binary points: k is in bits, and the LDS and workspace fields
  * follow k / 32 words of 4 bytes (k % 32 != 0 or k / 32 > 16384: NNS_ERR_UNSUPPORTED). */
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len);
 
@@ -469,6 +500,8 @@ int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, in
  * NNS_ERR_UNSUPPORTED for k outside 32 .. 256 or kn above NNS_TOPK_MAX; NNS_ERR_INVALID for the flags of fp32 points
  * (NNS_FILTER_F32, NNS_FILTER_BF16, NNS_FILTER_SPLIT_EAGER). */
 int nns_plan_topk_mfma_bf16(int k, int m, int n, int kn, unsigned flags, int *out, int out_len);
+/* K6m's plan for uint8 points: the same seventeen fields; kt is 256 and the layout field reads 3 (the int8 image). */
+int nns_plan_topk_mfma_u8(int k, int m, int n, int kn, unsigned flags, int *out, int out_len);
 
 /* ---- fixed-radius neighbours (range search) -----------------------------------
  * Semantics: a hit of query i is every reference j (global index, index_base added) whose V0 distance d (the value
@@ -514,13 +547,16 @@ int nns_search_f16_range(int k, int m, int n, const uint16_t *s_points, const ui
 /* int8 points: the same call; NNS_RANGE_MFMA: NNS_ERR_UNSUPPORTED. */
 int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_t *r_points, float radius2,
                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
+/* uint8 points: the same call; NNS_RANGE_MFMA at 32 <= k <= 256 runs K7m on the int8 MFMA (other k: NNS_ERR_UNSUPPORTED). */
+int nns_search_u8_range(int k, int m, int n, const uint8_t *s_points, const uint8_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 /* binary points (k in bits, packed words; radius2 is compared with the Hamming distance as fp32): the same call. */
 int nns_search_b1_range(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, float radius2,
                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device);
 /* Diagnostic (host only, no device needed): the range search's launch geometry for a k-D search of m queries over n
  * refs.  out[0..5] = {queries per workgroup, ref chunks (grid.y), refs per chunk, workgroups, LDS bytes per
- * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8 points, 4 binary points (k in bits; the
- * fields follow k / 32 words, as in nns_plan_topk). */
+ * workgroup, workspace bytes}.  bf16_points: 0 fp32, 1 bf16, 2 fp16, 3 int8, 5 uint8 points, 4 binary points (k in
+ * bits; the fields follow k / 32 words, as in nns_plan_topk). */
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
 
 /* ---- range search on the matrix cores (NNS_RANGE_MFMA, K7m) ------------------------
@@ -541,7 +577,12 @@ int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len);
  * bf16 points (32 <= k <= 256, the depths of the 16x16x32 tiles; nns_search_bf16_range takes the flag too): the flag
  * pass runs v_mfma_f32_16x16x32_bf16 on K2's order-1 image, the one the 1-NN bf16 filter reads.  The operands are the
  * points themselves, so a score is ONE product per k-step — no hi / lo parts, no centring — and the threshold is
- * nns_range_threshold_bf16's.  Ring, bitmap, batches, evaluation, fallbacks, info and stats are the same. */
+ * nns_range_threshold_bf16's.  Ring, bitmap, batches, evaluation, fallbacks, info and stats are the same.
+ * uint8 points (32 <= k <= 256; nns_search_u8_range / nns_search_u8_topk take the flags too): the flag pass
+ * (range_flag_u8_kernel) runs v_mfma_i32_16x16x64_i8 at depth 256 on K2's int8 image of the values biased by 128, the one
+ * the 1-NN filter of a uint8 index reads.  Score and distance are exact integers, so the threshold is exact
+ * (nns_range_threshold_u8) and a block is flagged if and only if it holds a hit.  No value voids the filter: the
+ * fall-backs are m < 64, radius2 = +INF and, for K6m, a sample stride below 2.  The rest is the same. */
 
 /* Diagnostic: what the last nns_index_range_count on this index did.  out[0..3] = {path taken (NNS_PATH_EXACT: K7,
  * NNS_PATH_MFMA: K7m), flagged (query, 32-ref block) pairs, pairs examined (m x blocks per query), total hits
@@ -569,6 +610,15 @@ int nns_plan_range_mfma_bf16(int k, int m, int n, unsigned flags, int *out, int 
  * query's own squared norm |x|^2 (no centring) and ymax2 the refs' largest |y|^2.  Every ref with a V0 distance
  * <= radius2 has a 16x16x32 score |y|^2 - 2 x.y <= *thr_out.  Monotone in radius2. */
 int nns_range_threshold_bf16(int kt, float qnorm2, float ymax2, float radius2, float *thr_out);
+/* K7m's geometry for uint8 points: the same ten fields, planned through nns_plan_filter's int8 geometry: kt is 256 for
+ * every k, the block bytes (and every other field) are the bf16 plan's at depth 128, and the layout field reads 3: the
+ * int8 image.  Rejections as nns_plan_range_mfma_bf16's. */
+int nns_plan_range_mfma_u8(int k, int m, int n, unsigned flags, int *out, int out_len);
+/* The threshold of a uint8 query (host only): thr = fl(floorf(fminf(radius2, 2^24)) - qnorm2), with qnorm2 the biased
+ * squared norm |x - 128|^2 (an integer <= 2^22) that K2 keeps.  The score s = |y'|^2 - 2 x'.y' and the distance
+ * d = qnorm2 + s are exact integers below 2^24 in magnitude and the subtraction is exact, so s <= thr <=> d <= radius2:
+ * no margin.  radius2 >= 0, not NaN. */
+int nns_range_threshold_u8(float qnorm2, float radius2, float *thr_out);
 
 /* Deterministic synthetic clouds: dev[i] = u24(splitmix64(seed, offset+i)) * 2^-24
  * in [0,1) — bit-identical to oracle/v0_oracle.c:nns_rng_fill on the CPU. */
@@ -619,7 +669,8 @@ int nns_filter_lazy_tile(void);
  * k > 256, NNS_RANGE_MFMA or NNS_TOPK_MFMA: NNS_ERR_UNSUPPORTED; the operand flags: NNS_ERR_INVALID.
  * 3 int8 points: kt = 256 for every k <= 256, every other field the bf16 plan's at a 128-deep tile (k <= 128) — the
  * int8 block has that tile's bytes and fragments; rejections as for fp16 points, NNS_REFS_SOA with them.
- * 4 binary points: NNS_ERR_UNSUPPORTED (no filter is built for them). */
+ * 4 binary points: NNS_ERR_UNSUPPORTED (no filter is built for them).
+ * 5 uint8 points: int8's plan field for field; NNS_RANGE_MFMA / NNS_TOPK_MFMA are accepted at 32 <= k <= 256. */
 int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *out, int out_len);
 /* Diagnostic (host only, no device needed): the launch geometry of the EXACT path (the reference's V1-V7 kernels,
  * core.cu:58-696) for a k-D search of m queries over n refs.  out[0..5] = {kernel: 0 K1a (lane = query, exact), 1 K1f

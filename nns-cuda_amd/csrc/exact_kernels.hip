@@ -1197,6 +1197,15 @@ __device__ __forceinline__ void widen16(const float4 &raw, const i8_t *, float (
         for (int b = 0; b < 4; ++b) o[4 * e + b] = i8_widen(w[e], b);
     }
 }
+__device__ __forceinline__ void widen16(const float4 &raw, const u8_t *, float (&o)[16])   // 16 uint8 -> 16 fp32
+{
+    const unsigned w[4] = {__float_as_uint(raw.x), __float_as_uint(raw.y), __float_as_uint(raw.z), __float_as_uint(raw.w)};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) o[4 * e + b] = u8_widen(w[e], b);
+    }
+}
 
 template <int QT, typename T>
 __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
@@ -1204,7 +1213,7 @@ __global__ __launch_bounds__(256) void exact_lane_ref_tiled_kernel(
     const int *__restrict__ qlist, const int *__restrict__ qcount, int mq,
     int64_t index_base, nns_key *__restrict__ keys)
 {
-    constexpr int EPC = 16 / sizeof(T);          // elements per 16-byte chunk (4 fp32 / 8 bf16, fp16 / 16 int8)
+    constexpr int EPC = 16 / sizeof(T);          // elements per 16-byte chunk (4 fp32 / 8 bf16, fp16 / 16 int8, uint8)
     constexpr int ROWB = 8 * 16 + 16;            // padded LDS row: 8 chunks + 16 B
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     float *sq = smem_f;                                            // [QT][k] fp32 queries
@@ -1764,6 +1773,8 @@ int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, 
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
     if (bf16 == DT_B1)
         NNS_TRY(launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, nullptr, nullptr, m, index_base, keys, st));
+    else if (bf16 == DT_U8)
+        NNS_TRY(launch_k1b(p, k, n, (const u8_t *)q, (const u8_t *)r, nullptr, nullptr, m, index_base, keys, st));
     else if (bf16 == DT_I8)
         NNS_TRY(launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, nullptr, nullptr, m, index_base, keys, st));
     else if (bf16 == DT_F16)
@@ -1788,6 +1799,7 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
     ExactPlan p{};
     k1b_plan(k, n, max_listed, 8, &p);
     if (bf16 == DT_B1) return launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, qlist, qcount, 0, index_base, keys, st);
+    if (bf16 == DT_U8) return launch_k1b(p, k, n, (const u8_t *)q, (const u8_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16 == DT_I8) return launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16 == DT_F16) return launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, qlist, qcount, 0, index_base, keys, st);
     if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);

@@ -2064,7 +2064,7 @@ static int with_filter_op(const FilterGeom &g, F &&f)
 }
 
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager,
-                bool f16, bool i8)
+                bool f16, bool i8, bool u8)
 {
     if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
     int kt = 0;
@@ -2103,6 +2103,7 @@ int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool 
     g->bf16 = bf16 ? 1 : 0;
     g->f16 = f16 ? 1 : 0;
     g->i8 = i8 ? 1 : 0;
+    g->u8 = (i8 && u8) ? 1 : 0;   // (uint8 points: int8's plan; K2 biases the image, K5 reads u8_t)
     g->mixed = mixed ? 1 : 0;
     // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
     g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;

@@ -92,6 +92,8 @@ __device__ __forceinline__ float load_f(const f16_t *p, size_t i) { return pt_ld
 __device__ __forceinline__ float4 load_f4(const f16_t *p) { return pt_ld4(p); }
 __device__ __forceinline__ float load_f(const i8_t *p, size_t i) { return pt_ld1(p + i); }    // int8 -> fp32: exact
 __device__ __forceinline__ float4 load_f4(const i8_t *p) { return pt_ld4(p); }
+__device__ __forceinline__ float load_f(const u8_t *p, size_t i) { return pt_ld1(p + i); }    // uint8 -> fp32: exact
+__device__ __forceinline__ float4 load_f4(const u8_t *p) { return pt_ld4(p); }
 
 // V0's exact distance (core.cu:38-43), t ascending; 4 dims per load when aligned
 template <typename T>
@@ -643,7 +645,11 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
     const int mode = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
     const bool data_bf16 = g.bf16 && !g.mixed && !g.f16 && !g.i8;    // element type of q / r
     if (g.splits >= 4) {   // few queries, many lists per query: one wave per query
-        if (g.i8)
+        if (g.u8)   // (uint8 points: the int8 image's lists, the re-rank on the uint8 values)
+            hipLaunchKernelGGL(finalize_wave_kernel<u8_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
+                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const u8_t *)q, (const u8_t *)r, lists,
+                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
+        else if (g.i8)
             hipLaunchKernelGGL(finalize_wave_kernel<i8_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
                                g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists,
                                counts, qnorm, scal, index_base, keys, amb_list, multi_list);
@@ -676,7 +682,11 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
         NNS_HIP(hipMemsetAsync(diag, 0, (size_t)units * 8 * sizeof(unsigned long long), st));
     }
 #endif
-    if (g.i8)
+    if (g.u8)
+        hipLaunchKernelGGL(K5_UNIT_KERNEL<u8_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
+                           g.splits, k, m, n, (const u8_t *)q, (const u8_t *)r, lists, counts, qnorm,
+                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
+    else if (g.i8)
         hipLaunchKernelGGL(K5_UNIT_KERNEL<i8_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
                            g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists, counts, qnorm,
                            scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);

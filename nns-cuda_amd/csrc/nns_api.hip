@@ -80,10 +80,10 @@ struct nns_index {
     int64_t base = 0;
     unsigned flags = 0;
     int path = NNS_PATH_EXACT;
-    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k], or int8 [n][k], or packed bits [n][k] (k words)
+    const void *r_dev = nullptr;   // fp32 [n][k], or bf16 / fp16 bits [n][k], or int8 / uint8 [n][k], or packed bits [n][k] (k words)
     const void *r_soa = nullptr;   // NNS_REFS_SOA: the caller's [k][n] array; r_dev is then r_own
     void *r_own = nullptr;         // owned point-major copy of r_soa
-    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8, DT_B1 (k then counts 32-bit words)
+    int bf16 = 0;                  // the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8, DT_B1 (k then counts 32-bit words), DT_U8
     bool profile = false;
     bool refs_bad = false;
     bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
@@ -243,7 +243,7 @@ static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *spl
 
 // what NNS_RANGE_MFMA / NNS_TOPK_MFMA take: fp32 points whose filter form is the split one, at the split tiles' depths;
 // bf16 points at the depths of the 16x16x32 tiles (below 32 dimensions AUTO does not filter bf16 points either); fp16
-// and int8 points: no flag pass is built
+// and int8 points: no flag pass is built; uint8 points at the depth of the int8 tile, 32 <= k <= 256 (range_flag_u8_kernel)
 static bool flag_pass_supported(int k, int bf16, unsigned flags)
 {
     if (bf16 == DT_F16 || bf16 == DT_I8 || (flags & (NNS_FILTER_F32 | NNS_FILTER_BF16))) return false;
@@ -254,9 +254,9 @@ static int prep_refs(nns_index *ix, hipStream_t st)
 {
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(ix->scal, 0, sizeof(DevScalars), st));
-    if (ix->bf16 == DT_I8) {   // (the values themselves: the filter applies the -2; no max-|v| word: nothing voids the filter)
+    if (dt_i8_image(ix->bf16)) {   // (the values themselves: the filter applies the -2; no max-|v| word: nothing voids the filter)
         NNS_TRY(launch_prep_image_i8(g.kt, ix->k, ix->n, g.n_pad, (const int8_t *)ix->r_dev, INFINITY, ix->rimg, ix->rnorm,
-                                     &ix->scal->ymax2_bits, st));
+                                     &ix->scal->ymax2_bits, st, ix->bf16 == DT_U8));
         return NNS_OK;
     }
     if (ix->bf16) {
@@ -345,6 +345,31 @@ static int index_destroy_impl(nns_index *ix, bool stream_idle)
     return NNS_OK;
 }
 
+// What uint8 points do not take, answered by create and by the whole calls before the device is looked up: the operand
+// flags and the int8 pre-pass flags (they choose among the filters of fp32 points), dimension-major refs, the MFMA path
+// beyond the int8 tile, the flag passes outside the int8 tile's depths
+static int check_u8_flags(const char *where, int bf16, int k, unsigned flags)
+{
+    if (bf16 != DT_U8) return NNS_OK;
+    if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE)) {
+        set_error("%s: the operand flags apply to fp32 points, not to uint8 points (flags 0x%x)", where, flags);
+        return NNS_ERR_INVALID;
+    }
+    if (flags & NNS_REFS_SOA) {
+        set_error("%s: dimension-major refs are not built for uint8 points (flags 0x%x)", where, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if ((flags & NNS_PATH_MASK) == NNS_PATH_MFMA && k > 256) {
+        set_error("%s: the MFMA path of uint8 points tiles k <= 256 (k=%d; use the auto or exact path)", where, k);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if ((flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA)) && !flag_pass_supported(k, bf16, flags)) {
+        set_error("%s: the range-MFMA and top-K MFMA flags take uint8 points at 32 <= k <= 256 (k=%d, flags 0x%x)", where, k, flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    return NNS_OK;
+}
+
 // Binary points: the entry points take k in bits; below them the dimension is kw = k / 32 words of 4 bytes (DT_B1).
 // What binary points do not take, answered before the device is looked up: a bit count that is not whole words or is
 // beyond the exact path's tile (in words), a point set that is not word-aligned, every flag but the auto / exact path
@@ -394,6 +419,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         return NNS_ERR_INVALID;
     }
     *out = nullptr;
+    NNS_TRY(check_u8_flags("nns_index_create_u8", bf16, k, flags));
     if (bf16 == DT_I8) {   // (what an int8 index does not take, answered before the device is looked up)
         if (flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER)) {
             set_error("nns_index_create_i8: the operand flags apply to fp32 points (flags 0x%x)", flags);
@@ -451,8 +477,8 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             return frc;
         }
     }
-    // deepest tile of the MFMA filter (fp16 points: the two 16x16x32 depths; int8 points: the 256-deep 16x16x64 tile)
-    const int kmax = (bf16 == DT_F16 || bf16 == DT_I8) ? 256 : (bf16 || ix->mixed) ? kMaxFilterK : 256;
+    // deepest tile of the MFMA filter (fp16 points: the two 16x16x32 depths; int8 and uint8 points: the 256-deep 16x16x64 tile)
+    const int kmax = (bf16 == DT_F16 || dt_i8_image(bf16)) ? 256 : (bf16 || ix->mixed) ? kMaxFilterK : 256;
     int path = flags & NNS_PATH_MASK;
     // crossover: from k = 8 the MFMA filter (KT = 16 / 32 tile) beats 3k VALU ops per pair; bf16 tiles
     // are at least 128 deep, so they only pay from k = 32
@@ -497,7 +523,7 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
         }
         if (path == NNS_PATH_MFMA || ix->flag_image()) {   // (the range and top-K flags build the image whatever the 1-NN path)
             if ((rc = filter_plan(k, 1, n, bf16 != 0, &ix->geom, ix->mixed, (flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16 == DT_F16, bf16 == DT_I8)) !=
+                                  (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16 == DT_F16, dt_i8_image(bf16), bf16 == DT_U8)) !=
                 NNS_OK)
                 break;
             const FilterGeom &g = ix->geom;
@@ -562,6 +588,13 @@ int nns_index_create_i8(nns_index **out, int device, int k, int n, const int8_t 
     return index_create_impl(out, device, k, n, r_dev, DT_I8, index_base, flags & ~kCreateNoSync, stream);
 }
 
+int nns_index_create_u8(nns_index **out, int device, int k, int n, const uint8_t *r_dev,
+                        int64_t index_base, unsigned flags, void *stream)
+{
+    DeviceScope keep_device;
+    return index_create_impl(out, device, k, n, r_dev, DT_U8, index_base, flags & ~kCreateNoSync, stream);
+}
+
 int nns_index_create_b1(nns_index **out, int device, int k, int n, const uint32_t *r_dev,
                         int64_t index_base, unsigned flags, void *stream)
 {
@@ -603,7 +636,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
     FilterGeom g = ix->geom;
     FilterGeom gq{};
     NNS_TRY(filter_plan(ix->k, m, ix->n, ix->bf16 != 0, &gq, ix->mixed, (ix->flags & NNS_RECORDS_PER_REF) != 0, ix->split,
-                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, ix->bf16 == DT_F16, ix->bf16 == DT_I8));
+                        (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, ix->bf16 == DT_F16, dt_i8_image(ix->bf16), ix->bf16 == DT_U8));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
     (void)g;
     if (gq.m_pad > ix->m_cap) {
@@ -702,7 +735,7 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
 {
     if (ix && ix->bf16 != bf16) {
         set_error("nns_index_search: query dtype does not match the index (%s index)",
-                  ix->bf16 == DT_B1 ? "binary" : ix->bf16 == DT_I8 ? "int8" : ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
+                  ix->bf16 == DT_U8 ? "uint8" : ix->bf16 == DT_B1 ? "binary" : ix->bf16 == DT_I8 ? "int8" : ix->bf16 == DT_F16 ? "fp16" : ix->bf16 ? "bf16" : "fp32");
         return NNS_ERR_INVALID;
     }
     if (!ix || !q_dev || !keys_dev || m <= 0) {
@@ -764,8 +797,9 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int bf16, 
         fpre.m = m;
         fpre.force = (ix->flags & NNS_FILTER_I8PRE_FORCE) ? 1 : 0;
     }
-    if (bf16 == DT_I8)
-        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st));
+    if (dt_i8_image(bf16))
+        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st,
+                                     bf16 == DT_U8));
     else if (bf16)
         NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg, ix->qnorm,
                                        nullptr, &ix->scal->q_maxabs_bits, st, bf16 == DT_F16));
@@ -827,6 +861,12 @@ int nns_index_search_i8(nns_index *ix, int m, const int8_t *q_dev, nns_key *keys
 {
     DeviceScope keep_device;
     return index_search_impl(ix, m, q_dev, DT_I8, keys_dev, stream);
+}
+
+int nns_index_search_u8(nns_index *ix, int m, const uint8_t *q_dev, nns_key *keys_dev, void *stream)
+{
+    DeviceScope keep_device;
+    return index_search_impl(ix, m, q_dev, DT_U8, keys_dev, stream);
 }
 
 int nns_index_search_b1(nns_index *ix, int m, const uint32_t *q_dev, nns_key *keys_dev, void *stream)
@@ -930,7 +970,7 @@ static int index_search_topk_impl(nns_index *ix, int m, const void *q_dev, int k
     if (ix->topk_mfma) {
         // K6m when its answer can be trusted and it has something to skip: the plan's conditions, finite refs below 1e17
         TopkMfmaPlan tp{};
-        NNS_TRY(topk_mfma_plan(ix->k, m, ix->n, kn, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &tp, ix->bf16 != 0));
+        NNS_TRY(topk_mfma_plan(ix->k, m, ix->n, kn, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &tp, ix->bf16));
         if (tp.filtered) NNS_TRY(latch_refs_bad(ix, st));
         if (tp.filtered && !ix->refs_bad) return topk_mfma_pass(ix, tp, m, q_dev, kn, keys_dev, st);
         ix->topk_path = NNS_PATH_EXACT;
@@ -973,8 +1013,8 @@ int nns_keys_topk_unpack(const nns_key *keys_dev, int m, int kn, int *idx_dev, f
 
 int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int out_len)
 {
-    // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read; binary points (4): k bits are
-    //  k / 32 words of 4 bytes)
+    // (same geometry: bf16, fp16 (2), int8 (3) and uint8 (5) refs are widened as they are read; binary points (4): k bits
+    //  are k / 32 words of 4 bytes)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (bf16_points == DT_B1) NNS_TRY(b1_enter("nns_plan_topk", k, 0, nullptr, nullptr, &k));
     NNS_TRY(topk_check_kn("nns_plan_topk", kn));
@@ -988,13 +1028,13 @@ int nns_plan_topk(int k, int m, int n, int kn, int bf16_points, int *out, int ou
     return NNS_OK;
 }
 
-static int plan_topk_mfma_impl(const char *where, int k, int m, int n, int kn, unsigned flags, bool bf16, int *out,
+static int plan_topk_mfma_impl(const char *where, int k, int m, int n, int kn, unsigned flags, int bf16, int *out,
                                int out_len)
 {
     if (!out || out_len < 17 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     NNS_TRY(topk_check_kn(where, kn));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
-    NNS_TRY(plan_flag_check_flags(where, flags, bf16));
+    NNS_TRY(plan_flag_check_flags(where, flags, bf16 != 0));
     TopkMfmaPlan t{};
     NNS_TRY(topk_mfma_plan(k, m, n, kn, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &t, bf16));
     const RangeMfmaPlan &p = t.rp;   // (all zero unless filtered)
@@ -1006,12 +1046,17 @@ static int plan_topk_mfma_impl(const char *where, int k, int m, int n, int kn, u
 
 int nns_plan_topk_mfma(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
 {
-    return plan_topk_mfma_impl("nns_plan_topk_mfma", k, m, n, kn, flags, false, out, out_len);
+    return plan_topk_mfma_impl("nns_plan_topk_mfma", k, m, n, kn, flags, DT_F32, out, out_len);
 }
 
 int nns_plan_topk_mfma_bf16(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
 {
-    return plan_topk_mfma_impl("nns_plan_topk_mfma_bf16", k, m, n, kn, flags, true, out, out_len);
+    return plan_topk_mfma_impl("nns_plan_topk_mfma_bf16", k, m, n, kn, flags, DT_BF16, out, out_len);
+}
+
+int nns_plan_topk_mfma_u8(int k, int m, int n, int kn, unsigned flags, int *out, int out_len)
+{
+    return plan_topk_mfma_impl("nns_plan_topk_mfma_u8", k, m, n, kn, flags, DT_U8, out, out_len);
 }
 
 int nns_index_topk_info(nns_index *ix, int64_t *out, int out_len)
@@ -1080,6 +1125,8 @@ static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipS
     NNS_TRY(ensure_query_ws(ix, m, st, false));
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
+    if (ix->bf16 == DT_U8)   // (the biased int8 image and its norms, as the 1-NN search of a uint8 index prepares them)
+        return launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st, true);
     if (ix->bf16)   // (the order-1 image and the uncentred norms, as the 1-NN search of a bf16 index prepares them)
         return launch_prep_image_bf16(kBf16ImageOrder, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg,
                                       ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st);
@@ -1104,7 +1151,7 @@ static int range_mfma_choose(nns_index *ix, int m, float radius2, hipStream_t st
     if (!ix->range_mfma || m < kTinyM || !(radius2 < INFINITY)) return NNS_OK;
     NNS_TRY(latch_refs_bad(ix, st));
     if (ix->refs_bad) return NNS_OK;
-    *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp, ix->bf16 != 0) == NNS_OK;
+    *use = range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, mp, ix->bf16) == NNS_OK;
     return NNS_OK;
 }
 
@@ -1196,7 +1243,7 @@ static int index_range_fill_impl(nns_index *ix, int m, const void *q_dev, float 
     // (the count's path; either plan depends on k, m, n and the index alone, and the count has made it once already)
     if (ix->range_path == NNS_PATH_MFMA) {
         RangeMfmaPlan mp{};
-        NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp, ix->bf16 != 0));
+        NNS_TRY(range_mfma_plan(ix->k, m, ix->n, (ix->flags & NNS_FILTER_SPLIT_EAGER) != 0, &mp, ix->bf16));
         if (!idx_dev && !dist_dev) return NNS_OK;
         return range_mfma_pass(ix, mp, true, m, q_dev, radius2, const_cast<int64_t *>(lims_dev), idx_dev, dist_dev, st);
     }
@@ -1224,8 +1271,8 @@ int nns_index_range_fill(nns_index *ix, int m, const void *q_dev, float radius2,
 
 int nns_plan_range(int k, int m, int n, int bf16_points, int *out, int out_len)
 {
-    // (same geometry: bf16, fp16 (2) and int8 (3) refs are widened as they are read; binary points (4): k bits are
-    //  k / 32 words of 4 bytes)
+    // (same geometry: bf16, fp16 (2), int8 (3) and uint8 (5) refs are widened as they are read; binary points (4): k bits
+    //  are k / 32 words of 4 bytes)
     if (!out || out_len < 6 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (bf16_points == DT_B1) NNS_TRY(b1_enter("nns_plan_range", k, 0, nullptr, nullptr, &k));
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
@@ -1274,14 +1321,15 @@ static int plan_flag_check_flags(const char *where, unsigned flags, bool bf16)
     return NNS_OK;
 }
 
-// the plans' `layout`: 0 eager split image, 1 lazy split image, 2 the order-1 16x16x32 image of bf16 points
-static int flag_plan_layout(const RangeMfmaPlan &p) { return p.bf16 ? 2 : p.lazy_img; }
+// the plans' `layout`: 0 eager split image, 1 lazy split image, 2 the order-1 16x16x32 image of bf16 points, 3 the int8
+// image (16x16x64 operands) of uint8 points
+static int flag_plan_layout(const RangeMfmaPlan &p) { return p.bf16 == DT_U8 ? 3 : p.bf16 ? 2 : p.lazy_img; }
 
-static int plan_range_mfma_impl(const char *where, int k, int m, int n, unsigned flags, bool bf16, int *out, int out_len)
+static int plan_range_mfma_impl(const char *where, int k, int m, int n, unsigned flags, int bf16, int *out, int out_len)
 {
     if (!out || out_len < 10 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (m > kMaxPoints || n > kMaxPoints) return NNS_ERR_INVALID;
-    NNS_TRY(plan_flag_check_flags(where, flags, bf16));
+    NNS_TRY(plan_flag_check_flags(where, flags, bf16 != 0));
     RangeMfmaPlan p{};
     NNS_TRY(range_mfma_plan(k, m, n, (flags & NNS_FILTER_SPLIT_EAGER) != 0, &p, bf16));
     const int v[10] = {p.kt, 32, p.blocks, p.batch, p.batches, (int)p.flag_bytes, p.gx, p.gy, p.lds, flag_plan_layout(p)};
@@ -1291,12 +1339,17 @@ static int plan_range_mfma_impl(const char *where, int k, int m, int n, unsigned
 
 int nns_plan_range_mfma(int k, int m, int n, unsigned flags, int *out, int out_len)
 {
-    return plan_range_mfma_impl("nns_plan_range_mfma", k, m, n, flags, false, out, out_len);
+    return plan_range_mfma_impl("nns_plan_range_mfma", k, m, n, flags, DT_F32, out, out_len);
 }
 
 int nns_plan_range_mfma_bf16(int k, int m, int n, unsigned flags, int *out, int out_len)
 {
-    return plan_range_mfma_impl("nns_plan_range_mfma_bf16", k, m, n, flags, true, out, out_len);
+    return plan_range_mfma_impl("nns_plan_range_mfma_bf16", k, m, n, flags, DT_BF16, out, out_len);
+}
+
+int nns_plan_range_mfma_u8(int k, int m, int n, unsigned flags, int *out, int out_len)
+{
+    return plan_range_mfma_impl("nns_plan_range_mfma_u8", k, m, n, flags, DT_U8, out, out_len);
 }
 
 int nns_range_threshold(int kt, float qnorm2, float ymax2, float radius2, float *thr_out)
@@ -1310,6 +1363,13 @@ int nns_range_threshold_bf16(int kt, float qnorm2, float ymax2, float radius2, f
 {
     if (kt <= 0 || !thr_out) return NNS_ERR_INVALID;
     *thr_out = range_threshold(kt, qnorm2, ymax2, radius2, 1);
+    return NNS_OK;
+}
+
+int nns_range_threshold_u8(float qnorm2, float radius2, float *thr_out)
+{
+    if (!thr_out) return NNS_ERR_INVALID;
+    *thr_out = range_threshold_u8(qnorm2, radius2);
     return NNS_OK;
 }
 
@@ -1705,9 +1765,18 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
         set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points (flags 0x%x)", flags);
         return NNS_ERR_UNSUPPORTED;
     }
+    if (bf16_points == DT_U8 && (flags & NNS_REFS_SOA)) {
+        set_error("nns_plan_filter: dimension-major refs are not built for uint8 points (flags 0x%x)", flags);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if (bf16_points == DT_U8 && (flags & (NNS_RANGE_MFMA | NNS_TOPK_MFMA)) && !flag_pass_supported(k, bf16_points, flags)) {
+        set_error("nns_plan_filter: the range-MFMA and top-K MFMA flags take uint8 points at 32 <= k <= 256 (k=%d)", k);
+        return NNS_ERR_UNSUPPORTED;
+    }
     FilterGeom g{};
     NNS_TRY(filter_plan(k, m, n, bf16_points != 0, &g, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split,
-                        (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16_points == DT_F16, bf16_points == DT_I8));
+                        (flags & NNS_FILTER_SPLIT_EAGER) != 0, bf16_points == DT_F16, dt_i8_image(bf16_points),
+                        bf16_points == DT_U8));
     const int v[16] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
                        g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split, g.lazy};
     memcpy(out, v, (out_len >= 16 ? 16 : out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
@@ -1821,12 +1890,12 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, 
     if (rbytes < kChunkMinBytes || n < 4096 || m < kTinyM) return false;
     if (bf16 == DT_B1) return false;   // (binary points: the rates below are not theirs; the plain path)
     const unsigned path = flags & NNS_PATH_MASK;
-    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > ((bf16 == DT_F16 || bf16 == DT_I8) ? 256 : kMaxFilterK);
+    const bool exact = path == NNS_PATH_EXACT || k < (bf16 ? 32 : 8) || k > ((bf16 == DT_F16 || dt_i8_image(bf16)) ? 256 : kMaxFilterK);
     double est_s;
     if (exact) {
         est_s = 3.0 * k * (double)m * (double)n / 45e12;
     } else {
-        int kt = bf16 == DT_I8 ? 256 : bf16 ? 128 : 16;
+        int kt = dt_i8_image(bf16) ? 256 : bf16 ? 128 : 16;
         while (kt < k) kt *= 2;
         const bool bf16_ops = bf16 || k > 256 || (flags & NNS_FILTER_BF16);
         // fp32 points: split-bf16 operands unless NNS_FILTER_F32 (3 bf16 MFMAs per 16 dims: ~5x the fp32 operands' rate)
@@ -2021,6 +2090,7 @@ static int search_host_impl(int k, int m, int n, const void *s_points, const voi
 {
     NNS_TRY(check_whole_call("nns_search_f32", k, m, n, s_points, r_points, idx_out));
     NNS_TRY(check_i8_flags("nns_search_i8_ex", bf16, flags));
+    NNS_TRY(check_u8_flags("nns_search_u8_ex", bf16, k, flags));
     DeviceScope keep_device;
     NNS_TRY(ensure_device_ok(device));
     if (num_shards < 1) num_shards = 1;
@@ -2053,9 +2123,10 @@ static int check_exact_only_flags(const char *where, const char *what, unsigned 
 static int search_topk_host_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int kn,
                                  int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
 {
-    const char *where = bf16 == DT_B1 ? "nns_search_b1_topk" : bf16 == DT_I8 ? "nns_search_i8_topk" : bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
+    const char *where = bf16 == DT_U8 ? "nns_search_u8_topk" : bf16 == DT_B1 ? "nns_search_b1_topk" : bf16 == DT_I8 ? "nns_search_i8_topk" : bf16 == DT_F16 ? "nns_search_f16_topk" : bf16 ? "nns_search_bf16_topk" : "nns_search_f32_topk";
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, idx_out));
     NNS_TRY(check_i8_flags(where, bf16, flags));
+    NNS_TRY(check_u8_flags(where, bf16, k, flags));
     NNS_TRY(topk_check_kn(where, kn));
     if ((int64_t)m * kn > 0x7FFFFFFFll * 4) {
         set_error("%s: m * kn too large for one call", where);
@@ -2133,7 +2204,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
                                   float radius2, int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags,
                                   int device)
 {
-    const char *where = bf16 == DT_B1 ? "nns_search_b1_range" : bf16 == DT_I8 ? "nns_search_i8_range" : bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
+    const char *where = bf16 == DT_U8 ? "nns_search_u8_range" : bf16 == DT_B1 ? "nns_search_b1_range" : bf16 == DT_I8 ? "nns_search_i8_range" : bf16 == DT_F16 ? "nns_search_f16_range" : bf16 ? "nns_search_bf16_range" : "nns_search_f32_range";
     if (idx_out) *idx_out = nullptr;
     if (dist_out) *dist_out = nullptr;
     if (!idx_out) {
@@ -2143,6 +2214,7 @@ static int search_range_host_impl(int k, int m, int n, const void *s_points, con
     // (lims_out stands for the output buffer of the shared check)
     NNS_TRY(check_whole_call(where, k, m, n, s_points, r_points, reinterpret_cast<const int *>(lims_out)));
     NNS_TRY(check_i8_flags(where, bf16, flags));
+    NNS_TRY(check_u8_flags(where, bf16, k, flags));
     NNS_TRY(range_check_radius(where, radius2));
     NNS_TRY(check_exact_only_flags(where, "range search", flags & ~(unsigned)NNS_RANGE_MFMA));
     if ((flags & NNS_RANGE_MFMA) && !flag_pass_supported(k, bf16, flags)) {
@@ -2189,6 +2261,24 @@ int nns_search_i8_range(int k, int m, int n, const int8_t *s_points, const int8_
                         int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
 {
     return search_range_host_impl(k, m, n, s_points, r_points, DT_I8, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_u8_range(int k, int m, int n, const uint8_t *s_points, const uint8_t *r_points, float radius2,
+                        int64_t *lims_out, int **idx_out, float **dist_out, unsigned flags, int device)
+{
+    return search_range_host_impl(k, m, n, s_points, r_points, DT_U8, radius2, lims_out, idx_out, dist_out, flags, device);
+}
+
+int nns_search_u8_ex(int k, int m, int n, const uint8_t *s_points, const uint8_t *r_points, int *idx_out,
+                     float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_host_impl(k, m, n, s_points, r_points, DT_U8, idx_out, dist_out, num_shards, flags, device);
+}
+
+int nns_search_u8_topk(int k, int m, int n, const uint8_t *s_points, const uint8_t *r_points, int kn,
+                       int *idx_out, float *dist_out, int num_shards, unsigned flags, int device)
+{
+    return search_topk_host_impl(k, m, n, s_points, r_points, DT_U8, kn, idx_out, dist_out, num_shards, flags, device);
 }
 
 int nns_search_b1_range(int k, int m, int n, const uint32_t *s_points, const uint32_t *r_points, float radius2,
@@ -2273,7 +2363,7 @@ int nns_warmup(int device)
     // filter: AUTO keeps a 64 x 512 x 16 problem on the exact kernel), the bf16-operand tiles for fp32 points (512 /
     // 384 / 512 / 640 / 768 / 1024: AUTO), the bf16 tiles 128 / 256 / 384 / 512 / 640 / 768 / 1024, the fp16 tiles 128 / 256
     // (dtype 2), the int8 tile (dtype 3: v_mfma_i32_16x16x64_i8, 256-deep), binary points (dtype 4: k = 8 words, K1b's
-    // Hamming scan)
+    // Hamming scan), uint8 points (dtype 5: K2's biased image under the int8 tile)
     static const int shapes[][5] = {{3, 64, 512, 0, NNS_PATH_AUTO},    {16, 64, 512, 0, NNS_PATH_AUTO},  {16, 1, 512, 0, NNS_PATH_AUTO},
                                     {16, 64, 512, 0, NNS_PATH_MFMA},   {24, 64, 512, 0, NNS_PATH_MFMA},  {40, 64, 512, 0, NNS_PATH_MFMA},
                                     {100, 64, 512, 0, NNS_PATH_MFMA},  {200, 64, 512, 0, NNS_PATH_MFMA}, {300, 64, 512, 0, NNS_PATH_AUTO},
@@ -2282,7 +2372,8 @@ int nns_warmup(int device)
                                     {64, 64, 512, 1, NNS_PATH_MFMA},   {200, 64, 512, 1, NNS_PATH_MFMA}, {300, 64, 512, 1, NNS_PATH_MFMA},
                                     {600, 64, 512, 1, NNS_PATH_MFMA},  {700, 64, 512, 1, NNS_PATH_MFMA}, {800, 64, 512, 1, NNS_PATH_MFMA},
                                     {64, 64, 512, 2, NNS_PATH_MFMA},   {200, 64, 512, 2, NNS_PATH_MFMA},
-                                    {64, 64, 512, DT_I8, NNS_PATH_MFMA}, {8, 64, 512, DT_B1, NNS_PATH_AUTO}};
+                                    {64, 64, 512, DT_I8, NNS_PATH_MFMA}, {8, 64, 512, DT_B1, NNS_PATH_AUTO},
+                                    {64, 64, 512, DT_U8, NNS_PATH_MFMA}};
     const int kmax = 800, mmax = 64, nmax = 512;
     float *q = (float *)malloc(sizeof(float) * kmax * mmax), *r = (float *)malloc(sizeof(float) * kmax * nmax);
     int *idx = (int *)malloc(sizeof(int) * mmax);
@@ -2300,14 +2391,15 @@ int nns_warmup(int device)
         if (sh[3] == DT_B1) {
             // the same numbers' fp32 bit patterns as words (q and r hold at least sh[0] * sh[1] and sh[0] * sh[2] floats)
             rc = search_host_impl(sh[0], sh[1], sh[2], q, r, DT_B1, idx, nullptr, 1, (unsigned)sh[4], device);
-        } else if (sh[3] == DT_I8) {
-            // the same numbers (in [0, 1)) as int8 values -128 .. 127
+        } else if (dt_i8_image(sh[3])) {
+            // the same numbers (in [0, 1)) as int8 values -128 .. 127 (uint8 points: 0 .. 255)
+            const int off = sh[3] == DT_U8 ? 0 : 128;
             int8_t *qb = (int8_t *)malloc((size_t)sh[0] * sh[1]);
             int8_t *rb = (int8_t *)malloc((size_t)sh[0] * sh[2]);
             if (qb && rb) {
-                for (int i = 0; i < sh[0] * sh[1]; ++i) qb[i] = (int8_t)((int)(q[i] * 256.0f) - 128);
-                for (int i = 0; i < sh[0] * sh[2]; ++i) rb[i] = (int8_t)((int)(r[i] * 256.0f) - 128);
-                rc = search_host_impl(sh[0], sh[1], sh[2], qb, rb, DT_I8, idx, nullptr, 1, (unsigned)sh[4], device);
+                for (int i = 0; i < sh[0] * sh[1]; ++i) qb[i] = (int8_t)((int)(q[i] * 256.0f) - off);
+                for (int i = 0; i < sh[0] * sh[2]; ++i) rb[i] = (int8_t)((int)(r[i] * 256.0f) - off);
+                rc = search_host_impl(sh[0], sh[1], sh[2], qb, rb, sh[3], idx, nullptr, 1, (unsigned)sh[4], device);
             } else {
                 rc = NNS_ERR_NOMEM;
             }

@@ -201,10 +201,12 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
 
 // ---- point element types ------------------------------------------------------------------------------------------
 // The dtype of an index and of its queries, the `int bf16` argument of the launchers: fp32, bf16 bit patterns, IEEE
-// binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word, the dimension counts words).
-// Element size: dt_size(dtype).
-enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4 };
-inline size_t dt_size(int dt) { return dt == DT_I8 ? 1 : dt == DT_B1 ? 4 : dt ? 2 : 4; }
+// binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word, the dimension counts words),
+// uint8 values.  Element size: dt_size(dtype).
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4, DT_U8 = 5 };
+inline size_t dt_size(int dt) { return (dt == DT_I8 || dt == DT_U8) ? 1 : dt == DT_B1 ? 4 : dt ? 2 : 4; }
+// the 8-bit point types share the int8 operand image, OpI8's filter and its plans (uint8: biased by 128 in K2)
+inline bool dt_i8_image(int dt) { return dt == DT_I8 || dt == DT_U8; }
 // uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
 struct f16_t {
     uint16_t bits;
@@ -218,7 +220,7 @@ __device__ __forceinline__ float f16_widen_hi(unsigned w) { return f16_widen((un
 __device__ __forceinline__ unsigned f16_narrow(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
 
 // point loads of the lane-per-ref scans (K1b, K6, K7): one fp32 value, or four of a 16-byte (fp32) / 8-byte (bf16, fp16) /
-// 4-byte (int8) aligned row; bf16 and fp16 bits and int8 values are widened exactly
+// 4-byte (int8, uint8) aligned row; bf16 and fp16 bits and int8 / uint8 values are widened exactly
 __device__ __forceinline__ float pt_ld1(const float *p) { return *p; }
 __device__ __forceinline__ float pt_ld1(const uint16_t *p) { return __uint_as_float((unsigned)*p << 16); }
 __device__ __forceinline__ float4 pt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -248,6 +250,24 @@ __device__ __forceinline__ float4 pt_ld4(const i8_t *p)
     o.y = i8_widen(v, 1);
     o.z = i8_widen(v, 2);
     o.w = i8_widen(v, 3);
+    return o;
+}
+// uint8 points travel as u8_t; every uint8 value is exact in fp32
+struct u8_t {
+    uint8_t v;
+};
+static_assert(sizeof(u8_t) == 1 && alignof(u8_t) == 1, "u8_t is the raw byte");
+// byte e (0 .. 3) of a 32-bit word as an unsigned value, widened to fp32 (v_cvt_f32_ubyte0 .. 3: one instruction, exact)
+__device__ __forceinline__ float u8_widen(unsigned w, int e) { return (float)((w >> (8 * e)) & 0xFFu); }
+__device__ __forceinline__ float pt_ld1(const u8_t *p) { return (float)p->v; }
+__device__ __forceinline__ float4 pt_ld4(const u8_t *p)
+{
+    const unsigned v = *reinterpret_cast<const unsigned *>(p);   // 4 uint8 of a 4-byte aligned row, widened exactly
+    float4 o;
+    o.x = u8_widen(v, 0);
+    o.y = u8_widen(v, 1);
+    o.z = u8_widen(v, 2);
+    o.w = u8_widen(v, 3);
     return o;
 }
 __device__ __forceinline__ float pt_ld1(const f16_t *p) { return f16_widen(p->bits); }
@@ -541,6 +561,7 @@ struct FilterGeom {
     int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; tau mode 4)
     int i8;               // 1: int8 points on v_mfma_i32_16x16x64_i8 (OpI8: kt = 256 on the 128-deep bf16 geometry, bf16 = 1
                           // too; exact integer scores, tau mode 1's margin, filter form 5)
+    int u8;               // 1: the points are uint8 (i8 = 1 too: K2 biases them by 128 into the int8 image; K5 reads u8_t)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
     int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
@@ -713,6 +734,18 @@ __host__ __device__ inline float range_threshold(int kt, float qnorm2, float yma
     return thr + 0x1p-22f * (radius2 + qnorm2);
 }
 
+// K7m's flag threshold of a uint8 query (range_mfma.hip, RmU8Tile).  Score and distance are exact integers there: with
+// x' = x - 128, y' = y - 128 the score is s = |y'|^2 - 2 x'.y', |s| < 2^24, and V0's distance is d = |x'|^2 + s, an integer
+// of at most 16 646 400 < 2^24.  So d <= radius2  <=>  d <= R := floor(min(radius2, 2^24)), an integer in 0 .. 2^24.
+// qnorm2 = |x'|^2 is an integer in 0 .. 2^22, so R - qnorm2 is an integer in -2^22 .. 2^24: the fp32 subtraction is exact,
+// and s <= thr  <=>  s + |x'|^2 <= R  <=>  d <= radius2.  No margin: a block is flagged if and only if it holds a hit.
+// radius2 >= 0 and not NaN (the callers' check); +INF is the callers' case (thr = -INF and a filled row).
+__host__ __device__ inline float range_threshold_u8(float qnorm2, float radius2)
+{
+#pragma clang fp contract(off)
+    return floorf(fminf(radius2, 0x1p24f)) - qnorm2;
+}
+
 // tau(a) of K1f, the vector-ALU filter of k <= 3 (exact_kernels.hip, lowdim_filter_kernel), in fp32, rounded up everywhere.
 // Its score is an FMA chain of 2K steps (K for the norm of y' = fl(r - c), K for -2 x'.y' on top of it), so the relative
 // part is tau_consts' model at kt = 2K <= 8 with (X + Y)^2 <= 2 (X^2 + Y^2): c0 <= 62.2 u (X^2 + Y^2), c1 <= 20.1 u.
@@ -880,8 +913,10 @@ int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, con
 // dims 64 ks + 16 (l >> 4) .. + 15 of point 16 tile + (l & 15)), the VALUES themselves (no scale: -2 v does not fit int8,
 // the filter applies it), zero-padded; norms = the exact integer |v|^2 as fp32 (pad points: pad_norm); max_norm_bits as
 // the bf16 form's.  No max-|v| word: int8 has no value that voids the filter.
+// bias (uint8 points): the image byte is u ^ 0x80, read as int8 u - 128; the norm is the sum of (u - 128)^2 over the k real
+// dimensions, the padded dimensions hold 0 AFTER the bias
 int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img,
-                         float *norms, unsigned *max_norm_bits, hipStream_t st);
+                         float *norms, unsigned *max_norm_bits, hipStream_t st, bool bias = false);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
 // the int8 pre-pass's operands beside the lazy image (K2, I8PreArgs): given to launch_filter, a lazy search at kt = 128
@@ -898,8 +933,9 @@ struct FilterPreArgs {
 // f16 (with bf16 = true): fp16 points — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
 // i8 (with bf16 = true): int8 points — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of
 // bytes = a 16x16x32 fragment of bf16: 8 fragments per 32-ref block either way); k > 256: unsupported
+// u8 (with i8 = true): uint8 points — int8's plan field for field; only g->u8 differs
 int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
-                bool split = false, bool split_eager = false, bool f16 = false, bool i8 = false);
+                bool split = false, bool split_eager = false, bool f16 = false, bool i8 = false, bool u8 = false);
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
@@ -965,7 +1001,8 @@ struct RangeMfmaPlan {
     int qw;               // queries per workgroup of the flag pass
     int n_pad, total_slots, blocks, wpq;   // K2's padding; ring slots; 32-ref blocks and flag words per query
     int lazy_img;         // the ref image is in the lazy layout
-    int bf16;             // 1: bf16 points (K2's order-1 image, range_flag16_kernel, tau mode 1); 0: fp32 points
+    int bf16;             // the point dtype.  DT_BF16: K2's order-1 image, range_flag16_kernel, tau mode 1; DT_U8: the
+                          // biased int8 image, range_flag_u8_kernel, the exact threshold; DT_F32: fp32 points
     int batch, batches;   // queries per flag-bitmap batch (whole workgroups), batches
     size_t flag_bytes;    // the bitmap of one batch
     int gx, gy, slots_per_split, lds;      // flag pass: grid of a full batch, slots per ref-range split, LDS bytes
@@ -973,7 +1010,8 @@ struct RangeMfmaPlan {
     int tiles;            // tiles of the lims scan
     size_t offs_bytes, ws_bytes;   // K7's workspace layout: [m][echunks] counts (several chunks), then the tile sums
 };
-int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, bool bf16 = false);
+// dtype: DT_F32, DT_BF16 or DT_U8 (planned through filter_plan's int8 geometry: kt = 256, 8 fragments per block)
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, int dtype = DT_F32);
 // radius2v (optional, K6m): the batch's per-query squared radii, used instead of radius2; a query whose entry is not
 // finite gets its flag row filled like a void query's; filled (optional): += the rows filled
 int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const void *q, const void *qimg, const float *qnorm,
@@ -997,7 +1035,7 @@ struct TopkMfmaPlan {
     RangeMfmaPlan rp;     // filtered: the flag pass (its evaluation chunks are the selection's)
 };
 constexpr int kTopkMfmaMinQueries = 64;   // the filters' query floor
-int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, bool bf16 = false);
+int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, int dtype = DT_F32);
 // bound[i] = the distance of keys[i][kn - 1], +INF for NNS_KEY_NONE
 int launch_topk_bound(const nns_key *keys, int m, int kn, float *bound, hipStream_t st);
 // the selection of one query batch: rows [i0, i0 + rows) of out[chunks][m][kn] (one chunk: the caller's keys); stat: +=

@@ -935,7 +935,11 @@ int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, con
 // ds_read_b128.  The bytes, blocks and fragment order of the 128-deep order-1 bf16 image.  The image holds the VALUES
 // (-2 v does not fit int8: the filter applies the factor), zero-padded to KT; the norms are exact integers <= 2^22,
 // stored as fp32.  int8 has no NaN / INF / huge value: no max-|v| word.
-template <int KT>
+// BIAS (uint8 points): every byte that exists is stored as u ^ 0x80, which read as int8 is u - 128; (q - 128) - (r - 128) =
+// q - r, so scores and distances on the biased image are those of the uint8 values.  The padding (dims k .. KT - 1, rows
+// past the last point) holds 0 AFTER the bias, in queries and refs alike, and the norm is the sum over the k real
+// dimensions of (u - 128)^2 <= 256 * 128^2 = 2^22.
+template <int KT, bool BIAS>
 __global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const int8_t *__restrict__ pts, float pad_norm,
                                                        uint4 *__restrict__ img, float *__restrict__ norms,
                                                        unsigned *__restrict__ max_norm_bits)
@@ -945,13 +949,16 @@ __global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const in
     const int tid = threadIdx.x;
     const int blk = blockIdx.x;
     const int p0 = blk * 32;
+    constexpr unsigned FLIP = BIAS ? 0x80808080u : 0u;   // the top bit of each byte
     if ((k & 15) == 0 && (((uintptr_t)pts) & 15) == 0) {
         // sixteen values per load, only the chunks that exist: the block's rows are one contiguous run of 32 k bytes
         const int kc = k >> 4, nrows = min(32, npts - p0);
         const uint4 *src = reinterpret_cast<const uint4 *>(pts + (size_t)p0 * k);
         for (int e = tid; e < nrows * kc; e += 256) {
             const int i = e / kc, c = e - i * kc;
-            *reinterpret_cast<uint4 *>(&tile[i * LD + 16 * c]) = src[e];
+            uint4 v = src[e];
+            if constexpr (BIAS) v = make_uint4(v.x ^ FLIP, v.y ^ FLIP, v.z ^ FLIP, v.w ^ FLIP);
+            *reinterpret_cast<uint4 *>(&tile[i * LD + 16 * c]) = v;
         }
         for (int e = tid; e < 32 * (KT / 16); e += 256) {   // zero padding: dims k .. KT - 1, rows past the last point
             const int i = e / (KT / 16), c = e - i * (KT / 16);
@@ -961,14 +968,14 @@ __global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const in
         for (int e = tid; e < 32 * (KT / 4); e += 256) {   // four values per load
             const int i = e / (KT / 4), t4 = e - i * (KT / 4);
             unsigned v = 0;
-            if (4 * t4 < k && p0 + i < npts) v = *reinterpret_cast<const unsigned *>(pts + (size_t)(p0 + i) * k + 4 * t4);
+            if (4 * t4 < k && p0 + i < npts) v = *reinterpret_cast<const unsigned *>(pts + (size_t)(p0 + i) * k + 4 * t4) ^ FLIP;
             *reinterpret_cast<unsigned *>(&tile[i * LD + 4 * t4]) = v;
         }
     } else {
         for (int e = tid; e < 32 * KT; e += 256) {
             const int i = e / KT, t = e - i * KT;
             int8_t v = 0;
-            if (t < k && p0 + i < npts) v = pts[(size_t)(p0 + i) * k + t];
+            if (t < k && p0 + i < npts) v = (int8_t)(pts[(size_t)(p0 + i) * k + t] ^ (int8_t)(FLIP & 0xFFu));
             tile[i * LD + t] = v;
         }
     }
@@ -1010,14 +1017,18 @@ __global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const in
 }
 
 int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img, float *norms,
-                         unsigned *max_norm_bits, hipStream_t st)
+                         unsigned *max_norm_bits, hipStream_t st, bool bias)
 {
     if (kt != 256 || k > kt) {
         set_error("prep: unsupported int8 tile K %d (k = %d)", kt, k);
         return NNS_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(image_i8_kernel<256>, dim3(npts_pad / 32), dim3(256), 0, st, k, npts, pts, pad_norm, (uint4 *)img,
-                       norms, max_norm_bits);
+    if (bias)   // (uint8 points: the same bytes with the top bit flipped)
+        hipLaunchKernelGGL((image_i8_kernel<256, true>), dim3(npts_pad / 32), dim3(256), 0, st, k, npts, pts, pad_norm,
+                           (uint4 *)img, norms, max_norm_bits);
+    else
+        hipLaunchKernelGGL((image_i8_kernel<256, false>), dim3(npts_pad / 32), dim3(256), 0, st, k, npts, pts, pad_norm,
+                           (uint4 *)img, norms, max_norm_bits);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }

@@ -22,6 +22,9 @@
 //   bf16 points: the same ring, bitmap and evaluation; the tile is the 1-NN bf16 filter's (OpBF16T): K2's order-1
 //               image, v_mfma_f32_16x16x32_bf16, ONE product per score (the operands are exact: no hi / lo, no
 //               centring), threshold range_threshold(..., tau mode 1), 32 <= k <= 256.
+//   uint8 points: the same ring, bitmap and evaluation; the tile is the int8 filter's (OpI8): K2's int8 image of the
+//               values biased by 128, v_mfma_i32_16x16x64_i8, always at depth 256; the score is an exact integer and so
+//               is the threshold (range_threshold_u8): a block is flagged if and only if it holds a hit.  32 <= k <= 256.
 // The evaluation alone decides hits; a false flag costs time, never an answer.  Why no hit is missed: DESIGN §4 "K7m".
 //
 // Shared with the rest: the plan's geometry is filter_plan's (FilterGeom: fragment steps per block, query blocks per wave,
@@ -37,6 +40,7 @@ namespace nns {
 typedef float rm_f32x16 __attribute__((ext_vector_type(16)));
 typedef float rm_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 rm_bf16x8 __attribute__((ext_vector_type(8)));
+typedef int rm_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRmWaves = kSplitWaves;                  // waves per workgroup: two per SIMD
 constexpr int kRmSlotSteps = kSplitSlotSteps;          // 1 KiB fragments per ring slot
@@ -60,6 +64,11 @@ __device__ __forceinline__ rm_f32x4 rm_mma16(const float4 &a, const float4 &b, r
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rm_bf16x8, a), __builtin_bit_cast(rm_bf16x8, b), acc, 0, 0,
                                                    0);
+}
+
+__device__ __forceinline__ rm_i32x4 rm_mma8(const float4 &a, const float4 &b, rm_i32x4 acc)
+{
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(rm_i32x4, a), __builtin_bit_cast(rm_i32x4, b), acc, 0, 0, 0);
 }
 
 struct RangeFlagArgs {
@@ -243,6 +252,91 @@ struct RmBf16Tile {
     }
 };
 
+// uint8 points on v_mfma_i32_16x16x64_i8 over K2's int8 image of the values biased by 128 (prep_kernels.hip,
+// image_i8_kernel): fragment 4 t + ks of a 32-point block holds, at lane l, dims 64 ks + 16 (l >> 4) .. + 15 of point
+// 16 t + (l & 15); always kt = 256, so SPB = 8 (OpI8's block: RmBf16Tile<8>'s bytes).  Refs are A, queries B; C lane l
+// holds query column l & 15 and ref rows 4 (l >> 4) .. + 3.  Registers: the wave's 2 QB = 4 query tiles x 4 k-steps
+// resident = 64 operand registers, 4 thresholds, 4 flag-row pointers (8); per block 2 x 4 i32 accumulators of 4 = 32,
+// two ref fragments in flight = 8, the norms 8.  The accumulators start at the zero constant; after the fourth k-step an
+// element becomes s = fma(-2, (float)acc, |y'|^2), exact as in OpI8::retire (|acc| <= 2^22, the norm an integer <= 2^22,
+// |s| < 2^24), and is tested against the exact threshold (range_threshold_u8).  A padding ref's norm is +INF: s = +INF,
+// never below a threshold.  Through the builtin: the compiler keeps the MFMA hazards.
+template <int SPB, int QB>
+struct RmU8Tile {
+    static constexpr int NKS = SPB / 2;   // 64-dim k-steps: kt / 64
+    static constexpr int NQT = 2 * QB;    // 16-query tiles per wave
+    static_assert(SPB == 8, "kt = 256: OpI8's blocks");
+    float4 bq[NQT][NKS];
+    float thr[NQT];
+    unsigned *row[NQT];   // the flag row of the lane's query of tile qt: 16 qt + (lane & 15) of the wave's queries
+
+    __device__ __forceinline__ void load(const RangeFlagArgs &a, int qblk0, int lane)
+    {
+        const float4 *src = a.qimg + (size_t)qblk0 * (SPB * 64) + lane;
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+            // query block qt >> 1 of the wave, its point tile qt & 1
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) bq[qt][ks] = src[((qt >> 1) * SPB + (qt & 1) * NKS + ks) * 64];
+            const int qi = qblk0 * 32 + 16 * qt + (lane & 15);
+            // (padding rows and a per-query radius that is not finite: -INF, nothing passes; the latter's row is filled
+            //  behind this pass)
+            const bool live = qi < a.rows_live;
+            const float r2 = a.radius2v && live ? a.radius2v[qi] : a.radius2;
+            thr[qt] = live && r2 < __builtin_inff() ? range_threshold_u8(a.qnorm[qi], r2) : -__builtin_inff();
+            row[qt] = a.flags + (size_t)qi * a.wpq;
+        }
+    }
+    __device__ __forceinline__ void pin()
+    {
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks)
+                asm volatile("" : "+v"(bq[qt][ks].x), "+v"(bq[qt][ks].y), "+v"(bq[qt][ks].z), "+v"(bq[qt][ks].w));
+            asm volatile("" : "+v"(thr[qt]));
+        }
+    }
+    __device__ __forceinline__ void block(const char *slot, int blk, int bg, int lane) const
+    {
+        rm_i32x4 acc[2][NQT];
+        const rm_i32x4 z = {0, 0, 0, 0};
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) acc[rt][qt] = z;
+        const float4 *fp = reinterpret_cast<const float4 *>(slot + blk * (SPB * 1024)) + lane;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const float4 r0 = fp[ks * 64], r1 = fp[(NKS + ks) * 64];
+#pragma unroll
+            for (int qt = 0; qt < NQT; ++qt) {
+                acc[0][qt] = rm_mma8(r0, bq[qt][ks], acc[0][qt]);
+                acc[1][qt] = rm_mma8(r1, bq[qt][ks], acc[1][qt]);
+            }
+        }
+        // |y'_j|^2 of the lane's rows: 16 rt + 4 (lane >> 4) + 0 .. 3
+        const float *nrm = reinterpret_cast<const float *>(slot + kRmSlotCoord) + blk * 32 + 4 * (lane >> 4);
+        const float4 n0 = *reinterpret_cast<const float4 *>(nrm), n1 = *reinterpret_cast<const float4 *>(nrm + 16);
+        const float nv[2][4] = {{n0.x, n0.y, n0.z, n0.w}, {n1.x, n1.y, n1.z, n1.w}};
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+            bool pass = false;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float s = __builtin_fmaf(-2.0f, (float)acc[rt][qt][e], nv[rt][e]);   // exact
+                    pass = pass || !(s > thr[qt]);
+                }
+            // (the four lanes of a query, and both ref tiles, set the same bit)
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(pass) != 0ull, 0)) {   // rare, wave-uniform
+                if (pass) atomicOr(row[qt] + (bg >> 5), 1u << (bg & 31));
+            }
+        }
+    }
+};
+
 // The flag pass of one workgroup: the ring over the refs of split blockIdx.y, TILE's body on every block of every slot.
 // SPB: 1 KiB fragment steps per 32-ref block of K2's image (a ring slot is kRmSlotSteps of them, contiguous in the eager
 // addressing); QB: 32-query blocks per wave
@@ -337,6 +431,13 @@ template <int SPB, int QB>
 __global__ __launch_bounds__(kRmWaves * 64) void range_flag16_kernel(const RangeFlagArgs a)
 {
     range_flag_main<SPB, QB, RmBf16Tile<SPB, QB>>(a);
+}
+
+// uint8 points: SPB = 8 (kt = 256 on 64-dim k-steps: four blocks per ring slot)
+template <int SPB, int QB>
+__global__ __launch_bounds__(kRmWaves * 64) void range_flag_u8_kernel(const RangeFlagArgs a)
+{
+    range_flag_main<SPB, QB, RmU8Tile<SPB, QB>>(a);
 }
 
 // one wave per query of the batch: a non-finite coordinate or |v| >= 1e17 — or, with per-query radii, a radius that is
@@ -445,21 +546,26 @@ __global__ __launch_bounds__(kRmEvalThreads) void range_eval_kernel(int k, int r
 // query blocks per wave (64 / 128 resident operand registers, no scratch), the split operators' workgroup and ring slot
 static_assert(kRmBf16QB * kRmWaves * 32 == 512, "filter_plan's queries per workgroup at the 16x16x32 depths");
 
-int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, bool bf16)
+int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, int dtype)
 {
+    if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_U8) {
+        set_error("the range-MFMA flag: no flag pass for point dtype %d", dtype);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    const bool bf16 = dtype != DT_F32, u8 = dtype == DT_U8;   // (uint8 points: the int8 tile's geometry = the 128-deep bf16 one)
     if (k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
-        set_error(bf16 ? "the range-MFMA flag: k = %d outside 32 .. 256 (bf16 points: the 16x16x32 tiles)"
+        set_error(bf16 ? "the range-MFMA flag: k = %d outside 32 .. 256 (bf16 and uint8 points: the 16x16 tiles)"
                        : "the range-MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
     }
     FilterGeom g{};
-    NNS_TRY(filter_plan(k, m, n, bf16, &g, false, false, !bf16, split_eager));
-    if (bf16 ? (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && g.spb != 16)) : !g.split) {
-        set_error("the range-MFMA flag: no %s tile for k = %d", bf16 ? "16x16x32 bf16" : "split-bf16", k);
+    NNS_TRY(filter_plan(k, m, n, bf16, &g, false, false, !bf16, split_eager, false, u8, u8));
+    if (bf16 ? (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && (u8 || g.spb != 16))) : !g.split) {
+        set_error("the range-MFMA flag: no %s tile for k = %d", u8 ? "16x16x64 int8" : bf16 ? "16x16x32 bf16" : "split-bf16", k);
         return NNS_ERR_UNSUPPORTED;
     }
-    p->bf16 = bf16 ? 1 : 0;
+    p->bf16 = dtype;
     p->kt = g.kt;
     p->spb = g.spb;
     p->qb = g.qb;
@@ -540,7 +646,13 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
     const int gx = rows_pad / p.qw;
     // (spb, qb) of the two 16x16x32 bf16 operators, of the five eager split operators
     const auto is = [&p](int spb, int qb) { return p.spb == spb && p.qb == qb; };
-    if (p.bf16 && is(8, kRmBf16QB)) NNS_TRY((launch_flag16_t<8>(p, a, gx, st)));
+    if (p.bf16 == DT_U8) {
+        if (!is(8, kRmBf16QB) || p.kt != 256) {
+            set_error("the range-MFMA flag: no uint8 flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
+            return NNS_ERR_UNSUPPORTED;
+        }
+        NNS_TRY(launch_lds(range_flag_u8_kernel<8, kRmBf16QB>, dim3(gx, p.gy), dim3(kRmWaves * 64), (size_t)kRmLds, st, a));
+    } else if (p.bf16 && is(8, kRmBf16QB)) NNS_TRY((launch_flag16_t<8>(p, a, gx, st)));
     else if (p.bf16 && is(16, kRmBf16QB)) NNS_TRY((launch_flag16_t<16>(p, a, gx, st)));
     else if (p.bf16) {
         set_error("the range-MFMA flag: no bf16 flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
@@ -554,7 +666,11 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
         set_error("the range-MFMA flag: no flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
         return NNS_ERR_UNSUPPORTED;
     }
-    if (p.bf16)
+    if (p.bf16 == DT_U8)   // (no uint8 value voids a row: only a per-query radius that is not finite fills one)
+        hipLaunchKernelGGL(range_void_rows_kernel<u8_t>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k,
+                           rows, (const u8_t *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v,
+                           filled);
+    else if (p.bf16)
         hipLaunchKernelGGL(range_void_rows_kernel<uint16_t>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k,
                            rows, (const uint16_t *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v,
                            filled);
@@ -572,7 +688,7 @@ static int launch_range_eval_t(const RangeMfmaPlan &p, bool fill, int k, int i0,
                                float *dist, unsigned long long *stat, hipStream_t st)
 {
     int *offs = p.echunks > 1 ? (int *)ws : nullptr;
-    // (K7's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) aligned)
+    // (K7's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) / 4-byte (uint8) aligned)
     const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
     const dim3 grid(divup(rows, kRmEvalWaves), p.echunks);
     const size_t lds = (size_t)kRmEvalWaves * k * sizeof(float);
@@ -588,6 +704,9 @@ int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows
                       const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
                       unsigned long long *stat, hipStream_t st)
 {
+    if (p.bf16 == DT_U8)
+        return launch_range_eval_t(p, fill, k, i0, rows, n, (const u8_t *)q, (const u8_t *)r, flags, radius2, base, lims, ws,
+                                   idx, dist, stat, st);
     if (p.bf16)
         return launch_range_eval_t(p, fill, k, i0, rows, n, (const uint16_t *)q, (const uint16_t *)r, flags, radius2, base,
                                    lims, ws, idx, dist, stat, st);

@@ -190,6 +190,8 @@ int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const voi
     nns_key *scan_out = p.splits > 1 ? ws : keys;
     if (bf16 == DT_B1)
         NNS_TRY(launch_topk_scan<b1_t>(p, k, m, n, kn, bstride, (const b1_t *)q, (const b1_t *)r, base, scan_out, st));
+    else if (bf16 == DT_U8)
+        NNS_TRY(launch_topk_scan<u8_t>(p, k, m, n, kn, bstride, (const u8_t *)q, (const u8_t *)r, base, scan_out, st));
     else if (bf16 == DT_I8)
         NNS_TRY(launch_topk_scan<i8_t>(p, k, m, n, kn, bstride, (const i8_t *)q, (const i8_t *)r, base, scan_out, st));
     else if (bf16 == DT_F16)

@@ -142,15 +142,16 @@ __global__ __launch_bounds__(kTopkThreads) void topk_select_kernel(int k, int i0
 // keeps the scan's list warm-up small against the sample.  Where that asks for more than every second block and the
 // unweighted rule (w = 1) does not, every second block is taken.  Every floor(blocks / sb)-th block is taken, so the
 // sample is spread over the whole ref range.
-int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, bool bf16)
+int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, int dtype)
 {
+    const bool bf16 = dtype != DT_F32;   // (bf16 and uint8 points: the depths of the 16x16 tiles)
     if (k <= 0 || m <= 0 || n <= 0 || kn <= 0) return NNS_ERR_INVALID;
     if (kn > NNS_TOPK_MAX) {
         set_error("top-K: kn = %d above 256", kn);
         return NNS_ERR_UNSUPPORTED;
     }
     if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
-        set_error(bf16 ? "the top-K MFMA flag: k = %d outside 32 .. 256 (bf16 points: the 16x16x32 tiles)"
+        set_error(bf16 ? "the top-K MFMA flag: k = %d outside 32 .. 256 (bf16 and uint8 points: the 16x16 tiles)"
                        : "the top-K MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
     }
@@ -173,7 +174,7 @@ int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *
     p->sample_refs = (int)((int64_t)(p->sample_blocks - 1) * 32 + (n - last < 32 ? n - last : 32));
     p->lds = (int)topk_select_lds(k, kn);
     if (p->stride < 2 || m < kTopkMfmaMinQueries) return NNS_OK;
-    if (range_mfma_plan(k, m, n, split_eager, &p->rp, bf16) != NNS_OK) {
+    if (range_mfma_plan(k, m, n, split_eager, &p->rp, dtype) != NNS_OK) {
         p->rp = RangeMfmaPlan{};
         return NNS_OK;
     }
@@ -196,7 +197,7 @@ static int launch_topk_select_t(const TopkMfmaPlan &p, int k, int i0, int rows, 
                                 const void *flags, const float *bound, int64_t base, nns_key *out,
                                 unsigned long long *stat, hipStream_t st)
 {
-    // (K6's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) aligned)
+    // (K6's rule: four values of a row per load where the rows are 16- (fp32) / 8-byte (bf16) / 4-byte (uint8) aligned)
     const bool vec = (k % 4 == 0) && (((uintptr_t)r & (4 * sizeof(T) - 1)) == 0);
     return launch_lds(vec ? topk_select_kernel<4, T> : topk_select_kernel<1, T>, dim3(rows, p.rp.echunks), dim3(kTopkThreads),
                       topk_select_lds(k, kn), st, k, i0, m, n, kn, p.rp.eper, p.rp.wpq, q, r, (const unsigned *)flags, bound,
@@ -207,6 +208,9 @@ int launch_topk_select(const TopkMfmaPlan &p, int k, int i0, int rows, int m, in
                        const void *flags, const float *bound, int64_t base, nns_key *out, unsigned long long *stat,
                        hipStream_t st)
 {
+    if (p.rp.bf16 == DT_U8)
+        return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const u8_t *)q, (const u8_t *)r, flags, bound, base, out, stat,
+                                    st);
     if (p.rp.bf16)
         return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const uint16_t *)q, (const uint16_t *)r, flags, bound, base,
                                     out, stat, st);

@@ -35,7 +35,7 @@ NNS_RECORDS_PER_REF = 512
 NNS_FILTER_F32 = 1024   # fp32 points: fp32 filter operands instead of the default split-bf16 ones
 NNS_FILTER_SPLIT_EAGER = 2048   # split-bf16 operands: the eager schedule (three products per tile) at every depth
 # range search through the MFMA flag pass (K7m) / top-K through the bound / flag / select path (K6m): fp32 points on
-# split-bf16 operands, 8 <= k <= 256; bf16 points on exact operands, 32 <= k <= 256
+# split-bf16 operands, 8 <= k <= 256; bf16 points on exact operands and uint8 points on the int8 MFMA, 32 <= k <= 256
 NNS_RANGE_MFMA = 4096
 NNS_TOPK_MFMA = 8192
 # the int8 pre-pass of the 128-deep lazy filter: off / force ("auto": neither; the device decides per search)
@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "nns_index_create_i8", "nns_index_search_i8", "nns_search_i8_ex", "nns_search_i8_topk", "nns_search_i8_range",
     "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk", "nns_search_b1_range",
     "nns_index_filter_pre", "nns_i8pre_bound", "nns_selftest_mfma_i8pre",
+    "nns_index_create_u8", "nns_index_search_u8", "nns_search_u8_ex", "nns_search_u8_topk", "nns_search_u8_range",
+    "nns_plan_range_mfma_u8", "nns_plan_topk_mfma_u8", "nns_range_threshold_u8",
 )
 # the newest of them: a build from before they existed, loaded through NNS_LIB_PATH as an A/B arm, may lack these (they
 # then fail when called); build() requires every symbol of the tree's own library
@@ -79,7 +81,9 @@ OPTIONAL_SYMBOLS = ("nns_filter_lazy_tile", "nns_selftest_mfma_lazy16",
                     "nns_search_i8_range",
                     "nns_index_create_b1", "nns_index_search_b1", "nns_search_b1_ex", "nns_search_b1_topk",
                     "nns_search_b1_range",
-                    "nns_index_filter_pre", "nns_i8pre_bound", "nns_selftest_mfma_i8pre")
+                    "nns_index_filter_pre", "nns_i8pre_bound", "nns_selftest_mfma_i8pre",
+                    "nns_index_create_u8", "nns_index_search_u8", "nns_search_u8_ex", "nns_search_u8_topk",
+                    "nns_search_u8_range", "nns_plan_range_mfma_u8", "nns_plan_topk_mfma_u8", "nns_range_threshold_u8")
 NNS_TOPK_MAX = 256
 NNS_COMM_ID_BYTES = 128
 
@@ -197,7 +201,15 @@ def _load() -> ctypes.CDLL:
                 "nns_search_b1_range": lib.nns_search_f32_range.argtypes,
                 "nns_index_filter_pre": [c_vp, ctypes.POINTER(c_int)],
                 "nns_i8pre_bound": [ctypes.c_float] * 6 + [c_vp],
-                "nns_selftest_mfma_i8pre": [c_vp, c_vp, c_vp, c_vp]}
+                "nns_selftest_mfma_i8pre": [c_vp, c_vp, c_vp, c_vp],
+                "nns_index_create_u8": lib.nns_index_create.argtypes,
+                "nns_index_search_u8": lib.nns_index_search.argtypes,
+                "nns_search_u8_ex": lib.nns_search_f32_ex.argtypes,
+                "nns_search_u8_topk": lib.nns_search_f32_topk.argtypes,
+                "nns_search_u8_range": lib.nns_search_f32_range.argtypes,
+                "nns_plan_range_mfma_u8": lib.nns_plan_range_mfma.argtypes,
+                "nns_plan_topk_mfma_u8": lib.nns_plan_topk_mfma.argtypes,
+                "nns_range_threshold_u8": [ctypes.c_float, ctypes.c_float, c_vp]}
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -297,7 +309,7 @@ def split_lazy_bound(kt: int, qnorm2: float, ymax2: float) -> float:
 
 def plan_filter(k: int, m: int, n: int, bf16: bool = False, flags: int = 0, schedule: bool = False) -> dict:
     """nns_plan_filter: the MFMA filter's launch geometry for a shape (host only).  bf16: False / True, 2 for fp16 or 3
-    for int8 points (here and in plan_topk / plan_range; those two also take 4, binary points, with k in bits).  "split": 1 when fp32 points
+    for int8, 5 for uint8 points (here and in plan_topk / plan_range; those two also take 4, binary points, with k in bits).  "split": 1 when fp32 points
     take split-bf16 operands (the default; NNS_FILTER_F32 in flags: fp32 operands, 0).  schedule=True asks for the
     16th field too, "lazy": 1 when the split operands run the lazy schedule (0 with NNS_FILTER_SPLIT_EAGER)."""
     nf = 16 if schedule else 15
@@ -337,9 +349,12 @@ def plan_range(k: int, m: int, n: int, bf16: bool = False) -> dict:
 def plan_range_mfma(k: int, m: int, n: int, flags: int = 0, *, bf16: bool = False) -> dict:
     """nns_plan_range_mfma: the launch geometry of the MFMA-filtered range search (K7m) for a shape (host only);
     flags: the index's (NNS_FILTER_SPLIT_EAGER selects the eager ref image layout).  bf16: the plan for bf16 points
-    (nns_plan_range_mfma_bf16; layout 2 = the order-1 16x16x32 image)."""
+    (nns_plan_range_mfma_bf16; layout 2 = the order-1 16x16x32 image); bf16=5: the plan for uint8 points
+    (nns_plan_range_mfma_u8; kt = 256, layout 3 = the int8 image)."""
     out = np.zeros(10, np.int32)
-    if bf16:
+    if bf16 == 5:
+        _check(lib.nns_plan_range_mfma_u8(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma_u8")
+    elif bf16:
         _check(lib.nns_plan_range_mfma_bf16(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma_bf16")
     else:
         _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
@@ -352,9 +367,11 @@ def plan_topk_mfma(k: int, m: int, n: int, kn: int, flags: int = 0, *, bf16: boo
     """nns_plan_topk_mfma: the plan of the MFMA-filtered top-K search (K6m) for a shape (host only): the block sample of
     the bound scan, whether the filtered path is taken, and then plan_range_mfma's fields, the selection's chunks per
     query and flag words per chunk (zeros otherwise), and the LDS bytes of a selection workgroup.  bf16: the plan for
-    bf16 points (nns_plan_topk_mfma_bf16)."""
+    bf16 points (nns_plan_topk_mfma_bf16); bf16=5: for uint8 points (nns_plan_topk_mfma_u8)."""
     out = np.zeros(17, np.int32)
-    if bf16:
+    if bf16 == 5:
+        _check(lib.nns_plan_topk_mfma_u8(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma_u8")
+    elif bf16:
         _check(lib.nns_plan_topk_mfma_bf16(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma_bf16")
     else:
         _check(lib.nns_plan_topk_mfma(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma")
@@ -372,6 +389,13 @@ def range_threshold(kt: int, qnorm2: float, ymax2: float, radius2: float, *, bf1
         _check(lib.nns_range_threshold_bf16(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold_bf16")
     else:
         _check(lib.nns_range_threshold(kt, qnorm2, ymax2, radius2, out.ctypes.data), "nns_range_threshold")
+    return float(out[0])
+
+
+def range_threshold_u8(qnorm2: float, radius2: float) -> float:
+    """nns_range_threshold_u8: the exact score threshold of a uint8 query of biased squared norm qnorm2 (host only)."""
+    out = np.zeros(1, np.float32)
+    _check(lib.nns_range_threshold_u8(qnorm2, radius2, out.ctypes.data), "nns_range_threshold_u8")
     return float(out[0])
 
 
@@ -564,6 +588,36 @@ def search_i8(query_points, reference_points, *, return_distances: bool = False,
     return (idx, dist) if return_distances else idx
 
 
+def to_u8(a) -> np.ndarray:
+    """A numpy uint8 array as a contiguous 2-D uint8 array of point values 0 .. 255 (other dtypes are refused: nothing is
+    quantised silently)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError("uint8 point sets must be numpy uint8 arrays")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("uint8 point sets must be 2-D arrays")
+    return a
+
+
+def search_u8(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
+              path: str = "auto", device: int = 0):
+    """search() for uint8 point sets (numpy uint8, values 0 .. 255) [points][k]: V0's arithmetic on the values widened
+    exactly to fp32 (nns_search_u8_ex).  For k <= 256 the distances are the exact integer squared distances."""
+    q = to_u8(query_points)
+    r = to_u8(reference_points)
+    if q.shape[1] != r.shape[1]:
+        raise ValueError("query and reference dimensionality differ")
+    m, k = q.shape
+    n = r.shape[0]
+    idx = np.empty(m, dtype=np.int32)
+    dist = np.empty(m, dtype=np.float32) if return_distances else None
+    _check(lib.nns_search_u8_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
+                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
+           "nns_search_u8_ex")
+    return (idx, dist) if return_distances else idx
+
+
 def pack_bits(a) -> np.ndarray:
     """A [n][k] array of bool / 0-1 values as packed binary points: uint8 [n][4 * ceil(k / 32)], bit t of a point at
     (byte[t // 8] >> (t % 8)) & 1 (= bit t % 32 of little-endian word t // 32), zero-padded to whole 32-bit words.
@@ -624,7 +678,7 @@ def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_so
     n = r.shape[1] if refs_soa else r.shape[0]
     idx = np.empty((m, max(kn, 0)), dtype=np.int32)
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
-    fn = lib.nns_search_b1_topk if bf16 == 4 else lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
+    fn = lib.nns_search_u8_topk if bf16 == 5 else lib.nns_search_b1_topk if bf16 == 4 else lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
         else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
               shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
@@ -667,6 +721,13 @@ def search_topk_i8(query_points, reference_points, kn: int, *, return_distances:
     return _search_topk(to_i8(query_points), to_i8(reference_points), kn, 3, return_distances, shards, path, device, False)
 
 
+def search_topk_u8(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
+                   path: str = "auto", device: int = 0, topk_mfma: bool = False):
+    """search_topk() for uint8 point sets (numpy uint8; nns_search_u8_topk).  topk_mfma: NNS_TOPK_MFMA (32 <= k <= 256)."""
+    return _search_topk(to_u8(query_points), to_u8(reference_points), kn, 5, return_distances, shards, path, device, False,
+                        topk_mfma)
+
+
 def search_topk_b1(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
                    path: str = "auto", device: int = 0):
     """search_topk() for packed binary points (see to_b1 / pack_bits; nns_search_b1_topk)."""
@@ -683,7 +744,7 @@ def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa,
     lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
     pidx = ctypes.POINTER(ctypes.c_int)()
     pdist = ctypes.POINTER(ctypes.c_float)()
-    fn = lib.nns_search_b1_range if bf16 == 4 else lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
+    fn = lib.nns_search_u8_range if bf16 == 5 else lib.nns_search_b1_range if bf16 == 4 else lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
         else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
               ctypes.byref(pdist) if return_distances else None,
@@ -737,6 +798,14 @@ def search_range_i8(query_points, reference_points, radius2: float, *, return_di
     return _search_range(to_i8(query_points), to_i8(reference_points), radius2, 3, return_distances, path, device, False)
 
 
+def search_range_u8(query_points, reference_points, radius2: float, *, return_distances: bool = False,
+                    path: str = "auto", device: int = 0, range_mfma: bool = False):
+    """search_range() for uint8 point sets (numpy uint8; nns_search_u8_range).  range_mfma: NNS_RANGE_MFMA
+    (32 <= k <= 256)."""
+    return _search_range(to_u8(query_points), to_u8(reference_points), radius2, 5, return_distances, path, device, False,
+                         range_mfma)
+
+
 def search_range_b1(query_points, reference_points, radius2: float, *, return_distances: bool = False,
                     path: str = "auto", device: int = 0):
     """search_range() for packed binary points (see to_b1 / pack_bits; nns_search_b1_range): radius2 is compared with the
@@ -766,7 +835,7 @@ class Index:
     def __init__(self, refs, *, index_base: int = 0, path: str = "auto", profile: bool = False, stream=None,
                  soa: bool = False, filter_bf16: bool = False, filter_f32: bool = False,
                  filter_split_eager: bool = False, range_mfma: bool = False, topk_mfma: bool = False,
-                 filter_i8pre: str = "auto"):
+                 filter_i8pre: str = "auto", points=None):
         """refs: [n][k] (or, with soa=True, dimension-major [k][n]: NNS_REFS_SOA) on a HIP device.
         filter_f32: fp32 points through fp32 filter operands (NNS_FILTER_F32) instead of split-bf16 ones.
         filter_split_eager: the split operands' eager schedule at every depth (NNS_FILTER_SPLIT_EAGER).
@@ -774,7 +843,9 @@ class Index:
         topk_mfma: top-K searches of this index go through the bound / flag / select path (NNS_TOPK_MFMA).
         filter_i8pre: "auto" | "off" | "force" — the int8 pre-pass of the 128-deep lazy filter (NNS_FILTER_I8PRE_*).
         A torch.uint8 [n][kb] tensor is a set of packed binary points (pack_bits' layout; kb % 4 == 0, 4-byte aligned):
-        Hamming distance, self.k = 8 * kb bits, self.b1 is true, queries are uint8 [m][kb] likewise."""
+        Hamming distance, self.k = 8 * kb bits, self.b1 is true, queries are uint8 [m][kb] likewise.
+        points: None infers the point type from the tensor's dtype as above; "u8" takes a torch.uint8 [n][k] tensor as
+        uint8 point values 0 .. 255 (self.u8 is true; range_mfma / topk_mfma at 32 <= k <= 256)."""
         import torch
         if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int8, torch.uint8) or refs.dim() != 2 \
                 or not refs.is_contiguous() or not refs.is_cuda:
@@ -782,7 +853,12 @@ class Index:
         self.bf16 = refs.dtype == torch.bfloat16
         self.f16 = refs.dtype == torch.float16
         self.i8 = refs.dtype == torch.int8
-        self.b1 = refs.dtype == torch.uint8
+        if points not in (None, "u8"):
+            raise ValueError('points must be None (inferred from the dtype) or "u8"')
+        if points == "u8" and refs.dtype != torch.uint8:
+            raise ValueError('points="u8" takes a torch.uint8 tensor')
+        self.u8 = points == "u8"
+        self.b1 = refs.dtype == torch.uint8 and not self.u8
         if self.b1 and (refs.shape[1] % 4 != 0 or refs.data_ptr() % 4 != 0):
             raise ValueError("packed binary refs hold whole 32-bit words: kb % 4 == 0 and a 4-byte aligned data_ptr()")
         self.refs = refs  # keep alive: the index reads the original values
@@ -797,7 +873,7 @@ class Index:
             | (NNS_TOPK_MFMA if topk_mfma else 0) | _I8PRE[filter_i8pre]
         self.flags = flags
         h = ctypes.c_void_p()
-        create = lib.nns_index_create_b1 if self.b1 else lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
+        create = lib.nns_index_create_u8 if self.u8 else lib.nns_index_create_b1 if self.b1 else lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
             else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
@@ -823,7 +899,7 @@ class Index:
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
-        fn = lib.nns_index_search_b1 if self.b1 else lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
+        fn = lib.nns_index_search_u8 if self.u8 else lib.nns_index_search_b1 if self.b1 else lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
             else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
         _check(fn(self._h, m, queries.data_ptr(), keys.data_ptr(), _stream_ptr(stream)), "nns_index_search")
         return keys
@@ -943,7 +1019,7 @@ class Index:
         d = st.asdict()
         # the filter's operand form the index uses: "split" (split-bf16, fp32 points by default), "fp32"
         # (NNS_FILTER_F32 or a depth without the split form), "bf16" (bf16 points / NNS_FILTER_BF16), "f16" (fp16 points),
-        # "i8" (int8 points);
+        # "i8" (int8 and uint8 points: the int8 filter);
         # None: exact path
         form = ctypes.c_int(-1)
         _check(lib.nns_index_filter_form(self._h, ctypes.byref(form)), "nns_index_filter_form")

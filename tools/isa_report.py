@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / spill / v_mov report of the filter kernels' ISA (tuning aid); `isa_report.py b1`: the Hamming scans of
-binary points instead (K1b, K6, K7 for b1_t)."""
+binary points instead (K1b, K6, K7 for b1_t); `isa_report.py u8`: K6's scan for int8 and uint8 points."""
 import importlib.util, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("c", os.path.join(ROOT, "tools", "check_mfma_hazards.py"))
@@ -55,8 +55,61 @@ def b1_report():
     print(tmp)
 
 
+def bytes_report():
+    """`isa_report.py u8`: the int8 (i8_t) and uint8 (u8_t) instantiations of K6's scan (topk_kernels.hip).  Per kernel the
+    registers, and the census of its hottest loop (the innermost loop body with the most byte-to-float conversions): the
+    row loads, the widening instructions (v_cvt_f32_ubyte0 .. 3 for uint8; v_bfe_i32 / shifts + v_cvt_f32_i32 for int8), and
+    from them what the loop issues per 4 dimensions (= per 32-bit row load of the VEC 4 form)."""
+    import subprocess, tempfile
+    csrc = os.path.join(ROOT, "nns-cuda_amd", "csrc")
+    tmp = tempfile.mkdtemp(prefix="nns_isa_u8_")
+    out = os.path.join(tmp, "topk_kernels.s")
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                    "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", out,
+                    os.path.join(csrc, "topk_kernels.hip")], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    txt = open(out).read()
+    lines = txt.splitlines()
+    meta = {re.search(r"\.name:\s+(\S+)", b).group(1): b
+            for b in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", txt, flags=re.S)}
+    conv = ("v_cvt_f32_ubyte", "v_cvt_f32_i32")
+    for sym in [l.split(":")[0] for l in lines if l.startswith("_ZN3nns") and "@" in l and ("4i8_t" in l or "4u8_t" in l)]:
+        start = next(i for i, l in enumerate(lines) if l.startswith(sym + ":"))
+        end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
+        body = [l.split(";")[0].strip() for l in lines[start:end]]
+        labels = {l[:-1]: i for i, l in enumerate(body) if re.fullmatch(r"\.LBB\d+_\d+:", l)}
+        best = None
+        for i, l in enumerate(body):
+            mm = re.match(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l)
+            if not mm or labels.get(mm.group(1), i) >= i:
+                continue
+            loop = body[labels[mm.group(1)] + 1:i]
+            if any(re.fullmatch(r"\.LBB\d+_\d+:", x) for x in loop):
+                continue
+            n = sum(x.startswith(conv) for x in loop)
+            if n and (best is None or n > best[0]):
+                best = (n, loop)
+        g = lambda k: re.search(r"\.%s:\s+(\d+)" % k, meta[sym]).group(1)
+        short = re.sub(r"^_ZN3nns\d+", "", sym)[:56]
+        if best is None:
+            print(short, "no conversion loop")
+            continue
+        n, loop = best
+        cnt = lambda p: sum(x.startswith(p) for x in loop)
+        valu = sum(x.startswith("v_") for x in loop)
+        widen = cnt("v_cvt_f32_ubyte") + cnt("v_cvt_f32_i32") + cnt("v_bfe_i32") + cnt("v_ashrrev_i32") + cnt("v_lshlrev_b32")
+        groups = n / 4.0                                  # 4-dimension groups the loop body widens
+        print(f"{short:56s} vgpr {g('vgpr_count')} spill {g('vgpr_spill_count')} | hot loop: {len(loop)} instr, "
+              f"global_load {cnt('global_load')}, v_cvt_f32_ubyte {cnt('v_cvt_f32_ubyte')}, v_cvt_f32_i32 {cnt('v_cvt_f32_i32')}, "
+              f"v_bfe_i32 {cnt('v_bfe_i32')}, shifts {cnt('v_ashrrev_i32') + cnt('v_lshlrev_b32')}, VALU {valu}, "
+              f"ds_read {cnt('ds_read')} -> per 4 dims: {widen / groups:.2f} widening, {valu / groups:.2f} VALU")
+    print(tmp)
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "b1":
     b1_report()
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "u8":
+    bytes_report()
     sys.exit(0)
 path = m.compile_isa()
 txt = open(path).read()
