@@ -1758,7 +1758,7 @@ int exact_plan(int k, int m, int n, bool bf16, bool refs_aligned, bool have_ws, 
     return NNS_OK;
 }
 
-int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int bf16,
+int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int dtype,
                         int64_t index_base, nns_key *keys, nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out,
                         hipStream_t st)
 {
@@ -1771,23 +1771,15 @@ int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, 
         return launch_k1c(p, k, m, n, (const float *)q, (const float *)r, index_base, keys, ws, ws_fresh, idx_out,
                           dist_out, st);
     NNS_TRY(launch_keys_fill(keys, m, NNS_KEY_NONE, st));
-    if (bf16 == DT_B1)
-        NNS_TRY(launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, nullptr, nullptr, m, index_base, keys, st));
-    else if (bf16 == DT_U8)
-        NNS_TRY(launch_k1b(p, k, n, (const u8_t *)q, (const u8_t *)r, nullptr, nullptr, m, index_base, keys, st));
-    else if (bf16 == DT_I8)
-        NNS_TRY(launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, nullptr, nullptr, m, index_base, keys, st));
-    else if (bf16 == DT_F16)
-        NNS_TRY(launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, nullptr, nullptr, m, index_base, keys, st));
-    else if (bf16)
-        NNS_TRY(launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, nullptr, nullptr, m, index_base, keys, st));
-    else
-        NNS_TRY(launch_k1b(p, k, n, (const float *)q, (const float *)r, nullptr, nullptr, m, index_base, keys, st));
+    NNS_TRY(with_point_type(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_k1b(p, k, n, (const T *)q, (const T *)r, nullptr, nullptr, m, index_base, keys, st);
+    }));
     if (idx_out) NNS_TRY(launch_keys_unpack(keys, m, idx_out, dist_out, st));
     return NNS_OK;
 }
 
-int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, const int *qlist, const int *qcount,
+int launch_exact_listed(int k, int n, const void *q, const void *r, int dtype, const int *qlist, const int *qcount,
                         int max_listed, int64_t index_base, nns_key *keys, hipStream_t st)
 {
     if (max_listed <= 0) return NNS_OK;
@@ -1798,12 +1790,10 @@ int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, co
     // batch both keep ~2048 workgroups busy.
     ExactPlan p{};
     k1b_plan(k, n, max_listed, 8, &p);
-    if (bf16 == DT_B1) return launch_k1b(p, k, n, (const b1_t *)q, (const b1_t *)r, qlist, qcount, 0, index_base, keys, st);
-    if (bf16 == DT_U8) return launch_k1b(p, k, n, (const u8_t *)q, (const u8_t *)r, qlist, qcount, 0, index_base, keys, st);
-    if (bf16 == DT_I8) return launch_k1b(p, k, n, (const i8_t *)q, (const i8_t *)r, qlist, qcount, 0, index_base, keys, st);
-    if (bf16 == DT_F16) return launch_k1b(p, k, n, (const f16_t *)q, (const f16_t *)r, qlist, qcount, 0, index_base, keys, st);
-    if (bf16) return launch_k1b(p, k, n, (const uint16_t *)q, (const uint16_t *)r, qlist, qcount, 0, index_base, keys, st);
-    return launch_k1b(p, k, n, (const float *)q, (const float *)r, qlist, qcount, 0, index_base, keys, st);
+    return with_point_type(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_k1b(p, k, n, (const T *)q, (const T *)r, qlist, qcount, 0, index_base, keys, st);
+    });
 }
 
 }  // namespace nns

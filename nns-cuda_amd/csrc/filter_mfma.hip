@@ -502,8 +502,7 @@ struct FilterArgs {
     CandEntry *lists;       // [splits][m_pad/32][kCandCap][64 lanes]
     int *counts;            // [splits][m_pad/32][64 lanes]
     int total_slots, slots_per_split, m_pad, kt;
-    int bf16;               // tau mode: 0 fp32 operands, 1 bf16 points, 2 fp32 points rounded to bf16 operands,
-                            // 3 fp32 points as split-bf16 operands (OpSplitT), 4 fp16 points (OpF16T)
+    int tau_mode;           // TAU_F32 .. TAU_F16 (filter_tau_mode)
     int share_thr;          // short streams: a query's lanes adopt the smallest of their thresholds
     int tile_rec;           // short streams: ONE record per (lane, ref tile) — (tile minimum, first ref of the lane's
                             // rows) — instead of one per score within the threshold; K5 re-ranks the lane's rows
@@ -624,7 +623,7 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
             // (record form 2 keeps no thresholds: skip the margin's double-precision arithmetic, ~1 us of a short stream)
             if (T16 || a.tile_rec != 2)
                 tc[st] = tau_consts(a.kt, a.qnorm[qblk0 * 32 + st * QPS + (lane & (QPS - 1))],
-                                    __uint_as_float(a.scal->ymax2_bits), a.bf16);
+                                    __uint_as_float(a.scal->ymax2_bits), a.tau_mode);
             else
                 tc[st] = TauConsts{0.0f, 0.0f, 0.0f};
             if constexpr (LAZY)
@@ -1712,7 +1711,7 @@ template __global__ void filter_lazy16_kernel<OpLazySplit16>(const FilterArgs a)
 // out[i][j] = accumulate over the image's k order of a[i][.] * b[j][.] seeded with c0[i];
 // a, b are [32][kt] fp32 (bf16 mode: values must be bf16-representable).  Lets the tests
 // check the hardware against host arithmetic — the error model behind tau.
-__global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, const float *__restrict__ a,
+__global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int mode, const float *__restrict__ a,
                                                            const float *__restrict__ b,
                                                            const float *__restrict__ c0,
                                                            float *__restrict__ out)
@@ -1721,12 +1720,12 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = c0[(r & 3) + 8 * (r >> 2) + 4 * h];
-    if (!bf16) {
+    if (mode == ST_F32) {
         for (int s = 0; s < kt / 2; ++s) {
             const int kk = 8 * (s >> 2) + 4 * h + (s & 3);   // same k permutation as the image
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i * kt + kk], b[i * kt + kk], acc, 0, 0, 0);
         }
-    } else if (bf16 == 1) {
+    } else if (mode == ST_BF16) {
         for (int s = 0; s < kt / 16; ++s) {
             bf16x8 av, bv;
 #pragma unroll
@@ -1736,9 +1735,9 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
             }
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
         }
-    } else if (bf16 == 3) {
+    } else if (mode == ST_SPLIT) {
         // the split chain of OpSplitT: v = h + l, h = rn_bf16(v), l = rn_bf16(v - h); per 16-dim k-step (same lane
-        // order as bf16 == 1) ah.bh, ah.bl (the ref hi fragment's two MFMAs), then al.bh (the lo fragment's)
+        // order as ST_BF16) ah.bh, ah.bl (the ref hi fragment's two MFMAs), then al.bh (the lo fragment's)
         for (int s = 0; s < kt / 16; ++s) {
             bf16x8 ah, al, bh, bl;
 #pragma unroll
@@ -1753,7 +1752,7 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
         }
-    } else if (bf16 == 4) {
+    } else if (mode == ST_LAZY) {
         // the lazy order of OpLazySplitT: the kt / 16 hi-hi MFMAs (partial result to out + 1024), then per k-step al.bh
         // (ref hi x query lo) and ah.bl on the same accumulator.  (a = query rows, b = ref rows as above.)
         for (int pass = 0; pass < 2; ++pass) {
@@ -1779,7 +1778,7 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
                 for (int r = 0; r < 16; ++r) out[1024 + ((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + i] = acc[r];
             }
         }
-    } else if (bf16 == 6) {
+    } else if (mode == ST_I8) {
         // mode 2's four 16x16 tiles and lane mapping on v_mfma_i32_16x16x64_i8 (OpI8 and K2's int8 image): lane l holds dims
         // 64 ks + 16 (l >> 4) .. + 15 of row l & 15, byte j of the four operand registers = dim j of the sixteen; operands
         // cast to int8, the i32 accumulator seeded with c0 and returned as fp32
@@ -1808,7 +1807,7 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
                 for (int e = 0; e < 4; ++e) out[(16 * rt + 4 * g + e) * 32 + 16 * qt + c] = (float)t[e];
             }
         return;
-    } else if (bf16 == 5) {
+    } else if (mode == ST_F16) {
         // mode 2's four 16x16 tiles and lane mapping on v_mfma_f32_16x16x32_f16, operands cast to binary16 (OpF16T)
         const int c = lane & 15, g = lane >> 4;
         for (int rt = 0; rt < 2; ++rt)
@@ -1830,7 +1829,7 @@ __global__ __launch_bounds__(64) void mfma_selftest_kernel(int kt, int bf16, con
             }
         return;
     } else {
-        // bf16 == 2: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
+        // ST_BF16_T16: the same 32x32 product as four 16x16 tiles of v_mfma_f32_16x16x32_bf16, with
         // the operand / result lane mapping the filter's OpBF16T and K2's order 1 image assume
         const int c = lane & 15, g = lane >> 4;
         for (int rt = 0; rt < 2; ++rt)
@@ -1974,10 +1973,10 @@ int launch_lane_share_selftest(int t16, const float *in, float *out, hipStream_t
     return NNS_OK;
 }
 
-int launch_mfma_selftest(int kt, int bf16, const float *a, const float *b, const float *c0, float *out,
+int launch_mfma_selftest(int kt, int mode, const float *a, const float *b, const float *c0, float *out,
                          hipStream_t st)
 {
-    hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, st, kt, bf16, a, b, c0, out);
+    hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, st, kt, mode, a, b, c0, out);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
 }
@@ -2063,10 +2062,12 @@ static int with_filter_op(const FilterGeom &g, F &&f)
     return NNS_ERR_UNSUPPORTED;
 }
 
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed, bool per_ref, bool split, bool split_eager,
-                bool f16, bool i8, bool u8)
+int filter_plan(const FilterRequest &rq, FilterGeom *g)
 {
-    if (mixed) bf16 = true;   // fp32 points, bf16 operands: the bf16 filter's geometry
+    const int k = rq.k, m = rq.m, n = rq.n;
+    const bool mixed = rq.mixed, per_ref = rq.per_ref, split = rq.split, split_eager = rq.split_eager;
+    const bool f16 = rq.dtype == DT_F16, i8 = point_type(rq.dtype).i8_image, u8 = rq.dtype == DT_U8;
+    const bool bf16 = dt_bf16_like(rq.dtype) || mixed;   // (mixed: fp32 points, bf16 operands: the bf16 filter's geometry)
     int kt = 0;
     if (i8) {                          // int8 points: the one 16x16x64 depth (k <= 128 pads to it too)
         if (k <= 256) kt = 256;
@@ -2217,7 +2218,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
     a.slots_per_split = g.slots_per_split;
     a.m_pad = g.m_pad;
     a.kt = g.kt;
-    a.bf16 = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
+    a.tau_mode = filter_tau_mode(g);
     a.share_thr = g.share_thr;   // (filter_plan)
     a.tile_rec = g.tile_rec;
 #ifdef NNS_DIAG

@@ -203,7 +203,7 @@ __device__ __forceinline__ unsigned long long k5_stamp()
 // evaluation, so keys, fallbacks and multi-candidate queries are the same for every input.
 template <typename T>
 __global__ __launch_bounds__(64) void finalize_kernel(
-    int kt, int bf16, int lpq, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
+    int kt, int tau_mode, int lpq, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
     const T *__restrict__ r, const CandEntry *__restrict__ lists, const int *__restrict__ counts,
     const float *__restrict__ qnorm, DevScalars *__restrict__ scal, int64_t index_base,
     nns_key *__restrict__ keys, int *__restrict__ amb_list, int *__restrict__ multi_list K5_DIAG_PARAM)
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(
     }
 
     // (mode 4, fp16 points: a ref beyond kF16RefMax has no finite scaled operand — the host latch's twin)
-    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, bf16 == 4);
+    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, tau_mode == TAU_F16);
     float a = __builtin_inff();
     int over = 0;
     if (!fallback && live) {
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(
     float thr = 0.0f;
     const bool walks = !fallback && live;
     if (walks) {
-        const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), bf16);
+        const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), tau_mode);
         thr = a + tau_of(tc, a);
     }
     for (int s = 0; s < splits; ++s) {
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(
 // candidates inside its own list walk — with the stamps of the diagnostic buffer, to measure what the compaction buys.
 template <typename T>
 __global__ __launch_bounds__(64) void finalize_sparse_kernel(
-    int kt, int bf16, int lpq, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
+    int kt, int tau_mode, int lpq, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
     const T *__restrict__ r, const CandEntry *__restrict__ lists, const int *__restrict__ counts,
     const float *__restrict__ qnorm, DevScalars *__restrict__ scal, int64_t index_base,
     nns_key *__restrict__ keys, int *__restrict__ amb_list, int *__restrict__ multi_list, unsigned long long *__restrict__ diag)
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(64) void finalize_sparse_kernel(
     unsigned long long d_eval = 0;
     unsigned d_rounds = 0, d_active = 0;
 
-    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, bf16 == 4);
+    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, tau_mode == TAU_F16);
     float a = __builtin_inff();
     int over = 0;
     if (!fallback && live) {
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(64) void finalize_sparse_kernel(
         const bool walks = !fallback && live;
         float thr = 0.0f;
         if (walks) {
-            const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), bf16);
+            const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), tau_mode);
             thr = a + tau_of(tc, a);
         }
         const T *qi = q + (size_t)i * k;
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(64) void finalize_sparse_kernel(
 // arithmetic; rows that are not in C_i take part in the exact minimum too, which cannot change V0's answer.
 template <typename T>
 __global__ __launch_bounds__(256) void finalize_wave_kernel(
-    int kt, int bf16, int lpq, int tile_rec, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
+    int kt, int tau_mode, int lpq, int tile_rec, int m_pad, int splits, int k, int m, int n, const T *__restrict__ q,
     const T *__restrict__ r, const CandEntry *__restrict__ lists, const int *__restrict__ counts,
     const float *__restrict__ qnorm, DevScalars *__restrict__ scal, int64_t index_base,
     nns_key *__restrict__ keys, int *__restrict__ amb_list, int *__restrict__ multi_list)
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256) void finalize_wave_kernel(
     const int nlists = lpq * splits;
     const int ush = lpq == 4 ? 4 : 5, qmask = (1 << ush) - 1, lsh = lpq == 4 ? 2 : 1;
     // (mode 4, fp16 points: a ref beyond kF16RefMax has no finite scaled operand — the host latch's twin)
-    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, bf16 == 4);
+    bool fallback = scal->q_maxabs_bits >= kHugeBits || refs_void(scal->r_maxabs_bits, tau_mode == TAU_F16);
     float a = __builtin_inff();
     int over = 0;
     for (int l = lane; l < nlists; l += 64) {
@@ -542,7 +542,7 @@ __global__ __launch_bounds__(256) void finalize_wave_kernel(
     nns_key best = NNS_KEY_NONE;
     int ncand = 0;
     if (!fallback) {
-        const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), bf16);
+        const TauConsts tc = tau_consts(kt, qnorm[i], __uint_as_float(scal->ymax2_bits), tau_mode);
         const float thr = a + tau_of(tc, a);
         const T *qi = q + (size_t)i * k;
         const bool vec = (k & 3) == 0 && (((uintptr_t)q | (uintptr_t)r) & (4 * sizeof(T) - 1)) == 0;
@@ -637,34 +637,32 @@ __global__ __launch_bounds__(256) void finalize_wave_kernel(
     }
 }
 
+// f(PointTag<T>{}) for the element type of the q / r that geometry g was planned for (the uint8 points' lists are the
+// int8 image's, the re-rank reads the uint8 values; binary points have no filter: no K5 is built for them)
+template <class F>
+static int with_geom_type(const FilterGeom &g, F &&f)
+{
+    const int dtype = g.u8 ? DT_U8 : g.i8 ? DT_I8 : g.f16 ? DT_F16 : (g.bf16 && !g.mixed) ? DT_BF16 : DT_F32;
+    return with_point_type(dtype, [&](auto tag) {
+        if constexpr (std::is_same_v<typename decltype(tag)::type, b1_t>) return (int)NNS_ERR_INVALID;
+        else return f(tag);
+    });
+}
+
 int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, const void *r,
                     const CandEntry *lists, const int *counts, const float *qnorm, DevScalars *scal,
                     int64_t index_base, nns_key *keys, int *amb_list, int *multi_list, hipStream_t st)
 {
-    // tau mode (nns_internal.h; int8 points: mode 1 — exact scores, exact V0 distances, so mode 1's margin is a valid one)
-    const int mode = g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
-    const bool data_bf16 = g.bf16 && !g.mixed && !g.f16 && !g.i8;    // element type of q / r
+    // (int8 and uint8 points: TAU_BF16 — exact scores, exact V0 distances, so its margin is a valid one)
+    const int tau_mode = filter_tau_mode(g);
     if (g.splits >= 4) {   // few queries, many lists per query: one wave per query
-        if (g.u8)   // (uint8 points: the int8 image's lists, the re-rank on the uint8 values)
-            hipLaunchKernelGGL(finalize_wave_kernel<u8_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
-                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const u8_t *)q, (const u8_t *)r, lists,
-                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
-        else if (g.i8)
-            hipLaunchKernelGGL(finalize_wave_kernel<i8_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
-                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists,
-                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
-        else if (g.f16)
-            hipLaunchKernelGGL(finalize_wave_kernel<f16_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
-                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists,
-                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
-        else if (data_bf16)
-            hipLaunchKernelGGL(finalize_wave_kernel<uint16_t>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode,
-                               g.lpq, g.tile_rec, g.m_pad, g.splits, k, m, n, (const uint16_t *)q, (const uint16_t *)r, lists,
-                               counts, qnorm, scal, index_base, keys, amb_list, multi_list);
-        else
-            hipLaunchKernelGGL(finalize_wave_kernel<float>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, mode, g.lpq, g.tile_rec,
-                               g.m_pad, g.splits, k, m, n, (const float *)q, (const float *)r, lists, counts, qnorm, scal,
-                               index_base, keys, amb_list, multi_list);
+        NNS_TRY(with_geom_type(g, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(finalize_wave_kernel<T>, dim3(divup(m, 4)), dim3(256), 0, st, g.kt, tau_mode, g.lpq,
+                               g.tile_rec, g.m_pad, g.splits, k, m, n, (const T *)q, (const T *)r, lists, counts, qnorm,
+                               scal, index_base, keys, amb_list, multi_list);
+            return (int)NNS_OK;
+        }));
         NNS_HIP(hipGetLastError());
         return NNS_OK;
     }
@@ -682,26 +680,13 @@ int launch_finalize(const FilterGeom &g, int k, int m, int n, const void *q, con
         NNS_HIP(hipMemsetAsync(diag, 0, (size_t)units * 8 * sizeof(unsigned long long), st));
     }
 #endif
-    if (g.u8)
-        hipLaunchKernelGGL(K5_UNIT_KERNEL<u8_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
-                           g.splits, k, m, n, (const u8_t *)q, (const u8_t *)r, lists, counts, qnorm,
-                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
-    else if (g.i8)
-        hipLaunchKernelGGL(K5_UNIT_KERNEL<i8_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
-                           g.splits, k, m, n, (const i8_t *)q, (const i8_t *)r, lists, counts, qnorm,
-                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
-    else if (g.f16)
-        hipLaunchKernelGGL(K5_UNIT_KERNEL<f16_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
-                           g.splits, k, m, n, (const f16_t *)q, (const f16_t *)r, lists, counts, qnorm,
-                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
-    else if (data_bf16)
-        hipLaunchKernelGGL(K5_UNIT_KERNEL<uint16_t>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
-                           g.splits, k, m, n, (const uint16_t *)q, (const uint16_t *)r, lists, counts, qnorm,
-                           scal, index_base, keys, amb_list, multi_list K5_DIAG_ARG);
-    else
-        hipLaunchKernelGGL(K5_UNIT_KERNEL<float>, dim3(units), dim3(64), 0, st, g.kt, mode, g.lpq, g.m_pad,
-                           g.splits, k, m, n, (const float *)q, (const float *)r, lists, counts, qnorm, scal,
-                           index_base, keys, amb_list, multi_list K5_DIAG_ARG);
+    NNS_TRY(with_geom_type(g, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(K5_UNIT_KERNEL<T>, dim3(units), dim3(64), 0, st, g.kt, tau_mode, g.lpq, g.m_pad, g.splits, k,
+                           m, n, (const T *)q, (const T *)r, lists, counts, qnorm, scal, index_base, keys, amb_list,
+                           multi_list K5_DIAG_ARG);
+        return (int)NNS_OK;
+    }));
 #ifdef NNS_DIAG
     if (diag) {
         std::vector<unsigned long long> h((size_t)units * 8);

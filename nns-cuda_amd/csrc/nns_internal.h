@@ -67,10 +67,8 @@ struct DeviceScope {
 int order_after_default_stream(hipStream_t st);
 void stager_release();         // free the small whole calls' pinned scratch (nns_api.hip)
 // the overlapped upload of a contiguous host ref range (nns_api.hip), shared with nns_search_*_multi's shards
-// (`bf16`, here and in every launcher below, is the point dtype: DT_F32, DT_BF16, DT_F16, DT_I8 or DT_B1; for DT_B1
-//  `k` is in 32-bit words everywhere below the C-ABI entry points)
-bool upload_overlap_pays(int k, int64_t m, int64_t n, int bf16, unsigned flags, size_t rbytes);
-int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int bf16,
+bool upload_overlap_pays(int k, int64_t m, int64_t n, int dtype, unsigned flags, size_t rbytes);
+int search_range_overlapped(int device, int k, int m, int n, const void *q_d, const void *r_host, char *r_d, int dtype,
                             int64_t base, unsigned flags, nns_key *keys, nns_key *keys_tmp);
 // the argument checks of every whole-call entry point (nns_search_*_ex / _topk / _multi), before any device work:
 // k, m, n > 0, non-null pointers, NNS_MAX_POINTS and the k * m / k * n bounds; `where` names the entry point
@@ -200,13 +198,51 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
 }
 
 // ---- point element types ------------------------------------------------------------------------------------------
-// The dtype of an index and of its queries, the `int bf16` argument of the launchers: fp32, bf16 bit patterns, IEEE
-// binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word, the dimension counts words),
-// uint8 values.  Element size: dt_size(dtype).
-enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4, DT_U8 = 5 };
-inline size_t dt_size(int dt) { return (dt == DT_I8 || dt == DT_U8) ? 1 : dt == DT_B1 ? 4 : dt ? 2 : 4; }
-// the 8-bit point types share the int8 operand image, OpI8's filter and its plans (uint8: biased by 128 in K2)
-inline bool dt_i8_image(int dt) { return dt == DT_I8 || dt == DT_U8; }
+// The dtype of an index and of its queries (`dtype` everywhere; the C ABI's nns_plan_* take the codes as bf16_points):
+// fp32, bf16 bit patterns, IEEE binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word;
+// below the C-ABI entry points the dimension k counts words), uint8 values.
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4, DT_U8 = 5, DT_COUNT = 6 };
+// What is a fact about a point type, not about a call.  A k range of {0, 0} means "none is built".  The flag masks are
+// what index_create (and, with whole_calls_check, the whole calls) refuse before the device is looked up, with the
+// message "<entry point>: <text> (flags 0x..)"; check_point_flags (nns_api.hip) is the one reader.
+struct PointType {
+    const char *infix;             // of the C ABI's names: nns_search_<infix>_ex, nns_index_create_<infix>
+    const char *name;              // in messages
+    int bytes;                     // of one element
+    bool i8_image;                 // the int8 operand image, OpI8's filter and its plans (uint8: biased by 128 in K2)
+    int filter_kmin, filter_kmax;  // the MFMA filter: AUTO takes it inside this range, NNS_PATH_MFMA up to filter_kmax
+    int flag_kmin, flag_kmax;      // the flag passes (NNS_RANGE_MFMA, NNS_TOPK_MFMA)
+    unsigned invalid_flags;        // answered NNS_ERR_INVALID ...
+    const char *invalid_text;
+    unsigned unsupported_flags;    // ... and NNS_ERR_UNSUPPORTED (a type without a filter: NNS_PATH_MFMA as well)
+    const char *unsupported_text;
+    // The next two columns only record where today's types answer differently from one another (kept: no answer may
+    // change in a refactor).  They go once those answers are made alike; a new type should not lean on them.
+    bool whole_calls_check;        // the whole calls make the check too (fp16 points: index_create alone)
+    bool k_checks;                 // the check also refuses NNS_PATH_MFMA beyond filter_kmax and a flag pass outside its range
+};
+constexpr unsigned kOperandFlags = NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER;
+constexpr unsigned kFlagPassFlags = NNS_RANGE_MFMA | NNS_TOPK_MFMA;
+constexpr PointType kPointTypes[DT_COUNT] = {
+    {"f32", "fp32", 4, false, 8, 256, 8, 256, 0, nullptr, 0, nullptr, false, false},   // (bf16-rounded operands: to 1024)
+    {"bf16", "bf16", 2, false, 32, 1024, 32, 256, 0, nullptr, 0, nullptr, false, false},
+    {"f16", "fp16", 2, false, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points", kFlagPassFlags,
+     "the range-MFMA and top-K MFMA flags are not built for fp16 points", false, false},
+    {"i8", "int8", 1, true, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
+     kFlagPassFlags | NNS_REFS_SOA,
+     "the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points", true, false},
+    {"b1", "binary", 4, false, 0, 0, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
+     kFlagPassFlags | NNS_REFS_SOA | NNS_RECORDS_PER_REF,
+     "no MFMA filter, flag pass or dimension-major form is built for binary points", true, false},
+    {"u8", "uint8", 1, true, 32, 256, 32, 256, kOperandFlags | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE,
+     "the operand flags apply to fp32 points, not to uint8 points", NNS_REFS_SOA,
+     "dimension-major refs are not built for uint8 points", true, true},
+};
+// (a code the ABI does not define counts as bf16 points, as it did when the rules were `dtype != 0`)
+inline const PointType &point_type(int dtype) { return kPointTypes[(unsigned)dtype < DT_COUNT ? dtype : DT_BF16]; }
+// The points are not fp32: they are their own filter operands on the bf16 tile geometry (FilterGeom::bf16), the operand
+// flags do not apply, and the fp32-only exact kernels (K1a, K1f, K1c) are not theirs (exact_plan's `bf16`)
+inline bool dt_bf16_like(int dtype) { return dtype != DT_F32; }
 // uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
 struct f16_t {
     uint16_t bits;
@@ -288,6 +324,31 @@ struct b1_t {
     uint32_t w;
 };
 static_assert(sizeof(b1_t) == 4 && alignof(b1_t) == 4, "b1_t is the raw 32-bit word");
+
+// f(PointTag<T>{}) for the element type T of dtype, in the style of with_qt: the one place a launcher turns the dtype
+// into a kernel's element type.  `default` is bf16 because a code the ABI does not define has always counted as bf16
+// points (point_type); it stands where DT_BF16 stood in the chains this replaces, so that the kernels are instantiated,
+// and laid out in the code object, in the order they always were
+template <typename T>
+struct PointTag {
+    using type = T;
+};
+template <class F>
+static inline int with_point_type(int dtype, F &&f)
+{
+    switch (dtype) {
+    case DT_B1: return f(PointTag<b1_t>{});
+    case DT_U8: return f(PointTag<u8_t>{});
+    case DT_I8: return f(PointTag<i8_t>{});
+    case DT_F16: return f(PointTag<f16_t>{});
+    default: return f(PointTag<uint16_t>{});
+    case DT_F32: return f(PointTag<float>{});
+    }
+}
+static_assert(sizeof(float) == kPointTypes[DT_F32].bytes && sizeof(uint16_t) == kPointTypes[DT_BF16].bytes &&
+                  sizeof(f16_t) == kPointTypes[DT_F16].bytes && sizeof(i8_t) == kPointTypes[DT_I8].bytes &&
+                  sizeof(b1_t) == kPointTypes[DT_B1].bytes && sizeof(u8_t) == kPointTypes[DT_U8].bytes,
+              "the table's element bytes are the tag types' sizes");
 
 __device__ __forceinline__ unsigned pt_ld1(const b1_t *p) { return p->w; }
 // The element type of the LDS query tile of a lane-per-ref scan: the widened fp32 value, or for b1_t the raw word.  The
@@ -558,9 +619,9 @@ __host__ __device__ constexpr bool pre_cadence_ok(int depth, int ahead, int grou
 
 struct FilterGeom {
     int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
-    int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; tau mode 4)
+    int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; TAU_F16)
     int i8;               // 1: int8 points on v_mfma_i32_16x16x64_i8 (OpI8: kt = 256 on the 128-deep bf16 geometry, bf16 = 1
-                          // too; exact integer scores, tau mode 1's margin, filter form 5)
+                          // too; exact integer scores, TAU_BF16's margin, filter form 5)
     int u8;               // 1: the points are uint8 (i8 = 1 too: K2 biases them by 128 into the int8 image; K5 reads u8_t)
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
     int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
@@ -608,21 +669,26 @@ struct TauConsts {
     float c0, c1, x2;
 };
 
-// mode: 0 fp32 operands, 1 bf16 points (operands exact), 2 fp32 points ROUNDED to bf16 operands, 3 fp32 points as
-// SPLIT bf16 operands (hi + lo, three products: OpSplitT), 4 fp16 points (operands exact) on v_mfma_f32_16x16x32_f16:
+// The tau mode of a filter search (FilterArgs::tau_mode, K5's tau_mode; nns_tau_consts takes the values over the ABI):
+// fp32 operands, bf16 points (operands exact), fp32 points ROUNDED to bf16 operands, fp32 points as SPLIT bf16 operands
+// (hi + lo, three products: OpSplitT), fp16 points (operands exact) on v_mfma_f32_16x16x32_f16:
 // two binary16 values multiply exactly in fp32 (11 + 11 significand bits), so mode 1's formula — exact products, the
 // order-free accumulation model at kMode4AddUlps u per add, no centring — holds as it stands ("fp16 points")
 constexpr double kMode4AddUlps = 2.0;
+enum { TAU_F32 = 0, TAU_BF16 = 1, TAU_MIXED = 2, TAU_SPLIT = 3, TAU_F16 = 4 };
+// The chains of nns_selftest_mfma (its own numbering over the ABI: 4 is the lazy order there): fp32, bf16 32x32x16, bf16
+// 16x16x32, the split chain, the split chain in the lazy filter's order, f16 16x16x32, i8 16x16x64
+enum { ST_F32 = 0, ST_BF16 = 1, ST_BF16_T16 = 2, ST_SPLIT = 3, ST_LAZY = 4, ST_F16 = 5, ST_I8 = 6 };
 __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax2, int mode)
 {
-    const bool bf16 = mode != 0;
+    const bool bf16 = mode != TAU_F32;
     const double u = 5.9604644775390625e-08;   // 2^-24
     const double X2 = (double)qnorm2 * (1.0 + 4.0 * u);
     const double Y2 = (double)ymax2 * (1.0 + 4.0 * u);
     const double X = sqrt(X2), Y = sqrt(Y2);
     const double gk = (kt + 2) * u / (1.0 - (kt + 2) * u);   // V0's own rounding (k+1 per term)
     double e3, e2;
-    if (mode == 3) {
+    if (mode == TAU_SPLIT) {
         // Split operands (derivation: DESIGN.md, "Exactness"), a = u_b = 2^-8: v = h + l + d with h = rn_bf16(v),
         // l = rn_bf16(v - h), |h| <= (1 + a)|v|, |l| <= a (1 + a)|v|, |d| <= a^2 |v|.  qh.rh + qh.rl + ql.rh drops
         // qh.d_r + ql.rl + ql.d_r + d_q.v, at most a^2 (3 + 4a + 2a^2) |x'_t v_t| <= 3 * 2^-16 (1 + 2^-6) |x'_t v_t|,
@@ -644,11 +710,11 @@ __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax
     } else {
         // bf16 products are exact in fp32; the accumulation order/rounding inside
         // v_mfma_f32_32x32x16_bf16 is not documented: allow 2u per add, kt + kt/16 adds
-        const double pa = mode == 4 ? kMode4AddUlps : 2.0;   // allowance per add, in u
+        const double pa = mode == TAU_F16 ? kMode4AddUlps : 2.0;   // allowance per add, in u
         const double gf = pa * (kt + kt / 16 + 2) * u / (1.0 - pa * (kt + kt / 16 + 2) * u);
         e3 = gf * (Y2 + 2.0 * X * Y) + 2.0 * u * Y2;
         e2 = 0.0;                            // no centring on the bf16 path
-        if (mode == 2) {
+        if (mode == TAU_MIXED) {
             // operands x^ = rn_bf16(x'), y^ = rn_bf16(y') with |x^ - x'| <= 2^-8 |x'| (8-bit significand):
             // |x^.y^ - x'.y'| <= (2 * 2^-8 + 2^-16) sum |x'_t||y'_t| <= 2^-7 (1 + 2^-9) X Y, doubled by the
             // factor -2 of the score; plus the centring term of the fp32 path (x' = fl(x - c)), and the
@@ -725,7 +791,7 @@ __host__ __device__ inline float record_threshold(const TauConsts &t, float a)
 // mode 1 (bf16 points, range_flag16_kernel): the same form over tau_consts' mode 1 — exact operands and products, the
 // order-free accumulation model, no centring (e2 = 0) — with qnorm2 = K2's uncentred |x|^2 and ymax2 the refs' largest
 // |y|^2.  Monotone in radius2 as well.  DESIGN section 4, "K7m", "bf16 points".
-__host__ __device__ inline float range_threshold(int kt, float qnorm2, float ymax2, float radius2, int mode = 3)
+__host__ __device__ inline float range_threshold(int kt, float qnorm2, float ymax2, float radius2, int mode = TAU_SPLIT)
 {
 #pragma clang fp contract(off)
     const TauConsts t = tau_consts(kt, qnorm2, ymax2, mode);
@@ -877,12 +943,12 @@ int exact_plan(int k, int m, int n, bool bf16, bool refs_aligned, bool have_ws, 
 // ws: p.ws_keys keys for the in-kernel cross-workgroup merge; ws_fresh: it was (re)allocated or re-laid out since
 // the last launch (it is then armed once; it re-arms itself).  idx_out / dist_out (optional): also write the unpacked
 // indices / distances (K1a, K1f, K1c: same launch).
-int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int bf16,
+int launch_exact_search(const ExactPlan &p, int k, int m, int n, const void *q, const void *r, int dtype,
                         int64_t index_base, nns_key *keys, nns_key *ws, bool ws_fresh, int *idx_out, float *dist_out,
                         hipStream_t st);
 // exact scan of the queries listed in qlist[0 .. *qcount) (device memory); keys
 // of listed queries must hold NNS_KEY_NONE on entry (atomic-min merge).
-int launch_exact_listed(int k, int n, const void *q, const void *r, int bf16, const int *qlist, const int *qcount,
+int launch_exact_listed(int k, int n, const void *q, const void *r, int dtype, const int *qlist, const int *qcount,
                         int max_listed, int64_t index_base, nns_key *keys, hipStream_t st);
 
 // prep_kernels.hip (K2)
@@ -929,13 +995,22 @@ struct FilterPreArgs {
     int m;                // real queries of the search
     int force;            // NNS_FILTER_I8PRE_FORCE: run the pre-pass whatever the count says
 };
-// split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth
-// f16 (with bf16 = true): fp16 points — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
-// i8 (with bf16 = true): int8 points — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of
-// bytes = a 16x16x32 fragment of bf16: 8 fragments per 32-ref block either way); k > 256: unsupported
-// u8 (with i8 = true): uint8 points — int8's plan field for field; only g->u8 differs
-int filter_plan(int k, int m, int n, bool bf16, FilterGeom *g, bool mixed = false, bool per_ref = false,
-                bool split = false, bool split_eager = false, bool f16 = false, bool i8 = false, bool u8 = false);
+// What a filter plan is asked for.  mixed / split: operand_form's answer for fp32 points; per_ref: NNS_RECORDS_PER_REF;
+// split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth.  By dtype:
+// DT_F16 — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
+// DT_I8 — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of bytes = a 16x16x32 fragment
+// of bf16: 8 fragments per 32-ref block either way); k > 256: unsupported
+// DT_U8 — int8's plan field for field; only g->u8 differs
+struct FilterRequest {
+    int k, m, n, dtype;
+    bool mixed, per_ref, split, split_eager;
+};
+int filter_plan(const FilterRequest &rq, FilterGeom *g);
+// the tau mode of the search that geometry g runs (launch_filter and K5 agree on it)
+inline int filter_tau_mode(const FilterGeom &g)
+{
+    return g.f16 ? TAU_F16 : g.mixed ? TAU_MIXED : g.split ? TAU_SPLIT : g.bf16 ? TAU_BF16 : TAU_F32;
+}
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,
@@ -943,7 +1018,7 @@ int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const
 int launch_mfma_i8pre_selftest(const int8_t *q, const int8_t *r, const int *seeds, int *out, hipStream_t st);
 int launch_mfma_lazy16_selftest(const float *q, const float *r, const float *c0, float *out, float *out_hh, hipStream_t st);
 int filter_lazy_tile();   // MFMA tile (16 or 32) of the lazy split kernel this build launches (NNS_F_LAZY_T16)
-int launch_mfma_selftest(int kt, int bf16, const float *a, const float *b, const float *c0, float *out,
+int launch_mfma_selftest(int kt, int mode, const float *a, const float *b, const float *c0, float *out,
                          hipStream_t st);
 int launch_lane_share_selftest(int t16, const float *in, float *out, hipStream_t st);
 
@@ -965,7 +1040,7 @@ struct TopkPlan {
 int topk_plan(int k, int m, int n, int kn, TopkPlan *p);
 // keys[m][kn]; ws: p.ws_keys keys (unused with one split)
 // bstride > 1 (K6m's sample): the scan reads every bstride-th 32-ref block of r, n counts the sampled refs
-int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
+int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int dtype,
                        int64_t base, nns_key *keys, nns_key *ws, hipStream_t st, int bstride = 1);
 // rows [0, rows) of ws[splits][m][kn] (m: the row stride of a split) merged into keys[rows][kn]
 int launch_topk_merge_splits(const nns_key *ws, int m, int rows, int kn, int splits, nns_key *keys, hipStream_t st);
@@ -984,10 +1059,10 @@ struct RangePlan {
 };
 int range_plan(int k, int m, int n, RangePlan *p);
 // count pass: lims[m + 1] (int64) and, with several chunks, the per-(query, chunk) start offsets in ws
-int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int dtype, float radius2,
                        int64_t *lims, void *ws, hipStream_t st);
 // fill pass: idx[lims[m]] (global indices), dist (optional) from the lims and ws of the count pass
-int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int dtype, float radius2,
                       int64_t base, const int64_t *lims, const void *ws, int *idx, float *dist, hipStream_t st);
 
 // the lims scans of the count pass alone (offs: [m][chunks] counts -> offsets and lims[i + 1]; one chunk: lims[1 .. m]
@@ -1001,8 +1076,8 @@ struct RangeMfmaPlan {
     int qw;               // queries per workgroup of the flag pass
     int n_pad, total_slots, blocks, wpq;   // K2's padding; ring slots; 32-ref blocks and flag words per query
     int lazy_img;         // the ref image is in the lazy layout
-    int bf16;             // the point dtype.  DT_BF16: K2's order-1 image, range_flag16_kernel, tau mode 1; DT_U8: the
-                          // biased int8 image, range_flag_u8_kernel, the exact threshold; DT_F32: fp32 points
+    int dtype;            // DT_BF16: K2's order-1 image, range_flag16_kernel, TAU_BF16; DT_U8: the biased int8 image,
+                          // range_flag_u8_kernel, the exact threshold; DT_F32: fp32 points
     int batch, batches;   // queries per flag-bitmap batch (whole workgroups), batches
     size_t flag_bytes;    // the bitmap of one batch
     int gx, gy, slots_per_split, lds;      // flag pass: grid of a full batch, slots per ref-range split, LDS bytes

@@ -123,7 +123,7 @@ struct ShardJob {
 };
 
 // one GPU's share: upload, build, search -> keys on that device (core.cu:793-819 per thread)
-static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const void *r, int bf16, unsigned flags)
+static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const void *r, int dtype, unsigned flags)
 {
     auto fail = [&](int rc, const char *what) {
         job->rc = rc;
@@ -131,7 +131,7 @@ static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const v
     };
     if (hipSetDevice(job->device) != hipSuccess) return fail(NNS_ERR_HIP, "hipSetDevice");   // (this thread's device)
     job->st = lib_stream_acquire();   // (nullptr: the default stream)
-    const size_t esz = bf16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t esz = point_type(dtype).bytes;
     const size_t qb = (size_t)m * k * esz, rb = (size_t)job->cnt * k * esz;
     if (pool_alloc(&job->q_d, qb) != hipSuccess || pool_alloc(&job->r_d, rb) != hipSuccess ||
         pool_alloc(&job->keys, (size_t)m * sizeof(nns_key)) != hipSuccess)
@@ -142,12 +142,12 @@ static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const v
         // a dense [k][cnt] device array, which the index transposes (NNS_REFS_SOA)
         up = up && hipMemcpy2D(job->r_d, (size_t)job->cnt * esz, (const char *)r + (size_t)job->beg * esz,
                                (size_t)n * esz, (size_t)job->cnt * esz, (size_t)k, hipMemcpyHostToDevice) == hipSuccess;
-    } else if (up && upload_overlap_pays(k, m, job->cnt, bf16, flags, rb)) {
+    } else if (up && upload_overlap_pays(k, m, job->cnt, dtype, flags, rb)) {
         // a shard worth it goes up in chunks that are searched while the next one is copied (nns_api.hip)
         nns_key *tmp = nullptr;
         if (pool_alloc(&tmp, (size_t)m * sizeof(nns_key)) != hipSuccess) return fail(NNS_ERR_NOMEM, "device allocation");
         const int orc = search_range_overlapped(job->device, k, m, job->cnt, job->q_d, (const char *)r + (size_t)job->beg * k * esz,
-                                                job->r_d, bf16, job->beg, flags, job->keys, tmp);
+                                                job->r_d, dtype, job->beg, flags, job->keys, tmp);
         pool_free(tmp);   // (the overlapped core returns with its stream waited for)
         if (orc == NNS_OK) return;
         // (NOMEM: four chunk indexes carry four query-side workspaces; the plain single-index path may still fit)
@@ -159,17 +159,17 @@ static void run_shard(ShardJob *job, int k, int m, int n, const void *q, const v
     if (!up) return fail(NNS_ERR_HIP, "H2D copy");
     if (order_after_default_stream(job->st) != NNS_OK) return fail(NNS_ERR_HIP, "event edge upload -> search");
     nns_index *ix = nullptr;
-    int rc = bf16 ? nns_index_create_bf16(&ix, job->device, k, job->cnt, (const uint16_t *)job->r_d, job->beg, flags, job->st)
+    int rc = dtype == DT_BF16 ? nns_index_create_bf16(&ix, job->device, k, job->cnt, (const uint16_t *)job->r_d, job->beg, flags, job->st)
                   : nns_index_create(&ix, job->device, k, job->cnt, (const float *)job->r_d, job->beg, flags, job->st);
     if (rc == NNS_OK)
-        rc = bf16 ? nns_index_search_bf16(ix, m, (const uint16_t *)job->q_d, job->keys, job->st)
+        rc = dtype == DT_BF16 ? nns_index_search_bf16(ix, m, (const uint16_t *)job->q_d, job->keys, job->st)
                   : nns_index_search(ix, m, (const float *)job->q_d, job->keys, job->st);
     if (rc == NNS_OK && hipStreamSynchronize(job->st) != hipSuccess) rc = NNS_ERR_HIP;
     nns_index_destroy(ix);
     if (rc != NNS_OK) fail(rc, "search");
 }
 
-static int search_multi_impl(int k, int m, int n, const void *s_points, const void *r_points, int bf16, int *idx_out,
+static int search_multi_impl(int k, int m, int n, const void *s_points, const void *r_points, int dtype, int *idx_out,
                              float *dist_out, int num_devices, unsigned flags)
 {
     // the same checks as the single-device entry points (nns.h), before any thread or allocation
@@ -193,7 +193,7 @@ static int search_multi_impl(int k, int m, int n, const void *s_points, const vo
     // the reference keeps small problems on one GPU (core.cu:775-777)
     const int64_t small_n = ((int64_t)m << 10) < (1 << 18) ? ((int64_t)m << 10) : (1 << 18);
     if (!force && (G == 1 || (!virt && n <= small_n)))
-        return bf16 ? nns_search_bf16_ex(k, m, n, (const uint16_t *)s_points, (const uint16_t *)r_points, idx_out, dist_out, 1, flags, 0)
+        return dtype == DT_BF16 ? nns_search_bf16_ex(k, m, n, (const uint16_t *)s_points, (const uint16_t *)r_points, idx_out, dist_out, 1, flags, 0)
                     : nns_search_f32_ex(k, m, n, (const float *)s_points, (const float *)r_points, idx_out, dist_out, 1, flags, 0);
 
     std::vector<ShardJob> jobs;
@@ -209,7 +209,7 @@ static int search_multi_impl(int k, int m, int n, const void *s_points, const vo
     G = (int)jobs.size();
     {
         std::vector<std::thread> th;
-        for (int g = 0; g < G; ++g) th.emplace_back(run_shard, &jobs[g], k, m, n, s_points, r_points, bf16, flags);
+        for (int g = 0; g < G; ++g) th.emplace_back(run_shard, &jobs[g], k, m, n, s_points, r_points, dtype, flags);
         for (auto &t : th) t.join();
     }
     int rc = NNS_OK;
@@ -317,13 +317,13 @@ extern "C" {
 int nns_search_f32_multi(int k, int m, int n, const float *s_points, const float *r_points, int *idx_out,
                          float *dist_out, int num_devices, unsigned flags)
 {
-    return search_multi_impl(k, m, n, s_points, r_points, 0, idx_out, dist_out, num_devices, flags);
+    return search_multi_impl(k, m, n, s_points, r_points, DT_F32, idx_out, dist_out, num_devices, flags);
 }
 
 int nns_search_bf16_multi(int k, int m, int n, const uint16_t *s_points, const uint16_t *r_points, int *idx_out,
                           float *dist_out, int num_devices, unsigned flags)
 {
-    return search_multi_impl(k, m, n, s_points, r_points, 1, idx_out, dist_out, num_devices, flags);
+    return search_multi_impl(k, m, n, s_points, r_points, DT_BF16, idx_out, dist_out, num_devices, flags);
 }
 
 int nns_comm_unique_id(void *id_out, size_t id_bytes)

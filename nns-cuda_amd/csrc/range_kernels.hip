@@ -285,37 +285,27 @@ static int launch_range_scan(const RangePlan &p, int k, int m, int n, const void
     });
 }
 
-int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+int launch_range_count(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int dtype, float radius2,
                        int64_t *lims, void *ws, hipStream_t st)
 {
     int *offs = p.chunks > 1 ? (int *)ws : nullptr;
     int64_t *sums = p.tiles > 1 ? (int64_t *)((char *)ws + range_offs_bytes(p, m)) : nullptr;
-    if (bf16 == DT_B1)
-        NNS_TRY((launch_range_scan<false, b1_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    else if (bf16 == DT_U8)
-        NNS_TRY((launch_range_scan<false, u8_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    else if (bf16 == DT_I8)
-        NNS_TRY((launch_range_scan<false, i8_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    else if (bf16 == DT_F16)
-        NNS_TRY((launch_range_scan<false, f16_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    else if (bf16)
-        NNS_TRY((launch_range_scan<false, uint16_t>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
-    else
-        NNS_TRY((launch_range_scan<false, float>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st)));
+    NNS_TRY(with_point_type(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_range_scan<false, T>(p, k, m, n, q, r, radius2, 0, lims, offs, nullptr, nullptr, st);
+    }));
     return launch_range_lims(m, p.chunks, p.tiles, offs, sums, lims, st);
 }
 
-int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int bf16, float radius2,
+int launch_range_fill(const RangePlan &p, int k, int m, int n, const void *q, const void *r, int dtype, float radius2,
                       int64_t base, const int64_t *lims, const void *ws, int *idx, float *dist, hipStream_t st)
 {
     int *offs = p.chunks > 1 ? (int *)ws : nullptr;
     int64_t *l = const_cast<int64_t *>(lims);   // (read only by the fill instantiation)
-    if (bf16 == DT_B1) return launch_range_scan<true, b1_t>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
-    if (bf16 == DT_U8) return launch_range_scan<true, u8_t>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
-    if (bf16 == DT_I8) return launch_range_scan<true, i8_t>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
-    if (bf16 == DT_F16) return launch_range_scan<true, f16_t>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
-    if (bf16) return launch_range_scan<true, uint16_t>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
-    return launch_range_scan<true, float>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
+    return with_point_type(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_range_scan<true, T>(p, k, m, n, q, r, radius2, base, l, offs, idx, dist, st);
+    });
 }
 
 }  // namespace nns

@@ -548,24 +548,25 @@ static_assert(kRmBf16QB * kRmWaves * 32 == 512, "filter_plan's queries per workg
 
 int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, int dtype)
 {
-    if (dtype != DT_F32 && dtype != DT_BF16 && dtype != DT_U8) {
+    const PointType &pt = point_type(dtype);
+    if ((unsigned)dtype >= DT_COUNT || !pt.flag_kmax) {   // (a code the ABI does not define has no flag pass either)
         set_error("the range-MFMA flag: no flag pass for point dtype %d", dtype);
         return NNS_ERR_UNSUPPORTED;
     }
-    const bool bf16 = dtype != DT_F32, u8 = dtype == DT_U8;   // (uint8 points: the int8 tile's geometry = the 128-deep bf16 one)
+    const bool bf16 = dt_bf16_like(dtype), u8 = dtype == DT_U8;   // (uint8 points: the int8 tile's geometry = the 128-deep bf16 one)
     if (k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
-    if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
+    if (k < pt.flag_kmin || k > pt.flag_kmax) {
         set_error(bf16 ? "the range-MFMA flag: k = %d outside 32 .. 256 (bf16 and uint8 points: the 16x16 tiles)"
                        : "the range-MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
     }
     FilterGeom g{};
-    NNS_TRY(filter_plan(k, m, n, bf16, &g, false, false, !bf16, split_eager, false, u8, u8));
+    NNS_TRY(filter_plan({k, m, n, dtype, false, false, !bf16, split_eager}, &g));
     if (bf16 ? (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && (u8 || g.spb != 16))) : !g.split) {
         set_error("the range-MFMA flag: no %s tile for k = %d", u8 ? "16x16x64 int8" : bf16 ? "16x16x32 bf16" : "split-bf16", k);
         return NNS_ERR_UNSUPPORTED;
     }
-    p->bf16 = dtype;
+    p->dtype = dtype;
     p->kt = g.kt;
     p->spb = g.spb;
     p->qb = g.qb;
@@ -646,15 +647,15 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
     const int gx = rows_pad / p.qw;
     // (spb, qb) of the two 16x16x32 bf16 operators, of the five eager split operators
     const auto is = [&p](int spb, int qb) { return p.spb == spb && p.qb == qb; };
-    if (p.bf16 == DT_U8) {
+    if (p.dtype == DT_U8) {
         if (!is(8, kRmBf16QB) || p.kt != 256) {
             set_error("the range-MFMA flag: no uint8 flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
             return NNS_ERR_UNSUPPORTED;
         }
         NNS_TRY(launch_lds(range_flag_u8_kernel<8, kRmBf16QB>, dim3(gx, p.gy), dim3(kRmWaves * 64), (size_t)kRmLds, st, a));
-    } else if (p.bf16 && is(8, kRmBf16QB)) NNS_TRY((launch_flag16_t<8>(p, a, gx, st)));
-    else if (p.bf16 && is(16, kRmBf16QB)) NNS_TRY((launch_flag16_t<16>(p, a, gx, st)));
-    else if (p.bf16) {
+    } else if (p.dtype == DT_BF16 && is(8, kRmBf16QB)) NNS_TRY((launch_flag16_t<8>(p, a, gx, st)));
+    else if (p.dtype == DT_BF16 && is(16, kRmBf16QB)) NNS_TRY((launch_flag16_t<16>(p, a, gx, st)));
+    else if (p.dtype == DT_BF16) {
         set_error("the range-MFMA flag: no bf16 flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
         return NNS_ERR_UNSUPPORTED;
     } else if (is(2, 2)) NNS_TRY((launch_flag_t<2, 2>(p, a, gx, st)));
@@ -666,11 +667,11 @@ int launch_range_flags(const RangeMfmaPlan &p, int k, int i0, int rows, const vo
         set_error("the range-MFMA flag: no flag kernel for %d fragment steps per block, %d query blocks per wave", p.spb, p.qb);
         return NNS_ERR_UNSUPPORTED;
     }
-    if (p.bf16 == DT_U8)   // (no uint8 value voids a row: only a per-query radius that is not finite fills one)
+    if (p.dtype == DT_U8)   // (no uint8 value voids a row: only a per-query radius that is not finite fills one)
         hipLaunchKernelGGL(range_void_rows_kernel<u8_t>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k,
                            rows, (const u8_t *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v,
                            filled);
-    else if (p.bf16)
+    else if (p.dtype == DT_BF16)
         hipLaunchKernelGGL(range_void_rows_kernel<uint16_t>, dim3(divup(rows, kRmEvalWaves)), dim3(kRmEvalThreads), 0, st, k,
                            rows, (const uint16_t *)q + (size_t)i0 * k, reinterpret_cast<unsigned *>(flags), p.wpq, radius2v,
                            filled);
@@ -704,10 +705,10 @@ int launch_range_eval(const RangeMfmaPlan &p, bool fill, int k, int i0, int rows
                       const void *flags, float radius2, int64_t base, int64_t *lims, void *ws, int *idx, float *dist,
                       unsigned long long *stat, hipStream_t st)
 {
-    if (p.bf16 == DT_U8)
+    if (p.dtype == DT_U8)
         return launch_range_eval_t(p, fill, k, i0, rows, n, (const u8_t *)q, (const u8_t *)r, flags, radius2, base, lims, ws,
                                    idx, dist, stat, st);
-    if (p.bf16)
+    if (p.dtype == DT_BF16)
         return launch_range_eval_t(p, fill, k, i0, rows, n, (const uint16_t *)q, (const uint16_t *)r, flags, radius2, base,
                                    lims, ws, idx, dist, stat, st);
     return launch_range_eval_t(p, fill, k, i0, rows, n, (const float *)q, (const float *)r, flags, radius2, base, lims, ws,

@@ -184,22 +184,14 @@ static int launch_topk_scan(const TopkPlan &p, int k, int m, int n, int kn, int 
     });
 }
 
-int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int bf16,
+int launch_topk_search(const TopkPlan &p, int k, int m, int n, int kn, const void *q, const void *r, int dtype,
                        int64_t base, nns_key *keys, nns_key *ws, hipStream_t st, int bstride)
 {
     nns_key *scan_out = p.splits > 1 ? ws : keys;
-    if (bf16 == DT_B1)
-        NNS_TRY(launch_topk_scan<b1_t>(p, k, m, n, kn, bstride, (const b1_t *)q, (const b1_t *)r, base, scan_out, st));
-    else if (bf16 == DT_U8)
-        NNS_TRY(launch_topk_scan<u8_t>(p, k, m, n, kn, bstride, (const u8_t *)q, (const u8_t *)r, base, scan_out, st));
-    else if (bf16 == DT_I8)
-        NNS_TRY(launch_topk_scan<i8_t>(p, k, m, n, kn, bstride, (const i8_t *)q, (const i8_t *)r, base, scan_out, st));
-    else if (bf16 == DT_F16)
-        NNS_TRY(launch_topk_scan<f16_t>(p, k, m, n, kn, bstride, (const f16_t *)q, (const f16_t *)r, base, scan_out, st));
-    else if (bf16)
-        NNS_TRY(launch_topk_scan<uint16_t>(p, k, m, n, kn, bstride, (const uint16_t *)q, (const uint16_t *)r, base, scan_out, st));
-    else
-        NNS_TRY(launch_topk_scan<float>(p, k, m, n, kn, bstride, (const float *)q, (const float *)r, base, scan_out, st));
+    NNS_TRY(with_point_type(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return launch_topk_scan<T>(p, k, m, n, kn, bstride, (const T *)q, (const T *)r, base, scan_out, st);
+    }));
     if (p.splits > 1) NNS_TRY(launch_topk_merge_splits(ws, m, m, kn, p.splits, keys, st));
     return NNS_OK;
 }

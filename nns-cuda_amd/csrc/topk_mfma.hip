@@ -144,13 +144,18 @@ __global__ __launch_bounds__(kTopkThreads) void topk_select_kernel(int k, int i0
 // sample is spread over the whole ref range.
 int topk_mfma_plan(int k, int m, int n, int kn, bool split_eager, TopkMfmaPlan *p, int dtype)
 {
-    const bool bf16 = dtype != DT_F32;   // (bf16 and uint8 points: the depths of the 16x16 tiles)
+    const PointType &pt = point_type(dtype);
+    const bool bf16 = dt_bf16_like(dtype);   // (bf16 and uint8 points: the depths of the 16x16 tiles)
     if (k <= 0 || m <= 0 || n <= 0 || kn <= 0) return NNS_ERR_INVALID;
     if (kn > NNS_TOPK_MAX) {
         set_error("top-K: kn = %d above 256", kn);
         return NNS_ERR_UNSUPPORTED;
     }
-    if (bf16 ? (k < 32 || k > 256) : (k < 8 || k > 256)) {
+    if ((unsigned)dtype >= DT_COUNT || !pt.flag_kmax) {   // (no caller passes one: range_mfma_plan's refusal, made here too)
+        set_error("the top-K MFMA flag: no flag pass for point dtype %d", dtype);
+        return NNS_ERR_UNSUPPORTED;
+    }
+    if (k < pt.flag_kmin || k > pt.flag_kmax) {
         set_error(bf16 ? "the top-K MFMA flag: k = %d outside 32 .. 256 (bf16 and uint8 points: the 16x16 tiles)"
                        : "the top-K MFMA flag: k = %d outside 8 .. 256 (the split-bf16 tiles)", k);
         return NNS_ERR_UNSUPPORTED;
@@ -208,10 +213,10 @@ int launch_topk_select(const TopkMfmaPlan &p, int k, int i0, int rows, int m, in
                        const void *flags, const float *bound, int64_t base, nns_key *out, unsigned long long *stat,
                        hipStream_t st)
 {
-    if (p.rp.bf16 == DT_U8)
+    if (p.rp.dtype == DT_U8)
         return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const u8_t *)q, (const u8_t *)r, flags, bound, base, out, stat,
                                     st);
-    if (p.rp.bf16)
+    if (p.rp.dtype == DT_BF16)
         return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const uint16_t *)q, (const uint16_t *)r, flags, bound, base,
                                     out, stat, st);
     return launch_topk_select_t(p, k, i0, rows, m, n, kn, (const float *)q, (const float *)r, flags, bound, base, out, stat,

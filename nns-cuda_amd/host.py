@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import Callable as _Callable, NamedTuple as _NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -110,6 +110,99 @@ class nns_stats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+# ---- host arrays as the library reads them, per point type ----------------------------------------------------------
+def _as_f32(a, what: str) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"{what} must be [points][k]")
+    return a
+
+
+def _as_bf16_bits(a) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.uint16)
+    if a.ndim != 2:
+        raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
+    return a
+
+
+def to_f16_bits(a) -> np.ndarray:
+    """A numpy float16 array, or uint16 bit patterns, as contiguous 2-D uint16 binary16 bit patterns (no conversion of
+    values: other dtypes are refused, so that nothing is rounded silently)."""
+    a = np.asarray(a)
+    if a.dtype == np.float16:
+        a = np.ascontiguousarray(a).view(np.uint16)
+    elif a.dtype != np.uint16:
+        raise ValueError("fp16 point sets must be numpy float16 arrays or uint16 bit patterns")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("fp16 point sets must be 2-D arrays")
+    return a
+
+
+def to_i8(a) -> np.ndarray:
+    """A numpy int8 array as a contiguous 2-D int8 array (other dtypes are refused: nothing is quantised silently)."""
+    a = np.asarray(a)
+    if a.dtype != np.int8:
+        raise ValueError("int8 point sets must be numpy int8 arrays")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("int8 point sets must be 2-D arrays")
+    return a
+
+
+def to_u8(a) -> np.ndarray:
+    """A numpy uint8 array as a contiguous 2-D uint8 array of point values 0 .. 255 (other dtypes are refused: nothing is
+    quantised silently)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError("uint8 point sets must be numpy uint8 arrays")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2:
+        raise ValueError("uint8 point sets must be 2-D arrays")
+    return a
+
+
+def to_b1(a) -> np.ndarray:
+    """Packed binary points, numpy uint8 [.][kb] with kb % 4 == 0 or uint32 [.][kw], as a contiguous uint8 [.][4 * kw]
+    array (anything else, a buffer that is not 4-byte aligned included, is refused)."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.uint32):
+        raise ValueError("binary point sets must be 2-D numpy uint8 or uint32 arrays of packed bits (see pack_bits)")
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.uint8)
+    if a.shape[1] % 4 != 0:
+        raise ValueError("binary point sets hold whole 32-bit words: the byte count per point must be a multiple of 4")
+    if a.ctypes.data % 4 != 0:   # (a view into a byte buffer: the library reads words)
+        raise ValueError("binary point sets must be 4-byte aligned")
+    return a
+
+
+class _PointType(_NamedTuple):
+    """One point type: what differs between the per-dtype entry points and their wrappers here."""
+    code: int            # the C ABI's dtype code (nns_plan_*'s bf16_points; the bf16= arguments here take it)
+    infix: str           # nns_search_<infix>_ex, nns_index_create_<infix>
+    convert: _Callable   # host array -> the contiguous 2-D array the library reads
+    k_mult: int          # k per array column (packed bits: 8 per byte)
+    refs_soa: bool       # dimension-major refs are offered
+    mfma_flags: bool     # range_mfma / topk_mfma are offered
+
+    def search_name(self, what: str) -> str:
+        return f"nns_search_{self.infix}_{what}"
+
+    def index_name(self, what: str) -> str:
+        return f"nns_index_{what}" + ("" if self.code == 0 else "_" + self.infix)   # (the fp32 ones carry no infix)
+
+
+_POINT_TYPES = {pt.code: pt for pt in (
+    _PointType(0, "f32", lambda a: _as_f32(a, "points"), 1, True, True),
+    _PointType(1, "bf16", _as_bf16_bits, 1, True, True),
+    _PointType(2, "f16", to_f16_bits, 1, True, False),
+    _PointType(3, "i8", to_i8, 1, False, False),
+    _PointType(4, "b1", to_b1, 8, False, False),
+    _PointType(5, "u8", to_u8, 1, False, True))}
+
+
 def _load() -> ctypes.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -125,11 +218,19 @@ def _load() -> ctypes.CDLL:
     c_int, c_vp, c_sz, c_u64, c_i64, c_u = (ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                              ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint)
     lib.nns_search_f32.argtypes = [c_int, c_int, c_int, c_vp, c_vp, ctypes.POINTER(ctypes.POINTER(c_int))]
-    lib.nns_search_f32_ex.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_u, c_int]
-    lib.nns_index_create.argtypes = [ctypes.POINTER(c_vp), c_int, c_int, c_int, c_vp, c_i64, c_u, c_vp]
-    lib.nns_index_create_bf16.argtypes = lib.nns_index_create.argtypes
-    lib.nns_index_search_bf16.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
-    lib.nns_search_bf16_ex.argtypes = lib.nns_search_f32_ex.argtypes
+    # the five per-dtype families: one signature each, whatever the element type
+    per_dtype = {}
+    for pt in _POINT_TYPES.values():
+        per_dtype[pt.index_name("create")] = [ctypes.POINTER(c_vp), c_int, c_int, c_int, c_vp, c_i64, c_u, c_vp]
+        per_dtype[pt.index_name("search")] = [c_vp, c_int, c_vp, c_vp, c_vp]
+        per_dtype[pt.search_name("ex")] = [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_u, c_int]
+        per_dtype[pt.search_name("topk")] = [c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_u, c_int]
+        per_dtype[pt.search_name("range")] = [c_int, c_int, c_int, c_vp, c_vp, ctypes.c_float, c_vp,
+                                              ctypes.POINTER(ctypes.POINTER(c_int)),
+                                              ctypes.POINTER(ctypes.POINTER(ctypes.c_float)), c_u, c_int]
+    for name, argtypes in per_dtype.items():
+        if name not in OPTIONAL_SYMBOLS:
+            getattr(lib, name).argtypes = argtypes
     lib.nns_search_f32_multi.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_u]
     lib.nns_search_bf16_multi.argtypes = lib.nns_search_f32_multi.argtypes
     lib.nns_comm_unique_id.argtypes = [c_vp, c_sz]
@@ -141,7 +242,6 @@ def _load() -> ctypes.CDLL:
     lib.nns_multi_last_exchange_ranks.argtypes = []
     lib.nns_index_destroy.argtypes = [c_vp]
     lib.nns_index_refresh.argtypes = [c_vp, c_vp]
-    lib.nns_index_search.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
     lib.nns_index_stats.argtypes = [c_vp, ctypes.POINTER(nns_stats)]
     lib.nns_index_search_indices.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.nns_index_near_ties.argtypes = [c_vp, c_vp, c_int, ctypes.POINTER(c_int)]
@@ -159,15 +259,9 @@ def _load() -> ctypes.CDLL:
     lib.nns_index_search_topk.argtypes = [c_vp, c_int, c_vp, c_int, c_vp, c_vp]
     lib.nns_keys_topk_merge.argtypes = [c_vp, c_vp, c_int, c_int, c_vp]
     lib.nns_keys_topk_unpack.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp]
-    lib.nns_search_f32_topk.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_u, c_int]
-    lib.nns_search_bf16_topk.argtypes = lib.nns_search_f32_topk.argtypes
     lib.nns_plan_topk.argtypes = [c_int, c_int, c_int, c_int, c_int, c_vp, c_int]
     lib.nns_index_range_count.argtypes = [c_vp, c_int, c_vp, ctypes.c_float, c_vp, c_vp]
     lib.nns_index_range_fill.argtypes = [c_vp, c_int, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp]
-    lib.nns_search_f32_range.argtypes = [c_int, c_int, c_int, c_vp, c_vp, ctypes.c_float, c_vp,
-                                         ctypes.POINTER(ctypes.POINTER(c_int)),
-                                         ctypes.POINTER(ctypes.POINTER(ctypes.c_float)), c_u, c_int]
-    lib.nns_search_bf16_range.argtypes = lib.nns_search_f32_range.argtypes
     lib.nns_plan_range.argtypes = [c_int, c_int, c_int, c_int, c_vp, c_int]
     lib.nns_index_range_info.argtypes = [c_vp, c_vp, c_int]
     lib.nns_plan_range_mfma.argtypes = [c_int, c_int, c_int, c_u, c_vp, c_int]
@@ -184,32 +278,13 @@ def _load() -> ctypes.CDLL:
                 "nns_plan_range_mfma_bf16": lib.nns_plan_range_mfma.argtypes,
                 "nns_plan_topk_mfma_bf16": lib.nns_plan_topk_mfma.argtypes,
                 "nns_range_threshold_bf16": lib.nns_range_threshold.argtypes,
-                "nns_index_create_f16": lib.nns_index_create.argtypes,
-                "nns_index_search_f16": lib.nns_index_search.argtypes,
-                "nns_search_f16_ex": lib.nns_search_f32_ex.argtypes,
-                "nns_search_f16_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_f16_range": lib.nns_search_f32_range.argtypes,
-                "nns_index_create_i8": lib.nns_index_create.argtypes,
-                "nns_index_search_i8": lib.nns_index_search.argtypes,
-                "nns_search_i8_ex": lib.nns_search_f32_ex.argtypes,
-                "nns_search_i8_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_i8_range": lib.nns_search_f32_range.argtypes,
-                "nns_index_create_b1": lib.nns_index_create.argtypes,
-                "nns_index_search_b1": lib.nns_index_search.argtypes,
-                "nns_search_b1_ex": lib.nns_search_f32_ex.argtypes,
-                "nns_search_b1_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_b1_range": lib.nns_search_f32_range.argtypes,
                 "nns_index_filter_pre": [c_vp, ctypes.POINTER(c_int)],
                 "nns_i8pre_bound": [ctypes.c_float] * 6 + [c_vp],
                 "nns_selftest_mfma_i8pre": [c_vp, c_vp, c_vp, c_vp],
-                "nns_index_create_u8": lib.nns_index_create.argtypes,
-                "nns_index_search_u8": lib.nns_index_search.argtypes,
-                "nns_search_u8_ex": lib.nns_search_f32_ex.argtypes,
-                "nns_search_u8_topk": lib.nns_search_f32_topk.argtypes,
-                "nns_search_u8_range": lib.nns_search_f32_range.argtypes,
                 "nns_plan_range_mfma_u8": lib.nns_plan_range_mfma.argtypes,
                 "nns_plan_topk_mfma_u8": lib.nns_plan_topk_mfma.argtypes,
                 "nns_range_threshold_u8": [ctypes.c_float, ctypes.c_float, c_vp]}
+    optional.update({name: argtypes for name, argtypes in per_dtype.items() if name in OPTIONAL_SYMBOLS})
     assert set(optional) == set(OPTIONAL_SYMBOLS)
     absent = tuple(n for n in OPTIONAL_SYMBOLS if not hasattr(lib, n))
     for name, argtypes in optional.items():
@@ -346,18 +421,18 @@ def plan_range(k: int, m: int, n: int, bf16: bool = False) -> dict:
     return dict(zip(names, (int(v) for v in out)))
 
 
+# the flag-pass plans of the point types that have one (any other code: the bf16 plan)
+_FLAG_PLAN_SUFFIX = {0: "", 1: "_bf16", 5: "_u8"}
+
+
 def plan_range_mfma(k: int, m: int, n: int, flags: int = 0, *, bf16: bool = False) -> dict:
     """nns_plan_range_mfma: the launch geometry of the MFMA-filtered range search (K7m) for a shape (host only);
     flags: the index's (NNS_FILTER_SPLIT_EAGER selects the eager ref image layout).  bf16: the plan for bf16 points
     (nns_plan_range_mfma_bf16; layout 2 = the order-1 16x16x32 image); bf16=5: the plan for uint8 points
     (nns_plan_range_mfma_u8; kt = 256, layout 3 = the int8 image)."""
     out = np.zeros(10, np.int32)
-    if bf16 == 5:
-        _check(lib.nns_plan_range_mfma_u8(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma_u8")
-    elif bf16:
-        _check(lib.nns_plan_range_mfma_bf16(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma_bf16")
-    else:
-        _check(lib.nns_plan_range_mfma(k, m, n, flags, out.ctypes.data, 10), "nns_plan_range_mfma")
+    name = "nns_plan_range_mfma" + _FLAG_PLAN_SUFFIX.get(int(bf16), "_bf16")
+    _check(getattr(lib, name)(k, m, n, flags, out.ctypes.data, 10), name)
     names = ("kt", "block_refs", "blocks_per_query", "batch", "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes",
              "layout")
     return dict(zip(names, (int(v) for v in out)))
@@ -369,12 +444,8 @@ def plan_topk_mfma(k: int, m: int, n: int, kn: int, flags: int = 0, *, bf16: boo
     query and flag words per chunk (zeros otherwise), and the LDS bytes of a selection workgroup.  bf16: the plan for
     bf16 points (nns_plan_topk_mfma_bf16); bf16=5: for uint8 points (nns_plan_topk_mfma_u8)."""
     out = np.zeros(17, np.int32)
-    if bf16 == 5:
-        _check(lib.nns_plan_topk_mfma_u8(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma_u8")
-    elif bf16:
-        _check(lib.nns_plan_topk_mfma_bf16(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma_bf16")
-    else:
-        _check(lib.nns_plan_topk_mfma(k, m, n, kn, flags, out.ctypes.data, 17), "nns_plan_topk_mfma")
+    name = "nns_plan_topk_mfma" + _FLAG_PLAN_SUFFIX.get(int(bf16), "_bf16")
+    _check(getattr(lib, name)(k, m, n, kn, flags, out.ctypes.data, 17), name)
     names = ("sample_blocks", "stride", "sample_refs", "filtered", "kt", "block_refs", "blocks_per_query", "batch",
              "batches", "flag_ws_bytes", "grid_x", "grid_y", "lds_bytes", "layout", "chunks", "chunk_words",
              "select_lds_bytes")
@@ -419,13 +490,6 @@ def device_count() -> int:
     return lib.nns_device_count()
 
 
-def _as_f32(a, what: str) -> np.ndarray:
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    if a.ndim != 2:
-        raise ValueError(f"{what} must be [points][k]")
-    return a
-
-
 def cudaCall(k: int, m: int, n: int, s_points, r_points) -> np.ndarray:
     """Drop-in for the reference's ``vN::cudaCall(k, m, n, s_points, r_points, &results)``.
 
@@ -444,6 +508,25 @@ def cudaCall(k: int, m: int, n: int, s_points, r_points) -> np.ndarray:
         _libc.free(res)
 
 
+def _search_1nn(code, query_points, reference_points, return_distances, shards, path, device, refs_soa=False, flags=0):
+    """The whole-call nearest-neighbour search of point type `code` (nns_search_<infix>_ex)."""
+    pt = _POINT_TYPES[code]
+    assert pt.refs_soa or not refs_soa
+    q = pt.convert(query_points)
+    r = pt.convert(reference_points)
+    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
+        raise ValueError("query and reference dimensionality differ")
+    m, cols = q.shape
+    n = r.shape[1] if refs_soa else r.shape[0]
+    idx = np.empty(m, dtype=np.int32)
+    dist = np.empty(m, dtype=np.float32) if return_distances else None
+    name = pt.search_name("ex")
+    _check(getattr(lib, name)(cols * pt.k_mult, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
+                              dist.ctypes.data if dist is not None else None, shards,
+                              _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | flags, device), name)
+    return (idx, dist) if return_distances else idx
+
+
 def search(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
            path: str = "auto", device: int = 0, refs_soa: bool = False, filter_bf16: bool = False):
     """``search(query_points, reference_points)`` — the entry point BASELINE.json names.
@@ -454,17 +537,7 @@ def search(query_points, reference_points, *, return_distances: bool = False, sh
     reference_points is dimension-major [k][n] (NNS_REFS_SOA, the reference's V4 layout)."""
     q = _as_f32(query_points, "query_points")
     r = _as_f32(reference_points, "reference_points")
-    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
-        raise ValueError("query and reference dimensionality differ")
-    m, k = q.shape
-    n = r.shape[1] if refs_soa else r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_f32_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                 dist.ctypes.data if dist is not None else None, shards,
-                                 _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0)
-                                 | (NNS_FILTER_BF16 if filter_bf16 else 0), device), "nns_search_f32_ex")
-    return (idx, dist) if return_distances else idx
+    return _search_1nn(0, q, r, return_distances, shards, path, device, refs_soa, NNS_FILTER_BF16 if filter_bf16 else 0)
 
 
 def search_multi(query_points, reference_points, *, num_devices: int = 0, return_distances: bool = False,
@@ -477,10 +550,8 @@ def search_multi(query_points, reference_points, *, num_devices: int = 0, return
     (tests): no single-GPU shortcut, so that ncclCommInitAll + the grouped all-reduce also run with one
     shard on a one-GPU box (NNS_MULTI_FORCE_COLLECTIVE)."""
     if bf16:
-        q = np.ascontiguousarray(query_points, dtype=np.uint16)
-        r = np.ascontiguousarray(reference_points, dtype=np.uint16)
-        if q.ndim != 2 or r.ndim != 2:
-            raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
+        q = _as_bf16_bits(query_points)
+        r = _as_bf16_bits(reference_points)
     else:
         q = _as_f32(query_points, "query_points")
         r = _as_f32(reference_points, "reference_points")
@@ -517,105 +588,28 @@ def search_bf16(query_bits, reference_bits, *, return_distances: bool = False, s
     r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
     if q.ndim != 2 or r.ndim != 2 or q.shape[1] != r.shape[1]:
         raise ValueError("bf16 point sets must be [points][k] with equal k")
-    m, k = q.shape
-    n = r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_bf16_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                  dist.ctypes.data if dist is not None else None, shards,
-                                  _PATHS[path], device), "nns_search_bf16_ex")
-    return (idx, dist) if return_distances else idx
-
-
-def to_f16_bits(a) -> np.ndarray:
-    """A numpy float16 array, or uint16 bit patterns, as contiguous 2-D uint16 binary16 bit patterns (no conversion of
-    values: other dtypes are refused, so that nothing is rounded silently)."""
-    a = np.asarray(a)
-    if a.dtype == np.float16:
-        a = np.ascontiguousarray(a).view(np.uint16)
-    elif a.dtype != np.uint16:
-        raise ValueError("fp16 point sets must be numpy float16 arrays or uint16 bit patterns")
-    a = np.ascontiguousarray(a)
-    if a.ndim != 2:
-        raise ValueError("fp16 point sets must be 2-D arrays")
-    return a
+    return _search_1nn(1, q, r, return_distances, shards, path, device)
 
 
 def search_f16(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
                path: str = "auto", device: int = 0, refs_soa: bool = False):
     """search() for fp16 point sets (numpy float16, or uint16 binary16 bit patterns) [points][k]: V0's arithmetic on the
     values widened exactly to fp32 (nns_search_f16_ex).  refs_soa: reference_points is dimension-major [k][n]."""
-    q = to_f16_bits(query_points)
-    r = to_f16_bits(reference_points)
-    if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
-        raise ValueError("query and reference dimensionality differ")
-    m, k = q.shape
-    n = r.shape[1] if refs_soa else r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_f16_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                 dist.ctypes.data if dist is not None else None, shards,
-                                 _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0), device), "nns_search_f16_ex")
-    return (idx, dist) if return_distances else idx
-
-
-def to_i8(a) -> np.ndarray:
-    """A numpy int8 array as a contiguous 2-D int8 array (other dtypes are refused: nothing is quantised silently)."""
-    a = np.asarray(a)
-    if a.dtype != np.int8:
-        raise ValueError("int8 point sets must be numpy int8 arrays")
-    a = np.ascontiguousarray(a)
-    if a.ndim != 2:
-        raise ValueError("int8 point sets must be 2-D arrays")
-    return a
+    return _search_1nn(2, query_points, reference_points, return_distances, shards, path, device, refs_soa)
 
 
 def search_i8(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
               path: str = "auto", device: int = 0):
     """search() for int8 point sets (numpy int8) [points][k]: V0's arithmetic on the values widened exactly to fp32
     (nns_search_i8_ex).  For k <= 256 the distances are the exact integer squared distances."""
-    q = to_i8(query_points)
-    r = to_i8(reference_points)
-    if q.shape[1] != r.shape[1]:
-        raise ValueError("query and reference dimensionality differ")
-    m, k = q.shape
-    n = r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_i8_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
-           "nns_search_i8_ex")
-    return (idx, dist) if return_distances else idx
-
-
-def to_u8(a) -> np.ndarray:
-    """A numpy uint8 array as a contiguous 2-D uint8 array of point values 0 .. 255 (other dtypes are refused: nothing is
-    quantised silently)."""
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise ValueError("uint8 point sets must be numpy uint8 arrays")
-    a = np.ascontiguousarray(a)
-    if a.ndim != 2:
-        raise ValueError("uint8 point sets must be 2-D arrays")
-    return a
+    return _search_1nn(3, query_points, reference_points, return_distances, shards, path, device)
 
 
 def search_u8(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
               path: str = "auto", device: int = 0):
     """search() for uint8 point sets (numpy uint8, values 0 .. 255) [points][k]: V0's arithmetic on the values widened
     exactly to fp32 (nns_search_u8_ex).  For k <= 256 the distances are the exact integer squared distances."""
-    q = to_u8(query_points)
-    r = to_u8(reference_points)
-    if q.shape[1] != r.shape[1]:
-        raise ValueError("query and reference dimensionality differ")
-    m, k = q.shape
-    n = r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_u8_ex(k, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
-           "nns_search_u8_ex")
-    return (idx, dist) if return_distances else idx
+    return _search_1nn(5, query_points, reference_points, return_distances, shards, path, device)
 
 
 def pack_bits(a) -> np.ndarray:
@@ -635,51 +629,24 @@ def pack_bits(a) -> np.ndarray:
     return out
 
 
-def to_b1(a) -> np.ndarray:
-    """Packed binary points, numpy uint8 [.][kb] with kb % 4 == 0 or uint32 [.][kw], as a contiguous uint8 [.][4 * kw]
-    array (anything else, a buffer that is not 4-byte aligned included, is refused)."""
-    a = np.asarray(a)
-    if a.ndim != 2 or a.dtype not in (np.uint8, np.uint32):
-        raise ValueError("binary point sets must be 2-D numpy uint8 or uint32 arrays of packed bits (see pack_bits)")
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.uint8)
-    if a.shape[1] % 4 != 0:
-        raise ValueError("binary point sets hold whole 32-bit words: the byte count per point must be a multiple of 4")
-    if a.ctypes.data % 4 != 0:   # (a view into a byte buffer: the library reads words)
-        raise ValueError("binary point sets must be 4-byte aligned")
-    return a
-
-
 def search_b1(query_points, reference_points, *, return_distances: bool = False, shards: int = 1,
               path: str = "auto", device: int = 0):
     """search() for packed binary points (see to_b1 / pack_bits) under Hamming distance (nns_search_b1_ex): the distances
     are the Hamming distances as fp32, V0's arithmetic on the bits widened to 0.0 / 1.0."""
-    q = to_b1(query_points)
-    r = to_b1(reference_points)
-    if q.shape[1] != r.shape[1]:
-        raise ValueError("query and reference dimensionality differ")
-    m, kb = q.shape
-    n = r.shape[0]
-    idx = np.empty(m, dtype=np.int32)
-    dist = np.empty(m, dtype=np.float32) if return_distances else None
-    _check(lib.nns_search_b1_ex(8 * kb, m, n, q.ctypes.data, r.ctypes.data, idx.ctypes.data,
-                                dist.ctypes.data if dist is not None else None, shards, _PATHS[path], device),
-           "nns_search_b1_ex")
-    return (idx, dist) if return_distances else idx
+    return _search_1nn(4, query_points, reference_points, return_distances, shards, path, device)
 
 
 def _search_topk(q, r, kn, bf16, return_distances, shards, path, device, refs_soa, topk_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
+    pt = _POINT_TYPES[int(bf16)]
+    assert (pt.refs_soa or not refs_soa) and (pt.mfma_flags or not topk_mfma)
     m, k = q.shape
-    if bf16 == 4:
-        k *= 8   # (packed binary points: uint8 columns, k in bits)
+    k *= pt.k_mult   # (packed binary points: uint8 columns, k in bits)
     n = r.shape[1] if refs_soa else r.shape[0]
     idx = np.empty((m, max(kn, 0)), dtype=np.int32)
     dist = np.empty((m, max(kn, 0)), dtype=np.float32) if return_distances else None
-    fn = lib.nns_search_u8_topk if bf16 == 5 else lib.nns_search_b1_topk if bf16 == 4 else lib.nns_search_i8_topk if bf16 == 3 else lib.nns_search_f16_topk if bf16 == 2 \
-        else lib.nns_search_bf16_topk if bf16 else lib.nns_search_f32_topk
+    fn = getattr(lib, pt.search_name("topk"))
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, kn, idx.ctypes.data, dist.ctypes.data if dist is not None else None,
               shards, _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_TOPK_MFMA if topk_mfma else 0), device),
            "nns_search_topk")
@@ -701,11 +668,7 @@ def search_topk_bf16(query_bits, reference_bits, kn: int, *, return_distances: b
                      path: str = "auto", device: int = 0, refs_soa: bool = False, topk_mfma: bool = False):
     """search_topk() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_topk).  topk_mfma: NNS_TOPK_MFMA
     (32 <= k <= 256 for bf16 points)."""
-    q = np.ascontiguousarray(query_bits, dtype=np.uint16)
-    r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
-    if q.ndim != 2 or r.ndim != 2:
-        raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
-    return _search_topk(q, r, kn, True, return_distances, shards, path, device, refs_soa, topk_mfma)
+    return _search_topk(_as_bf16_bits(query_bits), _as_bf16_bits(reference_bits), kn, True, return_distances, shards, path, device, refs_soa, topk_mfma)
 
 
 def search_topk_f16(query_points, reference_points, kn: int, *, return_distances: bool = False, shards: int = 1,
@@ -737,15 +700,15 @@ def search_topk_b1(query_points, reference_points, kn: int, *, return_distances:
 def _search_range(q, r, radius2, bf16, return_distances, path, device, refs_soa, range_mfma=False):
     if q.shape[1] != (r.shape[0] if refs_soa else r.shape[1]):
         raise ValueError("query and reference dimensionality differ")
+    pt = _POINT_TYPES[int(bf16)]
+    assert (pt.refs_soa or not refs_soa) and (pt.mfma_flags or not range_mfma)
     m, k = q.shape
-    if bf16 == 4:
-        k *= 8   # (packed binary points: uint8 columns, k in bits)
+    k *= pt.k_mult   # (packed binary points: uint8 columns, k in bits)
     n = r.shape[1] if refs_soa else r.shape[0]
     lims = np.zeros(max(m, 0) + 1, dtype=np.int64)
     pidx = ctypes.POINTER(ctypes.c_int)()
     pdist = ctypes.POINTER(ctypes.c_float)()
-    fn = lib.nns_search_u8_range if bf16 == 5 else lib.nns_search_b1_range if bf16 == 4 else lib.nns_search_i8_range if bf16 == 3 else lib.nns_search_f16_range if bf16 == 2 \
-        else lib.nns_search_bf16_range if bf16 else lib.nns_search_f32_range
+    fn = getattr(lib, pt.search_name("range"))
     _check(fn(k, m, n, q.ctypes.data, r.ctypes.data, float(radius2), lims.ctypes.data, ctypes.byref(pidx),
               ctypes.byref(pdist) if return_distances else None,
               _PATHS[path] | (NNS_REFS_SOA if refs_soa else 0) | (NNS_RANGE_MFMA if range_mfma else 0),
@@ -778,11 +741,7 @@ def search_range_bf16(query_bits, reference_bits, radius2: float, *, return_dist
                       path: str = "auto", device: int = 0, refs_soa: bool = False, range_mfma: bool = False):
     """search_range() for bf16 point sets given as uint16 bit patterns (nns_search_bf16_range).  range_mfma:
     NNS_RANGE_MFMA (32 <= k <= 256 for bf16 points)."""
-    q = np.ascontiguousarray(query_bits, dtype=np.uint16)
-    r = np.ascontiguousarray(reference_bits, dtype=np.uint16)
-    if q.ndim != 2 or r.ndim != 2:
-        raise ValueError("bf16 point sets must be 2-D arrays of bit patterns")
-    return _search_range(q, r, radius2, True, return_distances, path, device, refs_soa, range_mfma)
+    return _search_range(_as_bf16_bits(query_bits), _as_bf16_bits(reference_bits), radius2, True, return_distances, path, device, refs_soa, range_mfma)
 
 
 def search_range_f16(query_points, reference_points, radius2: float, *, return_distances: bool = False,
@@ -850,22 +809,20 @@ class Index:
         if refs.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.int8, torch.uint8) or refs.dim() != 2 \
                 or not refs.is_contiguous() or not refs.is_cuda:
             raise ValueError("refs must be a contiguous fp32, bf16, fp16, int8 or uint8 (packed bits) [n][k] tensor on a HIP device")
-        self.bf16 = refs.dtype == torch.bfloat16
-        self.f16 = refs.dtype == torch.float16
-        self.i8 = refs.dtype == torch.int8
         if points not in (None, "u8"):
             raise ValueError('points must be None (inferred from the dtype) or "u8"')
         if points == "u8" and refs.dtype != torch.uint8:
             raise ValueError('points="u8" takes a torch.uint8 tensor')
-        self.u8 = points == "u8"
-        self.b1 = refs.dtype == torch.uint8 and not self.u8
+        code = 5 if points == "u8" else {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.int8: 3,
+                                         torch.uint8: 4}[refs.dtype]
+        self._pt = _POINT_TYPES[code]
+        self.bf16, self.f16, self.i8, self.b1, self.u8 = (code == c for c in (1, 2, 3, 4, 5))
         if self.b1 and (refs.shape[1] % 4 != 0 or refs.data_ptr() % 4 != 0):
             raise ValueError("packed binary refs hold whole 32-bit words: kb % 4 == 0 and a 4-byte aligned data_ptr()")
         self.refs = refs  # keep alive: the index reads the original values
         self.n, self.k = (refs.shape[1], refs.shape[0]) if soa else refs.shape
         self.cols = self.k   # columns of a query tensor
-        if self.b1:
-            self.k *= 8      # bits
+        self.k *= self._pt.k_mult   # (packed binary points: bits)
         self.device = refs.device.index or 0
         flags = _PATHS[path] | (NNS_PROFILE if profile else 0) | (NNS_REFS_SOA if soa else 0) \
             | (NNS_FILTER_BF16 if filter_bf16 else 0) | (NNS_FILTER_F32 if filter_f32 else 0) \
@@ -873,8 +830,7 @@ class Index:
             | (NNS_TOPK_MFMA if topk_mfma else 0) | _I8PRE[filter_i8pre]
         self.flags = flags
         h = ctypes.c_void_p()
-        create = lib.nns_index_create_u8 if self.u8 else lib.nns_index_create_b1 if self.b1 else lib.nns_index_create_i8 if self.i8 else lib.nns_index_create_f16 if self.f16 \
-            else lib.nns_index_create_bf16 if self.bf16 else lib.nns_index_create
+        create = getattr(lib, self._pt.index_name("create"))
         _check(create(ctypes.byref(h), self.device, self.k, self.n, refs.data_ptr(),
                       index_base, flags, _stream_ptr(stream)), "nns_index_create")
         self._h = h
@@ -899,8 +855,7 @@ class Index:
         m = queries.shape[0]
         if keys is None:
             keys = torch.empty(m, dtype=torch.int64, device=queries.device)
-        fn = lib.nns_index_search_u8 if self.u8 else lib.nns_index_search_b1 if self.b1 else lib.nns_index_search_i8 if self.i8 else lib.nns_index_search_f16 if self.f16 \
-            else lib.nns_index_search_bf16 if self.bf16 else lib.nns_index_search
+        fn = getattr(lib, self._pt.index_name("search"))
         _check(fn(self._h, m, queries.data_ptr(), keys.data_ptr(), _stream_ptr(stream)), "nns_index_search")
         return keys
 
