@@ -517,27 +517,25 @@ __device__ __forceinline__ void filter_main(const FilterArgs &a)
 {
     constexpr int F_NW = OP::kNW;
     constexpr int SPB = OP::kSPB;                      // fragment steps per image block
-    // Blocks and ring slots: a slot is always 32 fragment steps.  Up to 32 steps per block a slot holds BPS whole
-    // blocks; deeper blocks straddle slots with a SUPER-PERIOD of SUP_SLOTS slots = SUP_BLKS blocks — 64 steps
-    // (1024-deep): 2 slots = 1 block; 48 steps (768-deep): 3 slots = 2 blocks, the second one starting in the middle
-    // of the second slot.  Accumulators carry across the slot barriers; every slot of a super-period brings the
-    // norms of all its blocks.  In general lcm(SPB, 32) steps: 40 steps (640-deep) = 5 slots = 4 blocks.
-    constexpr int SUP_GCD = SPB % 32 == 0 ? 32 : (SPB % 16 == 0 ? 16 : (SPB % 8 == 0 ? 8 : 1));
-    // (24 steps, 384-deep: 3 slots = 4 blocks.)  "Deep" = the block does not divide the slot.
+    // Blocks and ring slots (ring_geom, nns_internal.h): up to a slot's steps per block a slot holds BPS whole blocks;
+    // deeper blocks straddle slots with a SUPER-PERIOD of SUP_SLOTS slots = SUP_BLKS blocks, e.g. 48 steps (768-deep):
+    // 3 slots = 2 blocks, the second one starting in the middle of the second slot.  Accumulators carry across the slot
+    // barriers; every slot of a super-period brings the norms of all its blocks.
     // The lazy split operator streams hi fragments only: its slots are SPS = 16 steps in a ring of 8 (see OpLazySplitT);
     // everywhere else SPS = 32, F_D = 4.
     constexpr bool LAZY = OP::kLazy;
     constexpr int SPS = OP::kSlotSteps;
     static_assert(F_LDS_BYTES<OP> == 4 * (32768 + 2048) || (OP::kPre && F_LDS_BYTES<OP> <= 4 * (32768 + 2048)),
                   "every operator's ring takes the same LDS: one workgroup per CU");
-    constexpr bool DEEP = SPS % SPB != 0;
+    constexpr RingGeom RG = ring_geom(SPB, SPS);
+    constexpr bool DEEP = RG.deep;
     static_assert(SPS == 32 || !DEEP, "blocks straddling slots: 32-step slots only");
-    constexpr int SUP_SLOTS = DEEP ? SPB / SUP_GCD : 1;
-    constexpr int SUP_BLKS = DEEP ? 32 / SUP_GCD : SPS / SPB;
+    constexpr int SUP_SLOTS = RG.slots;
+    constexpr int SUP_BLKS = RG.blocks;
     constexpr int SPBLK = SUP_SLOTS;                   // (name kept: slots of a deep block's super-period)
     constexpr int BPS = DEEP ? 1 : SPS / SPB;          // image blocks per ring slot (shallow tiles)
     constexpr int BLK_BYTES = SPB * 1024;
-    constexpr int SLOT_REFS = 32 * SUP_BLKS;           // norms DMAed with a slot
+    constexpr int SLOT_REFS = RG.slot_refs;          // norms DMAed with a slot
     constexpr int F_PPW = F_SLOT_COORD<OP> / 1024 / F_NW;   // 1 KiB DMA pieces per wave per slot
     static_assert((SPS % SPB == 0 && SPB >= 2) || SPB == 64 || SPB == 48 || SPB == 40 || SPB == 24, "a slot is SPS fragment steps");
     static_assert(SUP_SLOTS * SPS == SUP_BLKS * SPB, "a super-period is whole slots and whole blocks");
@@ -2017,31 +2015,38 @@ int filter_lazy_tile()
     return LazyOp128::kTile16 ? 16 : 32;
 }
 
-// The one depth-to-operator table: f(OP{}) for the operator that runs geometry g — (bf16, split, lazy, kt).  The kt
-// ladder of filter_plan produces exactly the depths listed here.
+// The one (form, depth)-to-operator table: f(OP{}) for the operator that runs geometry g.  The depths listed here are
+// the forms' ladders (kFilterForms).  (The cases stand in the order the operators' kernels are laid out in the code object.)
 template <class F>
 static int with_filter_op(const FilterGeom &g, F &&f)
 {
-    if (g.i8) {
+    switch (g.form) {
+    case FORM_I8:
         if (g.kt == 256) return f(OpI8{});
-    } else if (g.f16) {
+        break;
+    case FORM_F16:
         switch (g.kt) {
         case 128: return f(OpF16K128{});
         case 256: return f(OpF16{});
         }
-    } else if (g.bf16) {
+        break;
+    case FORM_BF16:
+    case FORM_MIXED:
         switch (g.kt) {
-        case 128: return f(OpBF16K128{});
+        case 128: return f(OpBF16K128{});   // 4 k-steps per 16-ref tile, 4 blocks per slot
         case 256: return f(OpBF16{});
-        case 384: return f(OpBF16K384{});
+        case 384: return f(OpBF16K384{});   // four 24-step blocks over three ring slots
         case 512: return f(OpBF16K512T{});
-        case 640: return f(OpBF16K640{});
-        case 768: return f(OpBF16K768{});
-        case 1024: return f(OpBF16K1024{});
+        case 640: return f(OpBF16K640{});   // four 40-step blocks over five ring slots
+        case 768: return f(OpBF16K768{});   // two 48-step blocks over three ring slots
+        case 1024: return f(OpBF16K1024{}); // K-split accumulation over two ring slots per block
         }
-    } else if (g.lazy) {
-        if (g.kt == 128) return f(LazyOp128{});
-    } else if (g.split) {
+        break;
+    case FORM_SPLIT:
+        if (g.lazy) {
+            if (g.kt == 128) return f(LazyOp128{});
+            break;
+        }
         switch (g.kt) {
         case 16: return f(OpSplitK16{});
         case 32: return f(OpSplitK32{});
@@ -2049,65 +2054,41 @@ static int with_filter_op(const FilterGeom &g, F &&f)
         case 128: return f(OpSplit{});
         case 256: return f(OpSplitK256{});
         }
-    } else {
+        break;
+    case FORM_F32:
         switch (g.kt) {
-        case 16: return f(OpF32K16{});
-        case 32: return f(OpF32K32{});
-        case 64: return f(OpF32K64{});
+        case 16: return f(OpF32K16{});      // 2 fragment steps per block, 16 blocks per slot
+        case 32: return f(OpF32K32{});      // 4 fragment steps per block, 8 blocks per slot
+        case 64: return f(OpF32K64{});      // 8 steps per block, 4 blocks per slot
         case 128: return f(OpF32{});
-        case 256: return f(OpF32K256{});
+        case 256: return f(OpF32K256{});    // 32 fragment steps per block, 1 block per slot
         }
+        break;
     }
-    set_error("MFMA filter: no operator for kt = %d (bf16 %d, split %d, lazy %d)", g.kt, g.bf16, g.split, g.lazy);
+    set_error("MFMA filter: no operator for kt = %d (bf16 %d, split %d, lazy %d)", g.kt,
+              (unsigned)g.form < FORM_COUNT ? kFilterForms[g.form].bf16 : 0, g.form == FORM_SPLIT, g.lazy);
     return NNS_ERR_UNSUPPORTED;
 }
 
 int filter_plan(const FilterRequest &rq, FilterGeom *g)
 {
     const int k = rq.k, m = rq.m, n = rq.n;
-    const bool mixed = rq.mixed, per_ref = rq.per_ref, split = rq.split, split_eager = rq.split_eager;
-    const bool f16 = rq.dtype == DT_F16, i8 = point_type(rq.dtype).i8_image, u8 = rq.dtype == DT_U8;
-    const bool bf16 = dt_bf16_like(rq.dtype) || mixed;   // (mixed: fp32 points, bf16 operands: the bf16 filter's geometry)
+    const bool per_ref = rq.per_ref, split_eager = rq.split_eager;
+    const int form = (unsigned)rq.form < FORM_COUNT ? rq.form : FORM_BF16;   // (FORM_NONE: no caller plans a type without a filter)
+    const FilterForm &ff = kFilterForms[form];
     int kt = 0;
-    if (i8) {                          // int8 points: the one 16x16x64 depth (k <= 128 pads to it too)
-        if (k <= 256) kt = 256;
-        if (!kt) {
-            set_error("MFMA filter: k = %d exceeds the deepest tile of int8 points (256)", k);
-            return NNS_ERR_UNSUPPORTED;
-        }
-    } else if (f16) {                         // fp16 points: the two 16x16x32 depths (deeper tiles: not built)
-        if (k <= 128) kt = 128;
-        else if (k <= 256) kt = 256;
-        if (!kt) {
-            set_error("MFMA filter: k = %d exceeds the deepest tile of fp16 points (256)", k);
-            return NNS_ERR_UNSUPPORTED;
-        }
-    } else if (bf16) {
-        if (k <= 128) kt = 128;        // OpBF16K128: 4 k-steps per 16-ref tile, 4 blocks per slot
-        else if (k <= 256) kt = 256;
-        else if (k <= 384) kt = 384;   // OpBF16K384: four 24-step blocks over three ring slots
-        else if (k <= 512) kt = 512;   // OpBF16K512T
-        else if (k <= 640) kt = 640;   // OpBF16K640: four 40-step blocks over five ring slots
-        else if (k <= 768) kt = 768;   // OpBF16K768: two 48-step blocks over three ring slots
-        else if (k <= 1024) kt = 1024; // OpBF16K1024: K-split accumulation over two ring slots per block
-    } else {
-        if (k <= 16) kt = 16;          // OpF32K16: 2 fragment steps per block, 16 blocks per slot
-        else if (k <= 32) kt = 32;     // OpF32K32: 4 fragment steps per block, 8 blocks per slot
-        else if (k <= 64) kt = 64;     // OpF32K64: 8 steps per block, 4 blocks per slot
-        else if (k <= 128) kt = 128;
-        else if (k <= 256) kt = 256;   // OpF32K256: 32 fragment steps per block, 1 block per slot
-    }
+    for (int i = 0; i < 8 && ff.ladder[i] && !kt; ++i)
+        if (k <= ff.ladder[i]) kt = ff.ladder[i];
     if (!kt) {
-        set_error("MFMA filter: k = %d exceeds the deepest tile (fp32 operands: 256, bf16 operands: 1024)", k);
+        if (form == FORM_F16 || form == FORM_I8)   // (the two forms whose refusal names the points)
+            set_error("MFMA filter: k = %d exceeds the deepest tile of %s points (256)", k, ff.name);
+        else
+            set_error("MFMA filter: k = %d exceeds the deepest tile (fp32 operands: 256, bf16 operands: 1024)", k);
         return NNS_ERR_UNSUPPORTED;
     }
-    g->bf16 = bf16 ? 1 : 0;
-    g->f16 = f16 ? 1 : 0;
-    g->i8 = i8 ? 1 : 0;
-    g->u8 = (i8 && u8) ? 1 : 0;   // (uint8 points: int8's plan; K2 biases the image, K5 reads u8_t)
-    g->mixed = mixed ? 1 : 0;
+    g->dtype = (unsigned)rq.dtype < DT_COUNT ? rq.dtype : DT_BF16;   // (point_type's rule for a code the ABI does not define)
     // (the split form shares every geometry field below with the fp32 one: same blocks, slots and queries per wave)
-    g->split = (split && !bf16 && split_depth(kt)) ? 1 : 0;
+    g->form = form == FORM_SPLIT && !split_depth(kt) ? FORM_F32 : form;
     g->kt = kt;
     // (the schedule is chosen at the end, from the stream length that the query groups fix: the lazy operator has its
     //  eager twin's tiles and workgroup)
@@ -2132,17 +2113,11 @@ int filter_plan(const FilterRequest &rq, FilterGeom *g)
     }));
     const int qw = g->qw;
     g->m_pad = divup(m, qw) * qw;
-    // refs per ring slot (32 fragment steps of 8 fp32 / 16 bf16 dims)
-    const int steps_per_block = g->spb;
-    // deep blocks straddle slots: super-periods of `slots_per_block` slots = `pad_pts` refs (1024-deep: 2 slots = one
-    // block of 32; 768-deep: 3 slots = two blocks = 64 refs, i.e. 21.33 refs per slot — slot_pts, which only sizes
-    // paddings from here on, is rounded up)
-    // (640-deep: 5 slots = four blocks = 128 refs; 384-deep: 3 slots = four blocks = 128 refs)
-    const bool deep = 32 % steps_per_block != 0;
-    const int sup_gcd = steps_per_block % 32 == 0 ? 32 : (steps_per_block % 16 == 0 ? 16 : 8);
-    const int slots_per_block = deep ? steps_per_block / sup_gcd : 1;                         // slots of a super-period
-    const int pad_pts = deep ? 32 * (32 / sup_gcd) : 32 * (32 / steps_per_block);            // refs of a super-period: whole blocks
-    const int slot_pts = deep ? (pad_pts + slots_per_block - 1) / slots_per_block : pad_pts;
+    // the ring of 32-step slots (8 fp32 / 16 bf16 dims per step): the refs are padded to whole super-periods; slot_pts,
+    // which only sizes paddings from here on, is rounded up where a slot holds a fraction of a block (768-deep: 21.33 refs)
+    const RingGeom ring = ring_geom(g->spb);
+    const int slots_per_block = ring.slots, pad_pts = ring.slot_refs;
+    const int slot_pts = divup(pad_pts, slots_per_block);
     g->n_pad = divup(n, pad_pts) * pad_pts;
     g->total_slots = g->n_pad / pad_pts * slots_per_block;
     g->qgroups = g->m_pad / qw;
@@ -2160,7 +2135,7 @@ int filter_plan(const FilterRequest &rq, FilterGeom *g)
     // (fp32 points through bf16 operands: the rounding term makes tau ~2^-6 |x'||y'|, thousands of refs lie within it
     //  of the running minimum, and private thresholds fill the 64-entry rings — 5 504 of 65 536 queries overflowed into
     //  the exact scan at k = 1024 — so their lanes always share, whatever the stream length)
-    g->share_thr = (stream_tiles <= kShareThrMaxTiles || mixed) ? 1 : 0;
+    g->share_thr = (stream_tiles <= kShareThrMaxTiles || g->form == FORM_MIXED) ? 1 : 0;
     // record forms: 0 per score (long streams), 1 per (lane, ref tile) behind the threshold test (short streams, 16 x 16
     // bf16 tiles: their epilogue has no vector slots to spare), 2 the lane's two best tiles, branch-free (short streams,
     // 32 x 32 tiles: every fp32 depth and the 768- / 1024-deep bf16-operand tiles)
@@ -2168,7 +2143,7 @@ int filter_plan(const FilterRequest &rq, FilterGeom *g)
     // The lazy schedule: an index of a lazy depth keeps its image in the lazy layout whatever the query count (the
     // layout is fixed when the index is built); a search runs the lazy kernel where its records are per score, and the
     // eager kernel — reading the same image — on the short-stream record forms, where nearly every tile refines anyway.
-    g->lazy_img = (g->split && lazy_depth(kt) && !split_eager) ? 1 : 0;
+    g->lazy_img = (g->form == FORM_SPLIT && lazy_depth(kt) && !split_eager) ? 1 : 0;
     g->lazy = (g->lazy_img && g->tile_rec == 0) ? 1 : 0;
     return NNS_OK;
 }

@@ -642,8 +642,7 @@ __global__ __launch_bounds__(256) void finalize_wave_kernel(
 template <class F>
 static int with_geom_type(const FilterGeom &g, F &&f)
 {
-    const int dtype = g.u8 ? DT_U8 : g.i8 ? DT_I8 : g.f16 ? DT_F16 : (g.bf16 && !g.mixed) ? DT_BF16 : DT_F32;
-    return with_point_type(dtype, [&](auto tag) {
+    return with_point_type(g.dtype, [&](auto tag) {
         if constexpr (std::is_same_v<typename decltype(tag)::type, b1_t>) return (int)NNS_ERR_INVALID;
         else return f(tag);
     });

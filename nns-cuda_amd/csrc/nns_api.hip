@@ -31,17 +31,6 @@ void set_error(const char *fmt, ...)
 
 using namespace nns;
 
-// one point of a tile image
-static size_t img_row_bytes(const FilterGeom &g) { return (size_t)g.kt * (g.i8 ? 1 : g.bf16 ? 2 : 4); }
-// The filter's ring DMA runs up to three slots (32 KiB of image, slot_pts norms each) past the last one without a
-// bounds branch: images and norm arrays carry that much padding (+ the over-read of a 128-norm piece)
-static size_t img_bytes(const FilterGeom &g, int pts_pad) { return (size_t)pts_pad * img_row_bytes(g) + 3 * 32768 + 4096; }
-static size_t norm_bytes(const FilterGeom &g, int pts_pad) { return ((size_t)pts_pad + 3 * g.slot_pts + 256) * sizeof(float); }
-// The int8 pre-pass's operands sit behind the image they go with, in the same allocation.  Refs: the int8 region (128
-// bytes per ref; its ring runs up to 16 slots of 8 KiB past the end) and one i32 seed per ref (+ 16 slots of 64).
-// Queries: the q8 image (128 bytes per query) and one bound per query.
-static size_t i8pre_ref_bytes(int n_pad) { return (size_t)n_pad * 128 + 16 * 8192 + ((size_t)n_pad + 16 * 64) * sizeof(int); }
-static size_t i8pre_query_bytes(int m_pad) { return (size_t)m_pad * (128 + sizeof(float)); }
 // below this many queries the AUTO path skips the MFMA filter (and, in the whole-call
 // entry points, its ref pre-pass too)
 static const int kTinyM = 64;
@@ -86,9 +75,7 @@ struct nns_index {
     int dtype = DT_F32;            // DT_B1: k counts 32-bit words
     bool profile = false;
     bool refs_bad = false;
-    bool mixed = false;            // NNS_FILTER_BF16: fp32 points, bf16 filter operands
-    bool split = false;            // fp32 points without NNS_FILTER_BF16 / NNS_FILTER_F32: split-bf16 operands where
-                                   // filter_plan enables them (geom.split)
+    int form = FORM_NONE;          // operand_form's answer: what filter_plan is asked for (geom.form: what it grants)
 
     bool i8pre = false;            // a 128-deep lazy 1-NN index that also keeps the int8 pre-pass's operands
 
@@ -212,13 +199,13 @@ int order_after_default_stream(hipStream_t st)
 }  // namespace nns
 }  // extern "C++"
 
-// The filter's operand form, the one rule for nns_index_create* and nns_plan_filter: *mixed = fp32 points through
-// bf16-rounded operands (NNS_FILTER_BF16; AUTO beyond the deepest fp32 tile, k > 256: the alternative is the VALU
-// scan), *split = fp32 points through split-bf16 operands (the default elsewhere; NNS_FILTER_F32 keeps fp32
-// operands; filter_plan applies it at the depths where it pays).  The two operand flags are for fp32 points and
-// exclude each other.
-static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *split)
+// The filter's operand form, the one rule for nns_index_create* and nns_plan_filter.  Points that are not fp32: their
+// type's form.  fp32 points: FORM_MIXED, bf16-rounded operands (NNS_FILTER_BF16; AUTO beyond the deepest fp32 tile,
+// k > 256: the alternative is the VALU scan); FORM_F32 with NNS_FILTER_F32; FORM_SPLIT, split-bf16 operands, elsewhere
+// (filter_plan grants it at the depths where it pays).  The two operand flags are for fp32 points and exclude each other.
+static int operand_form(int k, int dtype, unsigned flags, int *form)
 {
+    const bool bf16 = dt_bf16_like(dtype);
     if ((flags & (NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE)) && bf16) {
         set_error("the operand flags (NNS_FILTER_BF16, fp32 operands, eager split, int8 pre-pass) apply to fp32 points (bf16, fp16 and int8 points use their own filter)");
         return NNS_ERR_INVALID;
@@ -236,8 +223,9 @@ static int operand_form(int k, bool bf16, unsigned flags, bool *mixed, bool *spl
         set_error("the eager-split flag selects a schedule of the split operands: not with NNS_FILTER_BF16 or the fp32-operand flag");
         return NNS_ERR_INVALID;
     }
-    *mixed = !bf16 && ((flags & NNS_FILTER_BF16) || ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && k > 256 && k <= kMaxFilterK));
-    *split = !bf16 && !*mixed && !(flags & NNS_FILTER_F32);
+    if (bf16) *form = point_type(dtype).filter_form;
+    else if ((flags & NNS_FILTER_BF16) || ((flags & NNS_PATH_MASK) == NNS_PATH_AUTO && k > 256 && k <= kMaxFilterK)) *form = FORM_MIXED;
+    else *form = (flags & NNS_FILTER_F32) ? FORM_F32 : FORM_SPLIT;
     return NNS_OK;
 }
 
@@ -253,39 +241,19 @@ static bool flag_pass_supported(int k, int dtype, unsigned flags)
 
 // what create, the query workspaces and nns_plan_filter ask filter_plan for: the shape, the dtype, operand_form's answer
 // and the two plan flags
-static FilterRequest filter_request(int k, int m, int n, int dtype, unsigned flags, bool mixed, bool split)
+static FilterRequest filter_request(int k, int m, int n, int dtype, unsigned flags, int form)
 {
-    return {k, m, n, dtype, mixed, (flags & NNS_RECORDS_PER_REF) != 0, split, (flags & NNS_FILTER_SPLIT_EAGER) != 0};
+    return {k, m, n, dtype, form, (flags & NNS_RECORDS_PER_REF) != 0, (flags & NNS_FILTER_SPLIT_EAGER) != 0};
 }
 
 static int prep_refs(nns_index *ix, hipStream_t st)
 {
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(ix->scal, 0, sizeof(DevScalars), st));
-    if (point_type(ix->dtype).i8_image) {   // (the values themselves: the filter applies the -2; no max-|v| word: nothing voids the filter)
-        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, ix->n, g.n_pad, (const int8_t *)ix->r_dev, INFINITY, ix->rimg, ix->rnorm,
-                                     &ix->scal->ymax2_bits, st, ix->dtype == DT_U8));
-        return NNS_OK;
-    }
-    if (dt_bf16_like(ix->dtype)) {
-        NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, ix->n, g.n_pad, (const uint16_t *)ix->r_dev, -2.0f, INFINITY,
-                                       ix->rimg, ix->rnorm, &ix->scal->ymax2_bits,
-                                       &ix->scal->r_maxabs_bits, st, ix->dtype == DT_F16));
-        return NNS_OK;
-    }
-    I8PreArgs pre{};
-    if (ix->i8pre) {
-        char *const r8 = (char *)ix->rimg + img_bytes(g, g.n_pad);
-        pre.img8 = (uint4 *)r8;
-        pre.seeds = (int *)(r8 + (size_t)g.n_pad * 128 + 16 * 8192);
-        pre.scal = ix->scal;
-    }
-    NNS_TRY(launch_prep_mean(ix->k, g.kt, ix->n, (const float *)ix->r_dev, ix->mean_ws, ix->mean,
-                             &ix->scal->r_maxabs_bits, st, ix->i8pre ? &ix->scal->i8_cmax_bits : nullptr));
-    NNS_TRY(launch_prep_image(ix->k, g.kt, ix->n, g.n_pad, (const float *)ix->r_dev, ix->mean, -2.0f,
-                              INFINITY, (float *)ix->rimg, ix->rnorm, &ix->scal->ymax2_bits, nullptr, st,
-                              g.lazy_img ? 3 : g.split ? 2 : ix->mixed ? 1 : 0, ix->i8pre ? &pre : nullptr));
-    return NNS_OK;
+    if (ix->dtype == DT_F32)   // (the mean that centres fp32 points, and their max-|v| word)
+        NNS_TRY(launch_prep_mean(ix->k, g.kt, ix->n, (const float *)ix->r_dev, ix->mean_ws, ix->mean,
+                                 &ix->scal->r_maxabs_bits, st, ix->i8pre ? &ix->scal->i8_cmax_bits : nullptr));
+    return launch_prep_points(g, PREP_REFS, {ix->k, ix->n, ix->r_dev, ix->mean, ix->rimg, ix->rnorm, ix->scal, ix->i8pre}, st);
 }
 
 // K2's scalars read back on `st` (one host wait), and the latch they decide: refs that void the error bound (NaN /
@@ -467,18 +435,19 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
     ix->topk_mfma = (flags & NNS_TOPK_MFMA) != 0;
     ix->last_stream = st;
     {
-        const int frc = operand_form(k, dt_bf16_like(dtype), flags, &ix->mixed, &ix->split);
+        const int frc = operand_form(k, dtype, flags, &ix->form);
         if (frc != NNS_OK) {
             delete ix;   // nothing allocated or enqueued yet
             return frc;
         }
     }
     // deepest tile of the MFMA filter (the type's; fp32 points rounded to bf16 operands: the bf16 tiles')
-    const int kmax = ix->mixed ? kMaxFilterK : pt.filter_kmax;
+    const PointType &krange = ix->form == FORM_MIXED ? kPointTypes[DT_BF16] : pt;
+    const int kmax = krange.filter_kmax;
     int path = flags & NNS_PATH_MASK;
     // crossover: from k = 8 the MFMA filter (KT = 16 / 32 tile) beats 3k VALU ops per pair; bf16 tiles
     // are at least 128 deep, so they only pay from k = 32
-    const int kmin = ix->mixed ? kPointTypes[DT_BF16].filter_kmin : pt.filter_kmin;
+    const int kmin = krange.filter_kmin;
     if (path == NNS_PATH_AUTO) path = (k >= kmin && k <= kmax) ? NNS_PATH_MFMA : NNS_PATH_EXACT;
     if (!pt.filter_kmax) path = NNS_PATH_EXACT;   // (no filter is built: check_point_flags has refused NNS_PATH_MFMA)
     if (path == NNS_PATH_MFMA && k > kmax) {
@@ -518,13 +487,13 @@ static int index_create_impl(nns_index **out, int device, int k, int n, const vo
             ix->ev_valid = true;
         }
         if (path == NNS_PATH_MFMA || ix->flag_image()) {   // (the range and top-K flags build the image whatever the 1-NN path)
-            if ((rc = filter_plan(filter_request(k, 1, n, dtype, flags, ix->mixed, ix->split), &ix->geom)) != NNS_OK) break;
+            if ((rc = filter_plan(filter_request(k, 1, n, dtype, flags, ix->form), &ix->geom)) != NNS_OK) break;
             const FilterGeom &g = ix->geom;
             size_t ws = 0;
             prep_workspace_bytes(g.kt, &ws);
             // the int8 pre-pass: a 1-NN index in the 128-deep lazy layout keeps its operands unless told not to
             ix->i8pre = path == NNS_PATH_MFMA && g.lazy_img && g.kt == 128 && filter_lazy_tile() == 16 && !(flags & NNS_FILTER_I8PRE_OFF);
-            if (pool_alloc(&ix->rimg, img_bytes(g, g.n_pad) + (ix->i8pre ? i8pre_ref_bytes(g.n_pad) : 0)) != hipSuccess ||
+            if (pool_alloc(&ix->rimg, ix->i8pre ? i8pre_layout(g, g.n_pad, true).end : img_bytes(g, g.n_pad)) != hipSuccess ||
                 pool_alloc(&ix->rnorm, norm_bytes(g, g.n_pad)) != hipSuccess ||
                 pool_alloc(&ix->mean, (size_t)g.kt * sizeof(float)) != hipSuccess ||
                 pool_alloc(&ix->mean_ws, ws) != hipSuccess ||
@@ -626,11 +595,9 @@ int nns_index_refresh(nns_index *ix, void *stream)
 //  not overlap — so once that event has fired nothing reads the old block any more.  No host wait.)
 static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists = true)
 {
-    FilterGeom g = ix->geom;
     FilterGeom gq{};
-    NNS_TRY(filter_plan(filter_request(ix->k, m, ix->n, ix->dtype, ix->flags, ix->mixed, ix->split), &gq));
+    NNS_TRY(filter_plan(filter_request(ix->k, m, ix->n, ix->dtype, ix->flags, ix->form), &gq));
     ix->geom = gq;   // same kt / n_pad / total_slots; m-dependent grid now filled in
-    (void)g;
     if (gq.m_pad > ix->m_cap) {
         void *const old[] = {ix->qimg, ix->qnorm, ix->amb_list, ix->multi_list};
         pool_free_after(old, 4, st);   // an earlier search may still read them
@@ -639,7 +606,7 @@ static int ensure_query_ws(nns_index *ix, int m, hipStream_t st, bool with_lists
         ix->amb_list = nullptr;
         ix->multi_list = nullptr;
         ix->m_cap = 0;
-        if (pool_alloc(&ix->qimg, img_bytes(gq, gq.m_pad) + (ix->i8pre ? i8pre_query_bytes(gq.m_pad) : 0)) != hipSuccess ||
+        if (pool_alloc(&ix->qimg, ix->i8pre ? i8pre_layout(gq, gq.m_pad, false).end : img_bytes(gq, gq.m_pad)) != hipSuccess ||
             pool_alloc(&ix->qnorm, (size_t)gq.m_pad * sizeof(float)) != hipSuccess ||
             pool_alloc(&ix->amb_list, (size_t)gq.m_pad * sizeof(int)) != hipSuccess ||
             pool_alloc(&ix->multi_list, (size_t)gq.m_pad * sizeof(int)) != hipSuccess) {
@@ -779,32 +746,15 @@ static int index_search_impl(nns_index *ix, int m, const void *q_dev, int dtype,
     const bool use_pre = ix->i8pre && g.lazy && g.kt == 128;
     FilterPreArgs fpre{};
     if (use_pre) {
-        const char *const r8 = (const char *)ix->rimg + img_bytes(g, g.n_pad);
-        const char *const q8 = (const char *)ix->qimg + img_bytes(g, g.m_pad);
-        fpre.rimg8 = r8;
-        fpre.rseed = (const int *)(r8 + (size_t)g.n_pad * 128 + 16 * 8192);
-        fpre.q8 = (const float4 *)q8;
-        fpre.qb8 = (const float *)(q8 + (size_t)g.m_pad * 128);
+        const I8PreLayout rl = i8pre_layout(g, g.n_pad, true), ql = i8pre_layout(g, g.m_pad, false);
+        fpre.rimg8 = (const char *)ix->rimg + rl.img8;
+        fpre.rseed = (const int *)((const char *)ix->rimg + rl.aux);
+        fpre.q8 = (const float4 *)((const char *)ix->qimg + ql.img8);
+        fpre.qb8 = (const float *)((const char *)ix->qimg + ql.aux);
         fpre.m = m;
         fpre.force = (ix->flags & NNS_FILTER_I8PRE_FORCE) ? 1 : 0;
     }
-    if (point_type(dtype).i8_image)
-        NNS_TRY(launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st,
-                                     dtype == DT_U8));
-    else if (dt_bf16_like(dtype))
-        NNS_TRY(launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg, ix->qnorm,
-                                       nullptr, &ix->scal->q_maxabs_bits, st, dtype == DT_F16));
-    else {
-        I8PreArgs qpre{};
-        if (use_pre) {
-            qpre.img8 = (uint4 *)fpre.q8;
-            qpre.bound = (float *)fpre.qb8;
-            qpre.scal = ix->scal;
-        }
-        NNS_TRY(launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f,
-                                  (float *)ix->qimg, ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st,
-                                  g.split ? 2 : ix->mixed ? 1 : 0, use_pre ? &qpre : nullptr));
-    }
+    NNS_TRY(launch_prep_points(g, PREP_QUERIES, {ix->k, m, q_dev, ix->mean, ix->qimg, ix->qnorm, ix->scal, use_pre}, st));
     if (prof) (void)hipEventRecord(ix->evr[ix->ev_slot][EV_QPREP], st);
     NNS_TRY(launch_filter(g, ix->qimg, ix->rimg, ix->rnorm, ix->qnorm, ix->scal, ix->lists, ix->counts, st,
                           use_pre ? &fpre : nullptr));
@@ -1116,13 +1066,7 @@ static int range_mfma_prep_queries(nns_index *ix, int m, const void *q_dev, hipS
     NNS_TRY(ensure_query_ws(ix, m, st, false));
     const FilterGeom &g = ix->geom;
     NNS_HIP(hipMemsetAsync(&ix->scal->q_maxabs_bits, 0, sizeof(unsigned) + 2 * sizeof(int), st));
-    if (ix->dtype == DT_U8)   // (the biased int8 image and its norms, as the 1-NN search of a uint8 index prepares them)
-        return launch_prep_image_i8(g.kt, ix->k, m, g.m_pad, (const int8_t *)q_dev, 0.0f, ix->qimg, ix->qnorm, nullptr, st, true);
-    if (dt_bf16_like(ix->dtype))   // (the order-1 image and the uncentred norms, as the 1-NN search of a bf16 index prepares them)
-        return launch_prep_image_bf16(kBf16ImageOrder, g.kt, ix->k, m, g.m_pad, (const uint16_t *)q_dev, 1.0f, 0.0f, ix->qimg,
-                                      ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st);
-    return launch_prep_image(ix->k, g.kt, m, g.m_pad, (const float *)q_dev, ix->mean, 1.0f, 0.0f, (float *)ix->qimg,
-                             ix->qnorm, nullptr, &ix->scal->q_maxabs_bits, st, 2);
+    return launch_prep_points(g, PREP_QUERIES, {ix->k, m, q_dev, ix->mean, ix->qimg, ix->qnorm, ix->scal, false}, st);
 }
 
 // refs_bad as of the last refresh: if the index was refreshed since the flag was latched, read K2's max-|v| word (one
@@ -1489,9 +1433,7 @@ int nns_i8pre_bound(float s, float ex2, float q82, float r8max2, float eymax2, f
 int nns_index_filter_form(nns_index *ix, int *form_out)
 {
     if (!ix || !form_out) return NNS_ERR_INVALID;
-    const FilterGeom &g = ix->geom;
-    // = the tau mode (5, int8 points: no tau mode of its own, the margin is mode 1's)
-    *form_out = ix->path != NNS_PATH_MFMA ? -1 : g.i8 ? 5 : g.f16 ? 4 : g.mixed ? 2 : g.split ? 3 : g.bf16;
+    *form_out = ix->path != NNS_PATH_MFMA ? -1 : ix->geom.form;   // (FORM_*: the public codes)
     return NNS_OK;
 }
 
@@ -1745,8 +1687,8 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
     if (!out || out_len < 12 || k <= 0 || m <= 0 || n <= 0) return NNS_ERR_INVALID;
     const int dtype = bf16_points;
     const PointType &pt = point_type(dtype);
-    bool mixed = false, split = false;
-    NNS_TRY(operand_form(k, dt_bf16_like(dtype), flags, &mixed, &split));
+    int form = FORM_NONE;
+    NNS_TRY(operand_form(k, dtype, flags, &form));
     if (!pt.filter_kmax) {
         set_error("nns_plan_filter: no MFMA filter is built for %s points", pt.name);
         return NNS_ERR_UNSUPPORTED;
@@ -1761,9 +1703,11 @@ int nns_plan_filter(int k, int m, int n, int bf16_points, unsigned flags, int *o
         return NNS_ERR_UNSUPPORTED;
     }
     FilterGeom g{};
-    NNS_TRY(filter_plan(filter_request(k, m, n, dtype, flags, mixed, split), &g));
-    const int v[16] = {g.kt, g.bf16, g.mixed, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits, g.slots_per_split,
-                       g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec, g.split, g.lazy};
+    NNS_TRY(filter_plan(filter_request(k, m, n, dtype, flags, form), &g));
+    // (fields 1, 2 and 14, `bf16`, `mixed` and `split`, are the granted form's)
+    const int v[16] = {g.kt, kFilterForms[g.form].bf16, g.form == FORM_MIXED, g.lpq, g.m_pad, g.n_pad, g.total_slots, g.splits,
+                       g.slots_per_split, g.qgroups, g.slot_pts, g.m_pad / g.qgroups, g.share_thr, g.tile_rec,
+                       g.form == FORM_SPLIT, g.lazy};
     memcpy(out, v, (out_len >= 16 ? 16 : out_len >= 15 ? 15 : out_len >= 14 ? 14 : 12) * sizeof(int));
     return NNS_OK;
 }
@@ -1883,7 +1827,7 @@ static bool chunked_pays(int k, int64_t m, int64_t n, int dtype, unsigned flags,
     if (exact) {
         est_s = 3.0 * k * (double)m * (double)n / 45e12;
     } else {
-        int kt = pt.i8_image ? 256 : bf16 ? 128 : 16;
+        int kt = pt.filter_form == FORM_I8 ? 256 : bf16 ? 128 : 16;
         while (kt < k) kt *= 2;
         const bool bf16_ops = bf16 || k > 256 || (flags & NNS_FILTER_BF16);
         // fp32 points: split-bf16 operands unless NNS_FILTER_F32 (3 bf16 MFMAs per 16 dims: ~5x the fp32 operands' rate)
@@ -2364,7 +2308,7 @@ int nns_warmup(int device)
         if (sh[3] == DT_B1) {
             // the same numbers' fp32 bit patterns as words (q and r hold at least sh[0] * sh[1] and sh[0] * sh[2] floats)
             rc = search_host_impl(sh[0], sh[1], sh[2], q, r, DT_B1, idx, nullptr, 1, (unsigned)sh[4], device);
-        } else if (point_type(sh[3]).i8_image) {
+        } else if (point_type(sh[3]).filter_form == FORM_I8) {
             // the same numbers (in [0, 1)) as int8 values -128 .. 127 (uint8 points: 0 .. 255)
             const int off = sh[3] == DT_U8 ? 0 : 128;
             int8_t *qb = (int8_t *)malloc((size_t)sh[0] * sh[1]);

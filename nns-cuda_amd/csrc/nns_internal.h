@@ -202,6 +202,9 @@ __device__ __forceinline__ float v0_step(float sum, float q, float r)
 // fp32, bf16 bit patterns, IEEE binary16 (fp16) bit patterns, int8 values, packed bits (one element = one 32-bit word;
 // below the C-ABI entry points the dimension k counts words), uint8 values.
 enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3, DT_B1 = 4, DT_U8 = 5, DT_COUNT = 6 };
+// The operand form of an MFMA filter search (kFilterForms below holds a row per form): the values are the public codes of
+// nns_index_filter_form.  FORM_NONE: a point type without a filter
+enum { FORM_NONE = -1, FORM_F32 = 0, FORM_BF16 = 1, FORM_MIXED = 2, FORM_SPLIT = 3, FORM_F16 = 4, FORM_I8 = 5, FORM_COUNT };
 // What is a fact about a point type, not about a call.  A k range of {0, 0} means "none is built".  The flag masks are
 // what index_create (and, with whole_calls_check, the whole calls) refuse before the device is looked up, with the
 // message "<entry point>: <text> (flags 0x..)"; check_point_flags (nns_api.hip) is the one reader.
@@ -209,7 +212,8 @@ struct PointType {
     const char *infix;             // of the C ABI's names: nns_search_<infix>_ex, nns_index_create_<infix>
     const char *name;              // in messages
     int bytes;                     // of one element
-    bool i8_image;                 // the int8 operand image, OpI8's filter and its plans (uint8: biased by 128 in K2)
+    int filter_form;               // the form the type's points take by default (fp32: operand_form chooses by flags and k;
+                                   // FORM_I8: the int8 operand image, uint8 points biased by 128 in K2)
     int filter_kmin, filter_kmax;  // the MFMA filter: AUTO takes it inside this range, NNS_PATH_MFMA up to filter_kmax
     int flag_kmin, flag_kmax;      // the flag passes (NNS_RANGE_MFMA, NNS_TOPK_MFMA)
     unsigned invalid_flags;        // answered NNS_ERR_INVALID ...
@@ -224,23 +228,23 @@ struct PointType {
 constexpr unsigned kOperandFlags = NNS_FILTER_BF16 | NNS_FILTER_F32 | NNS_FILTER_SPLIT_EAGER;
 constexpr unsigned kFlagPassFlags = NNS_RANGE_MFMA | NNS_TOPK_MFMA;
 constexpr PointType kPointTypes[DT_COUNT] = {
-    {"f32", "fp32", 4, false, 8, 256, 8, 256, 0, nullptr, 0, nullptr, false, false},   // (bf16-rounded operands: to 1024)
-    {"bf16", "bf16", 2, false, 32, 1024, 32, 256, 0, nullptr, 0, nullptr, false, false},
-    {"f16", "fp16", 2, false, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points", kFlagPassFlags,
+    {"f32", "fp32", 4, FORM_SPLIT, 8, 256, 8, 256, 0, nullptr, 0, nullptr, false, false},   // (bf16-rounded operands: to 1024)
+    {"bf16", "bf16", 2, FORM_BF16, 32, 1024, 32, 256, 0, nullptr, 0, nullptr, false, false},
+    {"f16", "fp16", 2, FORM_F16, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points", kFlagPassFlags,
      "the range-MFMA and top-K MFMA flags are not built for fp16 points", false, false},
-    {"i8", "int8", 1, true, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
+    {"i8", "int8", 1, FORM_I8, 32, 256, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
      kFlagPassFlags | NNS_REFS_SOA,
      "the range-MFMA and top-K MFMA flags and dimension-major refs are not built for int8 points", true, false},
-    {"b1", "binary", 4, false, 0, 0, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
+    {"b1", "binary", 4, FORM_NONE, 0, 0, 0, 0, kOperandFlags, "the operand flags apply to fp32 points",
      kFlagPassFlags | NNS_REFS_SOA | NNS_RECORDS_PER_REF,
      "no MFMA filter, flag pass or dimension-major form is built for binary points", true, false},
-    {"u8", "uint8", 1, true, 32, 256, 32, 256, kOperandFlags | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE,
+    {"u8", "uint8", 1, FORM_I8, 32, 256, 32, 256, kOperandFlags | NNS_FILTER_I8PRE_OFF | NNS_FILTER_I8PRE_FORCE,
      "the operand flags apply to fp32 points, not to uint8 points", NNS_REFS_SOA,
      "dimension-major refs are not built for uint8 points", true, true},
 };
 // (a code the ABI does not define counts as bf16 points, as it did when the rules were `dtype != 0`)
 inline const PointType &point_type(int dtype) { return kPointTypes[(unsigned)dtype < DT_COUNT ? dtype : DT_BF16]; }
-// The points are not fp32: they are their own filter operands on the bf16 tile geometry (FilterGeom::bf16), the operand
+// The points are not fp32: they are their own filter operands on the bf16 tile geometry, the operand
 // flags do not apply, and the fp32-only exact kernels (K1a, K1f, K1c) are not theirs (exact_plan's `bf16`)
 inline bool dt_bf16_like(int dtype) { return dtype != DT_F32; }
 // uint16_t means bf16 in every overload (pt_ld1, pt_ld4, widen8, load_f, load_f4, K2); fp16 bits travel as f16_t
@@ -568,6 +572,22 @@ __device__ __forceinline__ void dma4(const void *g, unsigned lds_byte)
 // (v_mfma_f32_32x32x2_f32: lane supplies A[i = lane&31][k = lane>>5]).
 constexpr int kBlockPts = 32;
 
+// Blocks and ring slots of the filter (filter_main's constants, filter_plan's paddings).  A block of 32 refs is spb 1 KiB
+// fragment steps, a ring slot sps steps (32; the lazy operators' hi-only slots 16).  A block that divides the slot: one
+// slot, sps / spb whole blocks.  A deeper block straddles slots with a super-period of lcm(spb, 32) steps: 64 steps
+// (1024-deep): 2 slots = 1 block; 48 (768-deep): 3 slots = 2 blocks; 40 (640-deep): 5 = 4; 24 (384-deep): 3 = 4.
+struct RingGeom {
+    bool deep;                     // the block does not divide the slot
+    int slots, blocks, slot_refs;  // of a super-period; 32 * blocks: the norms that travel with a slot, the refs' padding unit
+};
+__host__ __device__ constexpr RingGeom ring_geom(int spb, int sps = 32)
+{
+    const bool deep = sps % spb != 0;
+    const int g = spb % 32 == 0 ? 32 : (spb % 16 == 0 ? 16 : (spb % 8 == 0 ? 8 : 1));
+    const int blocks = deep ? 32 / g : sps / spb;
+    return {deep, deep ? spb / g : 1, blocks, 32 * blocks};
+}
+
 // The bf16 filter at KT 128 / 256 / 512 runs v_mfma_f32_16x16x32_bf16 on 16x16 tiles (the chip clocks ~14 % higher on
 // it under load than on the 32x32x16 form).  That fixes the bf16 tile-image order, 1 (prep_kernels.hip), and the four
 // lanes a query's candidate lists live on (FilterGeom.lpq, finalize.hip).
@@ -618,16 +638,11 @@ __host__ __device__ constexpr bool pre_cadence_ok(int depth, int ahead, int grou
 }
 
 struct FilterGeom {
-    int bf16;             // 1: bf16 operands (K4), 0: fp32 operands (K3)
-    int f16;              // 1: fp16 points on v_mfma_f32_16x16x32_f16 (OpF16T: the bf16 geometry, bf16 = 1 too; TAU_F16)
-    int i8;               // 1: int8 points on v_mfma_i32_16x16x64_i8 (OpI8: kt = 256 on the 128-deep bf16 geometry, bf16 = 1
-                          // too; exact integer scores, TAU_BF16's margin, filter form 5)
-    int u8;               // 1: the points are uint8 (i8 = 1 too: K2 biases them by 128 into the int8 image; K5 reads u8_t)
+    int dtype;            // the points' type (DT_*): what K2 and K5 read
+    int form;             // the operand form the plan grants (FORM_*, kFilterForms): SPLIT only at the depths split_depth names
     int lpq;              // lanes (= private candidate lists) per query and split: 2, or 4 with 16x16 tiles
-    int mixed;            // 1: fp32 points through the bf16 filter (NNS_FILTER_BF16); bf16 = 1 then too
-    int split;            // 1: fp32 points through split-bf16 operands (OpSplitT; bf16 = 0: the fp32 tile's geometry)
-    int lazy;             // split = 1: the lazy schedule (OpLazySplitT: cross products only on tiles near the threshold)
-    int lazy_img;         // split = 1: the ref image is in the lazy layout (hi fragments | lo fragments; K2 form 3)
+    int lazy;             // FORM_SPLIT: the lazy schedule (OpLazySplitT: cross products only on tiles near the threshold)
+    int lazy_img;         // FORM_SPLIT: the ref image is in the lazy layout (hi fragments | lo fragments; K2 form 3)
     int kt;               // K of the tile (k padded up with zeros)
     int spb;              // 1 KiB fragment steps per 32-ref block of the tile image (the operator's kSPB; a lazy search:
                           // its eager twin's — hi and lo fragments — which is how the image is sized either way)
@@ -679,6 +694,46 @@ enum { TAU_F32 = 0, TAU_BF16 = 1, TAU_MIXED = 2, TAU_SPLIT = 3, TAU_F16 = 4 };
 // The chains of nns_selftest_mfma (its own numbering over the ABI: 4 is the lazy order there): fp32, bf16 32x32x16, bf16
 // 16x16x32, the split chain, the split chain in the lazy filter's order, f16 16x16x32, i8 16x16x64
 enum { ST_F32 = 0, ST_BF16 = 1, ST_BF16_T16 = 2, ST_SPLIT = 3, ST_LAZY = 4, ST_F16 = 5, ST_I8 = 6 };
+
+// What is a fact about an operand form (FORM_*), one row each; FilterGeom::form indexes it (DESIGN, "The operand forms").
+// I8 has no tau mode of its own: its scores are exact integers, so TAU_BF16's margin is a valid one.
+enum { K2_F32, K2_BF16, K2_I8 };   // K2's three image kernels: fp32 points (centred), 16-bit points, 8-bit points
+struct FilterForm {
+    const char *name;     // in messages
+    int img_bytes;        // of one dimension of a point's tile-image row
+    int tau_mode;         // TAU_*: launch_filter and K5 agree on it
+    int bf16;             // nns_plan_filter's field 1: the bf16 tiles' geometry
+    int ladder[8];        // the tile depths, ascending, 0 behind the last: a plan takes the first that holds k
+    int k2_image;         // K2_*
+    int k2_form;          // K2_F32: launch_prep_image's form (the refs of a lazy-layout index take 3 instead of 2)
+};
+constexpr FilterForm kFilterForms[FORM_COUNT] = {
+    {"fp32", 4, TAU_F32, 0, {16, 32, 64, 128, 256}, K2_F32, 0},
+    {"bf16", 2, TAU_BF16, 1, {128, 256, 384, 512, 640, 768, 1024}, K2_BF16, 0},
+    {"mixed", 2, TAU_MIXED, 1, {128, 256, 384, 512, 640, 768, 1024}, K2_F32, 1},
+    {"split", 4, TAU_SPLIT, 0, {16, 32, 64, 128, 256}, K2_F32, 2},
+    {"fp16", 2, TAU_F16, 1, {128, 256}, K2_BF16, 0},
+    {"int8", 1, TAU_BF16, 1, {256}, K2_I8, 0},
+};
+
+// ---- sizes of the images and what sits beside them (nns_api.hip allocates, K2 and the filter address) -----------------
+// one point of a tile image
+inline size_t img_row_bytes(const FilterGeom &g) { return (size_t)g.kt * kFilterForms[g.form].img_bytes; }
+// The filter's ring DMA runs up to three slots (32 KiB of image, slot_pts norms each) past the last one without a
+// bounds branch: images and norm arrays carry that much padding (+ the over-read of a 128-norm piece)
+inline size_t img_bytes(const FilterGeom &g, int pts_pad) { return (size_t)pts_pad * img_row_bytes(g) + 3 * 32768 + 4096; }
+inline size_t norm_bytes(const FilterGeom &g, int pts_pad) { return ((size_t)pts_pad + 3 * g.slot_pts + 256) * sizeof(float); }
+// The int8 pre-pass's operands sit behind the image they go with, in the same allocation, at these byte offsets from the
+// image's start.  Refs: the int8 region (128 bytes per ref; its ring runs up to 16 slots of 8 KiB past the end), then one
+// i32 seed per ref (+ 16 slots of 64).  Queries: the q8 image (128 bytes per query), then one fp32 bound per query.
+struct I8PreLayout {
+    size_t img8, aux, end;   // the int8 image; the seeds (refs) or bounds (queries); the end of the allocation
+};
+inline I8PreLayout i8pre_layout(const FilterGeom &g, int pts_pad, bool refs)
+{
+    const size_t img8 = img_bytes(g, pts_pad), aux = img8 + (size_t)pts_pad * 128 + (refs ? 16 * 8192 : 0);
+    return {img8, aux, aux + (refs ? ((size_t)pts_pad + 16 * 64) * sizeof(int) : (size_t)pts_pad * sizeof(float))};
+}
 __host__ __device__ inline TauConsts tau_consts(int kt, float qnorm2, float ymax2, int mode)
 {
     const bool bf16 = mode != TAU_F32;
@@ -957,32 +1012,25 @@ int prep_workspace_bytes(int kt, size_t *bytes);
 // centred |coordinate|, rounded up, in that word (uint-ordered max: zero it first)
 int launch_prep_mean(int k, int kt, int n, const float *r, double *partial_ws,
                      float *mean, unsigned *maxabs_bits, hipStream_t st, unsigned *cmax_bits = nullptr);
-int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts,
-                      const float *mean, float scale, float pad_norm,
-                      float *img, float *norms, unsigned *max_norm_bits,
-                      unsigned *maxabs_bits, hipStream_t st, int form = 0, const I8PreArgs *i8 = nullptr);
-
-// form: 0 fp32 image, 1 bf16-rounded operands, 2 split-bf16 operands (hi, lo fragment per k-step), 3 the same values in
-// the lazy layout: the hi fragments of all blocks ([npts_pad / 32][kt / 16] KiB), then the lo fragments likewise
-// bf16 points (raw uint16 bits) -> bf16 tile image [blk][16][64 lanes][8 bf16], value * scale
-// (scale = 1 or -2, exact), fp32 norms of the UNcentred points, max-|v| word
+// K2 on one point set of an index whose geometry is g: the tile image, the norms and the scalar words of that side.
+// Refs: values scaled by -2 (the int8 image holds the values themselves: -2 v does not fit, the filter applies it), padding
+// refs' norm +INF, the largest norm into scal->ymax2_bits and (16-bit points; fp32 points: launch_prep_mean has written it)
+// the largest |value| into scal->r_maxabs_bits; the fp32 image of a lazy-layout index in the lazy layout.  Queries: scale 1,
+// padding norm 0, the largest |value| into scal->q_maxabs_bits.  8-bit points have no max-|value| word: none voids the filter.
+enum PrepSide { PREP_REFS, PREP_QUERIES };
+struct PrepPoints {
+    int k, npts;          // dimensions and points of the set (padded to g.n_pad / g.m_pad)
+    const void *pts;      // [npts][k] of g.dtype
+    const float *mean;    // fp32 points: the refs' mean (launch_prep_mean)
+    void *img;            // the tile image; i8pre: the int8 pre-pass's operands behind it (i8pre_layout) are written too
+    float *norms;
+    DevScalars *scal;
+    bool i8pre;
+};
+int launch_prep_points(const FilterGeom &g, PrepSide side, const PrepPoints &a, hipStream_t st);
 // dimension-major [k][n] -> point-major [n][k] (the inverse of the reference's mat_inv_kernel,
 // core.cu:293-306); esz = 4 (fp32) or 2 (bf16 bits)
 int launch_soa_to_aos(int k, int n, const void *src, void *dst, int esz, hipStream_t st);
-// order: 0 = 32x32x16 operands, 1 = 16x16x32 operands (fragment 8 * tile + k-step)
-// f16: pts are fp16 bit patterns -> the same image of binary16 operands (order 1, kt = 128 / 256), value * scale narrowed
-// with a real conversion; norms and the max-|v| word from the widened values
-int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale,
-                           float pad_norm, void *img, float *norms, unsigned *max_norm_bits,
-                           unsigned *maxabs_bits, hipStream_t st, bool f16 = false);
-// int8 points: the operand image of v_mfma_i32_16x16x64_i8 at kt = 256 (1 KiB fragment 4 * tile + k-step: lane l holds
-// dims 64 ks + 16 (l >> 4) .. + 15 of point 16 tile + (l & 15)), the VALUES themselves (no scale: -2 v does not fit int8,
-// the filter applies it), zero-padded; norms = the exact integer |v|^2 as fp32 (pad points: pad_norm); max_norm_bits as
-// the bf16 form's.  No max-|v| word: int8 has no value that voids the filter.
-// bias (uint8 points): the image byte is u ^ 0x80, read as int8 u - 128; the norm is the sum of (u - 128)^2 over the k real
-// dimensions, the padded dimensions hold 0 AFTER the bias
-int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img,
-                         float *norms, unsigned *max_norm_bits, hipStream_t st, bool bias = false);
 
 // filter_mfma.hip (K3 fp32 / K4 bf16)
 // the int8 pre-pass's operands beside the lazy image (K2, I8PreArgs): given to launch_filter, a lazy search at kt = 128
@@ -995,22 +1043,17 @@ struct FilterPreArgs {
     int m;                // real queries of the search
     int force;            // NNS_FILTER_I8PRE_FORCE: run the pre-pass whatever the count says
 };
-// What a filter plan is asked for.  mixed / split: operand_form's answer for fp32 points; per_ref: NNS_RECORDS_PER_REF;
-// split_eager (NNS_FILTER_SPLIT_EAGER): the eager split kernels and image layout at every depth.  By dtype:
-// DT_F16 — the bf16 geometry at kt = 128 / 256, the f16 operators; k > 256: unsupported
-// DT_I8 — kt = 256 for every k <= 256 on the 128-deep bf16 geometry (a 16x16x64 fragment of bytes = a 16x16x32 fragment
-// of bf16: 8 fragments per 32-ref block either way); k > 256: unsupported
-// DT_U8 — int8's plan field for field; only g->u8 differs
+// What a filter plan is asked for.  form: the type's own (point_type(dtype).filter_form), or operand_form's answer for
+// fp32 points; the plan's form is what is granted (SPLIT becomes F32 at a depth split_depth does not name); k beyond the
+// form's deepest tile: unsupported.  per_ref: NNS_RECORDS_PER_REF; split_eager (NNS_FILTER_SPLIT_EAGER): the eager split
+// kernels and image layout at every depth.  uint8 points: int8's plan field for field; only g->dtype differs
 struct FilterRequest {
-    int k, m, n, dtype;
-    bool mixed, per_ref, split, split_eager;
+    int k, m, n, dtype, form;
+    bool per_ref, split_eager;
 };
 int filter_plan(const FilterRequest &rq, FilterGeom *g);
 // the tau mode of the search that geometry g runs (launch_filter and K5 agree on it)
-inline int filter_tau_mode(const FilterGeom &g)
-{
-    return g.f16 ? TAU_F16 : g.mixed ? TAU_MIXED : g.split ? TAU_SPLIT : g.bf16 ? TAU_BF16 : TAU_F32;
-}
+inline int filter_tau_mode(const FilterGeom &g) { return kFilterForms[g.form].tau_mode; }
 // rimg of a lazy-layout index (g.lazy_img): hi region, then the lo region at + n_pad * kt * 2 bytes
 int launch_filter(const FilterGeom &g, const void *qimg, const void *rimg, const float *rnorm,
                   const float *qnorm, const DevScalars *scal, CandEntry *lists, int *counts,

@@ -638,9 +638,11 @@ __global__ __launch_bounds__(256) void image_deep_kernel(int k, int npts, const 
     if ((tid & 63) == 0 && maxabs_bits) max_word(maxabs_bits, mx);
 }
 
-int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, const float *mean,
-                      float scale, float pad_norm, float *img, float *norms,
-                      unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form, const I8PreArgs *i8)
+// form: 0 fp32 image, 1 bf16-rounded operands, 2 split-bf16 operands (hi, lo fragment per k-step), 3 the same values in
+// the lazy layout: the hi fragments of all blocks ([npts_pad / 32][kt / 16] KiB), then the lo fragments likewise
+static int launch_prep_image(int k, int kt, int npts, int npts_pad, const float *pts, const float *mean,
+                             float scale, float pad_norm, float *img, float *norms,
+                             unsigned *max_norm_bits, unsigned *maxabs_bits, hipStream_t st, int form, const I8PreArgs *i8)
 {
     const int blocks = npts_pad / 32;
     if (i8) {   // refs (form 3) or queries (form 2) of a 128-deep lazy index, with the int8 pre-pass's operands
@@ -882,9 +884,10 @@ __global__ __launch_bounds__(256) void image_bf16_kernel(int order, int k, int n
     if ((tid & 63) == 0 && maxabs_bits) max_word(maxabs_bits, mx);
 }
 
-int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale, float pad_norm,
-                           void *img, float *norms, unsigned *max_norm_bits, unsigned *maxabs_bits,
-                           hipStream_t st, bool f16)
+// order: 0 = 32x32x16 operands, 1 = 16x16x32 operands; f16: pts are fp16 bit patterns (order 1, kt = 128 / 256)
+static int launch_prep_image_bf16(int order, int kt, int k, int npts, int npts_pad, const uint16_t *pts, float scale,
+                                  float pad_norm, void *img, float *norms, unsigned *max_norm_bits, unsigned *maxabs_bits,
+                                  hipStream_t st, bool f16)
 {
     if (f16) {   // fp16 points: the order-1 image at the depths of the 16x16x32 tiles
         if (order == 1 && kt == 256)
@@ -1016,8 +1019,9 @@ __global__ __launch_bounds__(256) void image_i8_kernel(int k, int npts, const in
     }
 }
 
-int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img, float *norms,
-                         unsigned *max_norm_bits, hipStream_t st, bool bias)
+// bias (uint8 points): the image byte is u ^ 0x80, read as int8 u - 128; the padded dimensions hold 0 AFTER the bias
+static int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pts, float pad_norm, void *img,
+                                float *norms, unsigned *max_norm_bits, hipStream_t st, bool bias)
 {
     if (kt != 256 || k > kt) {
         set_error("prep: unsupported int8 tile K %d (k = %d)", kt, k);
@@ -1031,6 +1035,36 @@ int launch_prep_image_i8(int kt, int k, int npts, int npts_pad, const int8_t *pt
                            (uint4 *)img, norms, max_norm_bits);
     NNS_HIP(hipGetLastError());
     return NNS_OK;
+}
+
+// K2 on the refs or the queries of geometry g (nns_internal.h: what each side writes)
+int launch_prep_points(const FilterGeom &g, PrepSide side, const PrepPoints &a, hipStream_t st)
+{
+    const bool refs = side == PREP_REFS;
+    const FilterForm &f = kFilterForms[g.form];
+    const int pad = refs ? g.n_pad : g.m_pad;
+    const float scale = refs ? -2.0f : 1.0f, pad_norm = refs ? INFINITY : 0.0f;
+    unsigned *const max_norm = refs ? &a.scal->ymax2_bits : nullptr;
+    if (f.k2_image == K2_I8)
+        return launch_prep_image_i8(g.kt, a.k, a.npts, pad, (const int8_t *)a.pts, pad_norm, a.img, a.norms, max_norm, st,
+                                    g.dtype == DT_U8);
+    // (the image order follows the tile: 16x16 tiles read order 1 = kBf16ImageOrder, which is every geometry the flag
+    //  passes accept, so their K2 on the queries is the 1-NN search's)
+    if (f.k2_image == K2_BF16)
+        return launch_prep_image_bf16(g.lpq == 4 ? 1 : 0, g.kt, a.k, a.npts, pad, (const uint16_t *)a.pts, scale, pad_norm, a.img,
+                                      a.norms, max_norm, refs ? &a.scal->r_maxabs_bits : &a.scal->q_maxabs_bits, st,
+                                      g.form == FORM_F16);
+    I8PreArgs pre{};
+    if (a.i8pre) {
+        const I8PreLayout lay = i8pre_layout(g, pad, refs);
+        pre.img8 = (uint4 *)((char *)a.img + lay.img8);
+        if (refs) pre.seeds = (int *)((char *)a.img + lay.aux);
+        else pre.bound = (float *)((char *)a.img + lay.aux);
+        pre.scal = a.scal;
+    }
+    return launch_prep_image(a.k, g.kt, a.npts, pad, (const float *)a.pts, a.mean, scale, pad_norm, (float *)a.img, a.norms,
+                             max_norm, refs ? nullptr : &a.scal->q_maxabs_bits, st, refs && g.lazy_img ? 3 : f.k2_form,
+                             a.i8pre ? &pre : nullptr);
 }
 
 // ---- SoA -> AoS (NNS_REFS_SOA) --------------------------------------------------------------

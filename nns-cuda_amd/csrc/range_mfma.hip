@@ -561,8 +561,12 @@ int range_mfma_plan(int k, int m, int n, bool split_eager, RangeMfmaPlan *p, int
         return NNS_ERR_UNSUPPORTED;
     }
     FilterGeom g{};
-    NNS_TRY(filter_plan({k, m, n, dtype, false, false, !bf16, split_eager}, &g));
-    if (bf16 ? (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && (u8 || g.spb != 16))) : !g.split) {
+    FilterRequest rq{};
+    rq.k = k, rq.m = m, rq.n = n, rq.dtype = dtype, rq.form = pt.filter_form, rq.split_eager = split_eager;
+    NNS_TRY(filter_plan(rq, &g));
+    // (the form asked for must be the one granted; the 16x16 flag kernels: OpBF16K128 / OpBF16's geometry, uint8 the former's)
+    if (g.form != rq.form ||
+        (bf16 && (g.lpq != 4 || g.qb != kRmBf16QB || g.waves != kRmWaves || (g.spb != 8 && (u8 || g.spb != 16))))) {
         set_error("the range-MFMA flag: no %s tile for k = %d", u8 ? "16x16x64 int8" : bf16 ? "16x16x32 bf16" : "split-bf16", k);
         return NNS_ERR_UNSUPPORTED;
     }
